@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- GBP iterations/s on the synthetic 500-cam x 100k-landmark x 1M-factor BA graph.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one FactorGraph.synchronous_iteration(robustify=True, local_relin=True) (gbp/gbp.py:86-92) over the whole
 graph, inputs resident in HBM.  N > 1 shards the graph by landmark across N ranks, one process per GPU, one exchange of the
@@ -10,7 +10,15 @@ the ranks' mailboxes over xGMI with no collective call (--exchange; the default 
 the other beside it); the total work is fixed, so scaling is "strong".  Started without torchrun, `--gpus N` spawns its own N ranks (re-exec under
 torch.distributed.run on 127.0.0.1); started under torchrun it uses the ranks it is given.  Rank 0 prints ONE JSON line.
 
-Timing protocol.  Every batch starts from the same state -- the graph right after generate_priors_var +
+A plain run does only what its headline figure needs: it sets up the graph (generate_priors_var + update_all_beliefs), brings the
+GPU's clocks up with ~SPIN_UP_S of throw-away replays, restores the state, runs W untimed sweeps, then EXACTLY K timed sweeps
+bracketed by a barrier + device synchronisation on both sides (max over ranks), and prints the line: `value` = K / that time,
+`ms_per_step` = that time / K.  `--dump-outputs DIR` writes what the last timed sweep left (timed_outputs(): beliefs, means and ARE,
+float64) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared array by array.
+Everything below -- the repeated batches, the instrumented replays, the parity check, the CPU baselines, the HBM-bound size and, for
+N > 1, the prediction and the secondary workload -- runs with `--full` only.
+
+Timing protocol of --full.  Every batch starts from the same state -- the graph right after generate_priors_var +
 update_all_beliefs, restored from a device-resident checkpoint -- runs W untimed sweeps and then EXACTLY K timed sweeps bracketed by a
 barrier + device synchronisation on both sides (max over ranks).  Batches are repeated until >= 0.5 s have been timed;
 `value` = K / median batch time, the minimum is reported beside it.  One extra, untimed replay of the same batch is
@@ -44,6 +52,7 @@ sys.path.insert(0, REPO)
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md:35
 COPY_CEILING_GBS = 6290.0      # measured float4 copy on MI355X, same line of the guide: what a pure streaming kernel reaches
 MIN_TIMED_S = 0.5
+SPIN_UP_S = 0.3               # plain run: throw-away replays ahead of its one timed batch (clocks up after the host-side set-up)
 STAMPS = 1 << 30              # gbp_ba_set_kernel_timing(STAMPS): device-clock stamps in every launch, HIP events around the first one only
 EVENT_EVERY = 7               # HIP events bracket every 7th launch of the dominant kernel in the instrumented replay (cross-check)
 CLK_RING = 4096               # sweeps the library keeps stamps for (gbp_capi.hip)
@@ -65,6 +74,31 @@ def layout_bytes(F, L, C, n_blocks, fused, table_rows=None):
     # k_factor_tile: the same per-factor / per-landmark streams + what rebuilds the camera message, staged camera-major
     # (x0 9 | q_C 2 | W 3 in one whole 128-byte line, + cpos)
     return F * (per_factor + 16 * 8 + 4) + L * per_lmk
+
+
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs writes at most this much
+
+
+def timed_outputs(graph, limit=DUMP_LIMIT_BYTES):
+    """(collective for N > 1: the ARE is summed over ranks) What a caller of the timed path holds after its last sweep, as float64
+    arrays: the beliefs (information form) and means of every camera and landmark -- for N > 1 the landmarks of this rank's shard,
+    `lmk_range` -- and the average reprojection error.  When they would exceed `limit` bytes, the landmark rows are a fixed sample
+    (seed 0, ascending, listed in `lmk_sample_rows`); the cameras are always complete."""
+    are = graph.are()
+    eng = getattr(graph, 'engine', graph)
+    ce, cl, le, ll = eng.beliefs()
+    cm, lm = eng.means()
+    out = dict(cam_eta=ce, cam_lam=cl, cam_mean=cm, lmk_eta=le, lmk_lam=ll, lmk_mean=lm, are=np.array([are]))
+    if hasattr(graph, 'lmk_range'):
+        out['lmk_range'] = np.array(graph.lmk_range, dtype=np.float64)
+    lmk = ('lmk_eta', 'lmk_lam', 'lmk_mean')
+    if sum(a.nbytes for a in out.values()) > limit:
+        fixed = sum(a.nbytes for k, a in out.items() if k not in lmk)
+        per_row = sum(out[k][:1].nbytes for k in lmk) + 8                  # (+ its entry in lmk_sample_rows)
+        n = int(max(1, min(le.shape[0], (limit - fixed) // per_row)))
+        rows = np.sort(np.random.default_rng(0).choice(le.shape[0], size=n, replace=False))
+        out.update({k: out[k][rows] for k in lmk}, lmk_sample_rows=rows.astype(np.float64))
+    return {k: np.ascontiguousarray(a, dtype=np.float64) for k, a in out.items()}
 
 
 def library_fingerprint():
@@ -372,20 +406,28 @@ def main(shard_factory=None, script=None):
                                                 'tests/golden/data/fr1desk.txt); not the headline workload')
     ap.add_argument('--closures', type=float, default=0.0, help='with --window: this fraction of the landmarks is seen from anywhere along the trajectory')
     ap.add_argument('--no-fused', action='store_true')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-hbm-size', action='store_true', help='skip the 2M-factor replay behind roofline.frac_hbm_bound')
-    ap.add_argument('--single-batch', action='store_true', help='one timed batch only (profiling runs)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beside the headline figure: batches repeated until >= 0.5 s are timed, the instrumented replays behind '
+                         '`roofline` and `per_rank`, the parity check against fixture G9b, the CPU baselines, the 2M-factor HBM-bound replay, '
+                         'and for N > 1 the prediction and the secondary workload.  Without it: set up, W warm-up sweeps, K timed sweeps, one line')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed sweeps, write what the last timed sweep left (beliefs, means, ARE) as DIR/<name>.npy (float64)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='(--full) skip the CPU baselines')
+    ap.add_argument('--no-hbm-size', action='store_true', help='(--full) skip the 2M-factor replay behind roofline.frac_hbm_bound')
+    ap.add_argument('--single-batch', action='store_true', help='(--full) one timed batch only (profiling runs)')
     ap.add_argument('--sharded', action='store_true', help='take the N > 1 code path (process group, ShardedBA, RCCL exchange forced) even with one rank')
     ap.add_argument('--exchange', default='auto', choices=['auto', 'rccl', 'peer'],
                     help='N > 1: how the camera partial sums travel.  rccl = one ncclAllGather per sweep on the library\'s communicator; peer = '
                          'direct stores into the ranks\' mailboxes, no collective; auto = measure rccl, then peer, report the faster as `value` '
                          'and the other beside it')
     ap.add_argument('--python-loop', action='store_true', help='N > 1: drive the sweeps from Python (shard_begin / all_gather / shard_end)')
-    ap.add_argument('--dump-sweeps', default=None, help='write the per-sweep kernel times (ms) and relinearisation counts of the instrumented replay to this .npz')
+    ap.add_argument('--dump-sweeps', default=None, help='(--full) write the per-sweep kernel times (ms) and relinearisation counts of the instrumented replay to this .npz')
     ap.add_argument('--backend', default='nccl', help='torch.distributed backend of the side channel (tests: gloo)')
-    ap.add_argument('--secondary-lmks', type=int, default=800_000, help='N > 1: landmarks of the SECONDARY, bandwidth-bound workload timed after the headline '
+    ap.add_argument('--secondary-lmks', type=int, default=800_000, help='(--full) N > 1: landmarks of the SECONDARY, bandwidth-bound workload timed after the headline '
                     'one (default 800 000 = 8M factors: 1M per rank at N = 8; every rank makes its own share against the shared cameras); 0 = skip')
     args = ap.parse_args()
+    if args.dump_sweeps and not args.full:
+        ap.error('--dump-sweeps writes what the instrumented replay of --full recorded: give --full as well')
 
     dry = shard_factory is not None
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -459,8 +501,9 @@ def main(shard_factory=None, script=None):
         if not dry:
             torch.cuda.synchronize()
 
-    def measure(graph, min_timed_s=MIN_TIMED_S):
-        """The timing protocol on one graph object: returns batch times + the kernel-level picture of one instrumented replay."""
+    def measure(graph, min_timed_s=MIN_TIMED_S, dump=True):
+        """The timing protocol on one graph object: returns batch times (+ with --full the kernel-level picture of one instrumented
+        replay; + with --dump-outputs what the last timed batch left in the graph, taken before anything else runs on it)."""
         graph.generate_priors_var(50.0)
         graph.update_all_beliefs()
         graph.sync()
@@ -503,12 +546,33 @@ def main(shard_factory=None, script=None):
                 dt = float(t.item())
             return dt
 
-        batch()                                               # untimed: page in code, caches, clocks
-        times = [batch()]
-        while not args.single_batch and sum(times) < min_timed_s and len(times) < MAX_BATCHES:
-            times.append(batch())
+        if args.full:
+            batch()                                           # untimed: page in code, caches, clocks
+            times = [batch()]
+            while not args.single_batch and sum(times) < min_timed_s and len(times) < MAX_BATCHES:
+                times.append(batch())
+        else:
+            # The host-side set-up leaves the GPU idle long enough to drop its clocks, and W warm-up sweeps (1.4 ms at W = 20) do not bring
+            # them back: a cold K = 200 batch measured 13 % above the median of --full.  ~SPIN_UP_S of throw-away replays (restore + at most
+            # 200 sweeps each) go first, as the untimed batch of --full does; batch() restores the state, so the timed sweeps are the same.
+            if not dry:
+                t_end = time.perf_counter() + SPIN_UP_S
+                while True:
+                    graph.restore_snapshot()
+                    graph.iterate(min(args.warmup + args.steps, 200))
+                    graph.sync()
+                    done = time.perf_counter() >= t_end
+                    if dist is not None:                       # (every rank runs the same number of replays: they contain exchanges)
+                        t = torch.tensor([0.0 if done else 1.0], dtype=torch.float64, device=side_dev)
+                        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                        done = float(t.item()) < 0.5
+                    if done:
+                        break
+            times = [batch()]                                 # W warm-up sweeps, then exactly K timed
         m = dict(times=np.array(times), ev_ms=np.zeros(0), clk=np.zeros((0, 6)), relin=np.zeros(0, np.int64), k_name='')
-        if not dry:
+        if dump and args.dump_outputs:
+            m['outputs'] = timed_outputs(graph)
+        if args.full and not dry:
             # One more, untimed replay of the same batch, instrumented: every kernel of every sweep stamps the device's
             # constant-rate clock (first workgroup in, last workgroup out), and HIP events bracket every EVENT_EVERY-th launch of
             # the dominant kernel as a cross-check (an event pair around a launch also times the dispatch behind the event's
@@ -538,7 +602,7 @@ def main(shard_factory=None, script=None):
             graph.set_kernel_timing(0)
             if args.steps <= 512:
                 m['relin'] = np.asarray(graph.relin_counts(args.steps), dtype=np.int64)
-        m['are'] = graph.are()
+        m['are'] = graph.are() if args.full else None
         return m
 
     def kernel_picture(m, F_total):
@@ -695,8 +759,8 @@ def main(shard_factory=None, script=None):
         else:
             k_src = "none"
         achieved = lay / (k_steady * 1e-3) / 1e9 if k_steady else 0.0
-        traffic, traffic_src = measured_traffic() if (world == 1 and fused and F == 1_000_000 and not dry) else (None, None)
-        lib_hash = None if dry else library_fingerprint()
+        traffic, traffic_src = measured_traffic() if (args.full and world == 1 and fused and F == 1_000_000 and not dry) else (None, None)
+        lib_hash = None if (dry or not args.full) else library_fingerprint()
         roof = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                 "frac_of_copy_ceiling": achieved / COPY_CEILING_GBS, "copy_ceiling": COPY_CEILING_GBS,
                 "traffic": traffic, "kernel": m['k_name'], "bytes_per_launch": lay,
@@ -756,13 +820,15 @@ def main(shard_factory=None, script=None):
                        "topology": topology,
                        "camera_windows": {"widest": plan['max_window'], "table_rows": plan['table_rows']} if plan.get('max_window') else None,
                        "loop": ("python" if (args.python_loop or dry or not getattr(graph, 'library_loop', True)) else "in-library") if (world > 1 or args.sharded) else "gbp_ba_iterate"},
-            "timing": {"protocol": "state restored before every batch; W warm-up + K timed sweeps between barrier+synchronize; median over batches",
+            "timing": {"protocol": ("state restored before every batch; W warm-up + K timed sweeps between barrier+synchronize; median over batches"
+                                    if args.full else "one batch: W warm-up + K timed sweeps between barrier+synchronize"),
                        "batches": int(times.size), "timed_seconds": float(times.sum()),
                        "ms_per_step_median": ms_step, "ms_per_step_min": dt_min / args.steps * 1e3,
                        "ms_per_step_first": float(times[0]) / args.steps * 1e3},
-            "roofline": roof,
-            "are_after": are,
         }
+        if args.full:
+            out["roofline"] = roof
+            out["are_after"] = are
         if per_rank is not None:
             out["per_rank"] = per_rank
         if alt is not None:
@@ -771,7 +837,7 @@ def main(shard_factory=None, script=None):
                                      "batches": int(at.size), "camera_beliefs_match": alt.get('matches_rccl', alt.get('matches'))}
         if dry:
             out["dry_run"] = True
-        if world == 1 and not args.no_cpu_baseline and not dry:
+        if args.full and world == 1 and not args.no_cpu_baseline and not dry:
             out["cpu_baseline"] = cpu_baseline(problem, engine=graph)
             if args.bal and F <= 50_000:
                 out["cpu_baseline_numpy"] = cpu_baseline_numpy(problem)
@@ -788,7 +854,8 @@ def main(shard_factory=None, script=None):
     m = measure(graph)
     exchange_used = getattr(graph, 'exchange', None)
     # outside the timed region: the first ten sweeps once more, against the reference's own run of this graph (fixture G9b)
-    pc = None if dry else parity_check(graph, problem, dist, torch, side_dev, world, local_rank, default_graph=args.window is None and not args.bal)
+    pc = None if (dry or not args.full) else parity_check(graph, problem, dist, torch, side_dev, world, local_rank,
+                                                          default_graph=args.window is None and not args.bal)
     per_rank = gather_per_rank(m)
     alt = None
     peer_unavailable = None
@@ -821,11 +888,15 @@ def main(shard_factory=None, script=None):
                                                            "the RCCL result stands")
     if args.dump_sweeps and rank == 0:
         np.savez(args.dump_sweeps, clk_us=m['clk'], event_ms=m['ev_ms'], relin=m['relin'], batch_s=m['times'])
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in m['outputs'].items():
+            np.save(os.path.join(args.dump_outputs, name + '.npy'), a)
 
     # ---- N > 1: a stated model to judge the measurement against, and a workload that is NOT latency-bound ---------------------------
     # Both run after the headline measurement is complete, under a watchdog that prints that measurement should they hang.
     extras = {}
-    if world > 1 and not dry:
+    if args.full and world > 1 and not dry:
         import threading
         base = assemble(m, alt, exchange_used, per_rank, pc) if rank == 0 else None
         if base is not None and peer_unavailable:
@@ -899,7 +970,7 @@ def main(shard_factory=None, script=None):
             if all_max(0.0 if sec_err is None else 1.0) < 0.5:
                 g2 = ShardedBA(mine, device=local_rank, fused=False if args.no_fused else None, local_shard=True, exchange=exchange_used)
                 try:
-                    m2 = measure(g2, min_timed_s=MIN_TIMED_S / 2)
+                    m2 = measure(g2, min_timed_s=MIN_TIMED_S / 2, dump=False)
                     pr2 = gather_per_rank(m2, g2)
                     t2 = float(np.median(m2['times']))
                     sec = {"label": "SECONDARY (bandwidth-bound companion; not the BASELINE metric)",
@@ -914,7 +985,7 @@ def main(shard_factory=None, script=None):
         wd.cancel()
 
     hbm = None
-    if world == 1 and not dry and not args.bal and not args.no_fused and not args.single_batch and not args.no_hbm_size and F == 1_000_000:
+    if args.full and world == 1 and not dry and not args.bal and not args.no_fused and not args.single_batch and not args.no_hbm_size and F == 1_000_000:
         try:
             hbm = hbm_bound_size()
         except Exception as e:                                   # noqa: BLE001

@@ -18,7 +18,7 @@ def test_bench_spawns_its_own_ranks(oracle_mod, world):
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     cmd = [sys.executable, os.path.join(REPO, 'tests', 'tools', 'bench_dry_launch.py'), '--gpus', str(world), '--steps', '3', '--warmup', '1',
            '--bal', os.path.join(REPO, 'tests', 'golden', 'data', 'fr1desk_vsmall.txt'),
-           '--backend', 'gloo', '--single-batch']
+           '--backend', 'gloo', '--single-batch', '--full']
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=540)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -27,6 +27,69 @@ def test_bench_spawns_its_own_ranks(oracle_mod, world):
     assert out['n_gpus'] == world and out['steps'] == 3 and out['dry_run'] is True
     assert out['value'] > 0 and out['scaling'] == 'strong' and out['config']['n_factors'] == 1801
     assert 0.0 <= out['roofline']['frac'] <= 1.0
+
+
+@pytest.mark.timeout(600)
+def test_plain_run_times_exactly_k_steps_and_dumps_its_outputs(oracle_mod, tmp_path):
+    """Without --full the line is the headline alone: ONE batch of exactly K timed sweeps (ms_per_step = its time / K), none of the
+    --full fields; --dump-outputs writes what the last timed sweep left as float64 .npy files, the same in two runs of one command line."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f'run{run}'
+        cmd = [sys.executable, os.path.join(REPO, 'tests', 'tools', 'bench_dry_launch.py'), '--gpus', '2', '--steps', '3', '--warmup', '1',
+               '--bal', os.path.join(REPO, 'tests', 'golden', 'data', 'fr1desk_vsmall.txt'), '--backend', 'gloo', '--dump-outputs', str(d)]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=270)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+        assert len(lines) == 1, r.stdout
+        out = json.loads(lines[0])
+        assert out['steps'] == 3 and out['warmup'] == 1 and out['timing']['batches'] == 1 and out['dry_run'] is True
+        assert out['ms_per_step'] == pytest.approx(1e3 / out['value'], rel=1e-12)
+        assert out['ms_per_step'] == pytest.approx(out['timing']['timed_seconds'] / 3 * 1e3, rel=1e-12)
+        for k in ('metric', 'unit', 'higher_is_better', 'dtype'):
+            assert k in out
+        for k in ('roofline', 'are_after', 'parity_check', 'cpu_baseline', 'prediction', 'secondary', 'per_rank'):
+            assert k not in out, k
+        dumps.append({f.name[:-4]: np.load(f) for f in sorted(d.iterdir())})
+    a, b = dumps
+    assert {'cam_eta', 'cam_lam', 'cam_mean', 'lmk_eta', 'lmk_lam', 'lmk_mean', 'are'} <= set(a) and set(a) == set(b)
+    assert a['cam_eta'].shape == (10, 6) and a['cam_lam'].shape == (10, 6, 6) and a['lmk_lam'].shape[1:] == (3, 3)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k in a:
+        assert a[k].dtype == np.float64 and np.array_equal(a[k], b[k]), k
+
+
+def test_dumped_outputs_stay_within_the_limit():
+    """timed_outputs(): past the size limit the landmark rows are a fixed, seeded sample (listed), the cameras stay complete."""
+    import numpy as np
+    sys.path.insert(0, REPO)
+    import bench
+
+    class Graph:
+        C, L = 4, 5000
+
+        def are(self):
+            return 1.5
+
+        def beliefs(self):
+            r = np.arange(self.L, dtype=np.float64)
+            return np.ones((self.C, 6)), np.ones((self.C, 6, 6)), np.repeat(r[:, None], 3, 1), np.repeat(r[:, None, None], 9, 1).reshape(-1, 3, 3)
+
+        def means(self):
+            return np.zeros((self.C, 6)), np.repeat(np.arange(self.L, dtype=np.float64)[:, None], 3, 1)
+
+    whole = bench.timed_outputs(Graph())
+    assert whole['lmk_eta'].shape == (5000, 3) and 'lmk_sample_rows' not in whole and float(whole['are'][0]) == 1.5
+    limit = 100_000
+    cut = bench.timed_outputs(Graph(), limit=limit)
+    assert sum(v.nbytes for v in cut.values()) <= limit
+    rows = cut['lmk_sample_rows']
+    assert 0 < rows.size < 5000 and np.all(np.diff(rows) > 0) and cut['cam_lam'].shape == (4, 6, 6)
+    assert np.array_equal(cut['lmk_eta'][:, 0], rows) and np.array_equal(cut['lmk_mean'][:, 0], rows)
+    assert np.array_equal(bench.timed_outputs(Graph(), limit=limit)['lmk_sample_rows'], rows)
+    assert all(v.dtype == np.float64 for v in cut.values())
 
 
 def test_world_size_mismatch_is_refused():

@@ -122,7 +122,7 @@ def test_bench_n_ranks_on_one_gpu(tmp_path, world):
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(GBP_BENCH_SHARE_GPU='1', GBP_XCHG_BLOCKS='16', HSA_ENABLE_IPC_MODE_LEGACY='0', GBP_PEER_TIMEOUT_MS='20000')
     cmd = [sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', str(world), '--steps', '20', '--warmup', '5',
-           '--backend', 'gloo', '--exchange', 'peer', '--single-batch', '--secondary-lmks', str(8000 * world)]      # the headline graph: parity_check has its fixture
+           '--backend', 'gloo', '--exchange', 'peer', '--single-batch', '--full', '--secondary-lmks', str(8000 * world)]      # the headline graph: parity_check has its fixture
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -166,7 +166,7 @@ def test_bench_line_survives_an_rccl_that_does_not_come_up(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(GBP_BENCH_SHARE_GPU='1', HSA_ENABLE_IPC_MODE_LEGACY='0', GBP_RCCL_FAIL='1')
     cmd = [sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '2', '--steps', '10', '--warmup', '2', '--backend', 'gloo', '--exchange', 'rccl',
-           '--single-batch', '--secondary-lmks', '0']
+           '--single-batch', '--full', '--secondary-lmks', '0']
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]

@@ -8,7 +8,7 @@ shapes = [("500_nofused", ['--cams', '500', '--no-fused']), ("1000", ['--cams', 
           ("13682_x_3.08M", ['--cams', '13682', '--lmks', '616000', '--obs', '5'])]
 out = {}
 for name, extra in shapes:
-    r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--steps', '20', '--warmup', '5', '--no-cpu-baseline', '--no-hbm-size'] + extra,
+    r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--full', '--steps', '20', '--warmup', '5', '--no-cpu-baseline', '--no-hbm-size'] + extra,
                        capture_output=True, text=True)
     line = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
     if not line:

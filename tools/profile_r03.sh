@@ -19,6 +19,6 @@ for d in 3 6; do
   timeout 300 python tools/bench_linear.py --dofs $d 2>/dev/null >> $S/${TAG}_linear_bench.jsonl
 done
 for n in 50000 70000 85000 100000 105000 110000 120000 150000 200000; do
-  python bench.py --no-cpu-baseline --lmks $n 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print(json.dumps({'n_factors': d['config']['n_factors'], 'us_per_step': d['ms_per_step']*1e3, 'kernel_us': r['kernel_avg_ms']*1e3, 'ns_per_factor': r['kernel_avg_ms']*1e9/d['config']['n_factors'], 'layout_MB': r['bytes_per_launch']/1e6, 'frac': r['frac']}))" >> $S/${TAG}_size_sweep.jsonl
+  python bench.py --full --no-cpu-baseline --lmks $n 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print(json.dumps({'n_factors': d['config']['n_factors'], 'us_per_step': d['ms_per_step']*1e3, 'kernel_us': r['kernel_avg_ms']*1e3, 'ns_per_factor': r['kernel_avg_ms']*1e9/d['config']['n_factors'], 'layout_MB': r['bytes_per_launch']/1e6, 'frac': r['frac']}))" >> $S/${TAG}_size_sweep.jsonl
 done
 ls -la $S

@@ -14,7 +14,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp && cd "$ROOT"
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
-B="python bench.py --no-cpu-baseline --single-batch"
+B="python bench.py --full --no-cpu-baseline --single-batch"
 timeout 300 rocprofv3 --kernel-trace --stats -f csv -d $OUT/stats_1m -o run -- $B --steps 200 --warmup 20 > $OUT/bench_stats_1m.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout 300 rocprofv3 --pmc $c -f csv -d $OUT/${c}_1m -o run -- $B --steps 10 --warmup 2 > $OUT/bench_${c}_1m.log 2>&1
@@ -42,5 +42,5 @@ python tools/summarize_round.py $OUT $TAG
 cp $OUT/summary/${TAG}_hbm_traffic.json profiles/${TAG}_hbm_traffic.json
 rm -rf $OUT/stats_1m
 timeout 300 rocprofv3 --kernel-trace --stats -f csv -d $OUT/stats_1m -o run -- $B --steps 200 --warmup 20 > $OUT/bench_stats_1m.log 2>&1
-timeout 600 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout 600 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 python tools/summarize_round.py $OUT $TAG

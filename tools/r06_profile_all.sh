@@ -9,7 +9,8 @@ timeout 900 python tools/shard_probe.py --sizes 50000 25000 12500 6250 --reps 24
 bash tools/shard_kstats.sh 12500 engine peer1 > gpurun_out/r06_final/shard_kstats_125k.txt 2>&1
 bash tools/shard_kstats.sh 25000 engine peer1 > gpurun_out/r06_final/shard_kstats_250k.txt 2>&1
 # BASELINE configs 2-3
-for f in fr1desk.txt fr1desk_small.txt; do timeout 300 python bench.py --bal tests/golden/data/$f --steps 200 --warmup 20 > gpurun_out/r06_final/bench_$f.json 2> gpurun_out/r06_final/bench_$f.err; done
+B=${GBP_OUT:-out}/r06_final; mkdir -p $B
+for f in fr1desk.txt fr1desk_small.txt; do timeout 300 python bench.py --full --bal tests/golden/data/$f --steps 200 --warmup 20 > $B/bench_$f.json 2> $B/bench_$f.err; done
 # what an N > 1 line carries (all ranks on this box's one GPU: field carriers, not measurements)
 mkdir -p gpurun_out/r06_final/lines
 GBP_KEEP_BENCH_LINES=$ROOT/gpurun_out/r06_final/lines timeout 1200 python -m pytest tests/test_peer_ipc_gpu.py -x -q -k "bench_n_ranks or rccl_that" 2>&1 | grep -E "passed|failed" > gpurun_out/r06_final/pytest_lines.txt

@@ -10,7 +10,7 @@ obs_list = [int(a) for a in sys.argv[1:]] or [3, 5, 10, 20, 40, 100]
 out = {}
 for obs in obs_list:
     lmks = 1_000_000 // obs
-    r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--lmks', str(lmks), '--obs', str(obs), '--steps', '20', '--warmup', '5',
+    r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--full', '--lmks', str(lmks), '--obs', str(obs), '--steps', '20', '--warmup', '5',
                         '--no-cpu-baseline', '--no-hbm-size'], capture_output=True, text=True)
     line = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
     if not line:

@@ -17,7 +17,7 @@ for sh in shapes:
     for variant, extra, env in (("windows", [], {}), ("general", ['--no-fused'], {}), ("whole_tables", [], {"GBP_WINDOWS": "0"})):
         if variant == "whole_tables" and cams > 587:
             continue
-        r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--steps', '20', '--warmup', '5', '--no-cpu-baseline', '--no-hbm-size',
+        r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--full', '--steps', '20', '--warmup', '5', '--no-cpu-baseline', '--no-hbm-size',
                             '--cams', str(cams), '--lmks', str(lmks), '--obs', str(obs), '--window', str(window), '--closures', str(closures)] + extra,
                            capture_output=True, text=True, env=dict(os.environ, **env))
         line = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
