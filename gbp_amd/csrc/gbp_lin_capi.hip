@@ -207,27 +207,70 @@ __global__ __launch_bounds__(64) void k_lin_belief(LinParams p)
     }
 }
 
-// sum over factors of 0.5 mu^T Lambda_f mu - eta_f^T mu + const = 0.5 |h(mu) - z|^2 / sigma^2 for linear h (gbp.py:36-44, 261-265)
+// sum over factors of 0.5 |h(mu) - z|^2 / sigma^2 for linear h (gbp.py:36-44, 251-265), from (Lambda_f, eta_f, const) without
+// the cancellation of the expanded 0.5 x^T Lambda_f x - eta_f^T x + const (terms of |x|^2 / sigma^2 that cancel to the residual:
+// map coordinates with centimetre noise lose every digit).  A pivoted LDL^T of Lambda_f, stopped at a relative pivot tolerance
+// (a factor has rank m <= 2d), writes Lambda_f = sum_k d_k l_k l_k^T and eta_f = sum_k d_k y_k l_k, so the energy is
+//   0.5 sum_k d_k (l_k^T x - y_k)^2 + (const - 0.5 sum_k d_k y_k^2)
+// whose squares are of residuals.  For linear_displacement (Lambda_f = [I -I; -I I] / sigma^2) l_k^T x = x_a - x_b exactly.
 template <int D>
 __global__ __launch_bounds__(256) void k_lin_energy(LinParams p, double *out)
 {
-    constexpr int P = LinDims<D>::P, REC = LinDims<D>::REC;
+    constexpr int P = LinDims<D>::P, REC = LinDims<D>::REC, N2 = 2 * D;
     __shared__ double red[256 / 64];
     const int f = blockIdx.x * 256 + threadIdx.x;
     double e = 0.0;
     if (f < p.F) {
         const size_t F = (size_t)p.F;
-        double x[2 * D];
+        double x[N2], eta[N2], a[Sym<N2>::size];
         const double *ra = p.bel + (size_t)p.va[f] * REC + D + P, *rb = p.bel + (size_t)p.vb[f] * REC + D + P;
 #pragma unroll
         for (int k = 0; k < D; ++k) { x[k] = ra[k]; x[D + k] = rb[k]; }
-        e = p.fconst ? p.fconst[f] : 0.0;
 #pragma unroll
-        for (int i = 0; i < 2 * D; ++i) {
-            e -= p.feta[i * F + f] * x[i];
+        for (int i = 0; i < N2; ++i) eta[i] = p.feta[i * F + f];
 #pragma unroll
-            for (int j = i; j < 2 * D; ++j) e += (i == j ? 0.5 : 1.0) * p.flam[(size_t)Sym<2 * D>::at(i, j) * F + f] * x[i] * x[j];
+        for (int i = 0; i < Sym<N2>::size; ++i) a[i] = p.flam[(size_t)i * F + f];
+        double amax = 0.0;
+#pragma unroll
+        for (int i = 0; i < N2; ++i) amax = fmax(amax, a[Sym<N2>::at(i, i)]);
+        const double tol = N2 * 64 * __DBL_EPSILON__ * amax;
+        double cst = p.fconst ? p.fconst[f] : 0.0, sq = 0.0;
+        int done = 0;                                         // bit i: index i already eliminated
+#pragma unroll 1
+        for (int step = 0; step < N2; ++step) {
+            int piv = -1;
+            double dk = tol;
+#pragma unroll
+            for (int i = 0; i < N2; ++i)
+                if (!((done >> i) & 1) && a[Sym<N2>::at(i, i)] > dk) { dk = a[Sym<N2>::at(i, i)]; piv = i; }
+            if (piv < 0) break;                               // the rest of Lambda_f is rounding: rank reached
+            // column piv over the live indices (register arrays: selected, never indexed by piv)
+            double col[N2], raw[N2], zk = 0.0, lx = 0.0;
+#pragma unroll
+            for (int i = 0; i < N2; ++i) {
+                double c = 0.0;
+#pragma unroll
+                for (int j = 0; j < N2; ++j)
+                    if (j == piv) c = a[Sym<N2>::at(i < j ? i : j, i < j ? j : i)];
+                const bool live = !((done >> i) & 1) && i != piv;
+                raw[i] = live ? c : 0.0;
+                col[i] = live ? c / dk : 0.0;                 // l_k (exactly -1 / 0 for a displacement factor)
+                if (i == piv) { zk = eta[i]; lx = x[i]; }
+            }
+#pragma unroll
+            for (int i = 0; i < N2; ++i) lx += col[i] * x[i];
+            const double yk = zk / dk, t = lx - yk;
+            sq += 0.5 * dk * t * t;
+            cst -= 0.5 * zk * yk;
+#pragma unroll
+            for (int i = 0; i < N2; ++i) {
+                eta[i] -= col[i] * zk;
+#pragma unroll
+                for (int j = i; j < N2; ++j) a[Sym<N2>::at(i, j)] -= col[i] * raw[j];
+            }
+            done |= 1 << piv;
         }
+        e = cst + sq;
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) e += __shfl_down(e, off, 64);

@@ -43,7 +43,10 @@ void gbp_lin_destroy(gbp_lin_t *h);
 int  gbp_lin_sync(gbp_lin_t *h);
 int  gbp_lin_update_beliefs(gbp_lin_t *h);                                      /* FactorGraph.update_all_beliefs gbp.py:56-58 */
 int  gbp_lin_iterate(gbp_lin_t *h, int32_t n_iters);                            /* n x synchronous_iteration gbp.py:86-92      */
-int  gbp_lin_energy(gbp_lin_t *h, double *out);                                 /* FactorGraph.energy gbp.py:36-44             */
+/* FactorGraph.energy gbp.py:36-44: sum_f 0.5 |h(mu) - z|^2 / sigma^2, evaluated per factor in residual form from a pivoted LDL^T of
+ * Lambda_f (0.5 sum_k d_k (l_k^T x - y_k)^2 + const - 0.5 sum_k d_k y_k^2), not as 0.5 x^T Lambda_f x - eta_f^T x + const, which
+ * cancels far from the origin; exact differences x_a - x_b for linear_displacement factors */
+int  gbp_lin_energy(gbp_lin_t *h, double *out);
 int  gbp_lin_get_beliefs(gbp_lin_t *h, double *eta, double *lam);               /* N x d, N x d x d   VariableNode.belief      */
 int  gbp_lin_get_means(gbp_lin_t *h, double *mu);                               /* N x d   FactorGraph.get_means gbp.py:146-153 */
 int  gbp_lin_get_messages(gbp_lin_t *h, double *eta_a, double *lam_a, double *eta_b, double *lam_b);   /* Factor.messages gbp.py:222 */
