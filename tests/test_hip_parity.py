@@ -583,8 +583,13 @@ def test_full_size_against_oracle_and_reference(eng_mod, oracle_mod):
     ARE and relinearisation count after every sweep, iters_since_relin / eta_damping of 4000 sampled factors after 9 and 10."""
     p, o, e = _full_size_pair(eng_mod, oracle_mod)
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'G9b_synthetic_full_1000000.npz')
-    g9b = np.load(path) if os.path.exists(path) else None
-    n_ref = len(g9b['relin_trace']) if g9b is not None and 'relin_trace' in g9b else 0
+    assert os.path.exists(path), f'fixture G9b is missing: {path}'      # without it every reference assertion below would be skipped
+    g9b = np.load(path)
+    n_ref = len(g9b['relin_trace'])
+    ref_tags = {k[:-len('_cam_eta')] for k in g9b.files if k.endswith('_cam_eta')}                    # every checkpoint the fixture holds
+    ref_state_tags = {k[:-len('_iters_since_relin')] for k in g9b.files if k.endswith('_iters_since_relin')}
+    assert n_ref > 0 and ref_tags and ref_state_tags
+    compared = set()
 
     obs = dict(belief_gap_oracle={}, belief_gap_reference={}, are_gap_oracle={}, are_gap_reference={}, relin=[])
 
@@ -593,7 +598,8 @@ def test_full_size_against_oracle_and_reference(eng_mod, oracle_mod):
         gap = max(rel_err_rows(a, b) for a, b in zip(eb, o.beliefs()))
         obs['belief_gap_oracle'][tag] = gap
         assert gap < BELIEF_TOL, (tag, gap)
-        if g9b is not None and tag + '_cam_eta' in g9b:
+        if tag in ref_tags:
+            compared.add(tag)
             s = g9b['lmk_sample']
             got = (eb[0], eb[1], eb[2][s], eb[3][s])
             want = (g9b[tag + '_cam_eta'], g9b[tag + '_cam_lam'], g9b[tag + '_lmk_eta'], g9b[tag + '_lmk_lam'])
@@ -601,7 +607,8 @@ def test_full_size_against_oracle_and_reference(eng_mod, oracle_mod):
             obs['belief_gap_reference'][tag] = gap
             assert gap < BELIEF_TOL, (tag, gap)
             assert e.are() == pytest.approx(float(g9b[tag + '_are']), rel=ARE_TOL)
-        if g9b is not None and tag + '_iters_since_relin' in g9b:
+        if tag in ref_state_tags:
+            compared.add(tag + '_state')
             fs = g9b['factor_sample']
             st = e.relin_state()
             assert np.array_equal(st['iters_since_relin'][fs], g9b[tag + '_iters_since_relin']), tag
@@ -628,6 +635,9 @@ def test_full_size_against_oracle_and_reference(eng_mod, oracle_mod):
         if it in transitions:
             check(f'it{it}', it)
             _state_machine_equal(o, e, it)
+    # every reference checkpoint of the fixture was compared (a key the schedule does not reach would otherwise be skipped silently)
+    assert compared == ref_tags | {t + '_state' for t in ref_state_tags}, (sorted(compared), sorted(ref_tags), sorted(ref_state_tags))
+    assert n_ref <= FULL_SWEEPS
     # the schedule really went through what it is meant to cover
     assert all(n == 0 for n in relin_seen[:7]) and relin_seen[7] > p.n_factors // 2 and relin_seen[16] > p.n_factors // 2, relin_seen
     d = e.relin_state()['eta_damping']

@@ -282,7 +282,9 @@ def test_full_size_sharded_config5(full_size_single, world, exchange):
     assert max(r['F'] for r in ranks) - min(r['F'] for r in ranks) <= 10          # balanced by factor count
     rce, rcl, rle, rll = ref['bel']
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'G9b_synthetic_full_1000000.npz')
-    g9b = np.load(path) if os.path.exists(path) else None
+    assert os.path.exists(path), f'fixture G9b is missing: {path}'      # without it every reference assertion below would be skipped
+    g9b = np.load(path)
+    assert f'it{FULL_SHARD_SWEEPS}_cam_eta' in g9b
     lo = 0
     for r in ranks:
         assert r['exchange'] == exchange
@@ -295,13 +297,13 @@ def test_full_size_sharded_config5(full_size_single, world, exchange):
         assert r['are'] == pytest.approx(ref['are'], rel=1e-8) and r['energy'] == pytest.approx(ref['energy'], rel=1e-7)
         assert r['n_relin'] == ref['n_relin']
         assert np.array_equal(r['relin'], ref['relin'])
-        if g9b is not None and f'it{FULL_SHARD_SWEEPS}_cam_eta' in g9b:
-            tag = f'it{FULL_SHARD_SWEEPS}'
-            assert rel_err_rows(r['ce'], g9b[tag + '_cam_eta']) < 1e-6 and rel_err_rows(r['cl'], g9b[tag + '_cam_lam']) < 1e-6
-            s = g9b['lmk_sample']
-            mine = (s >= a) & (s < b)
-            assert rel_err_rows(r['le'][s[mine] - a], g9b[tag + '_lmk_eta'][mine]) < 1e-6
-            assert rel_err_rows(r['ll'][s[mine] - a], g9b[tag + '_lmk_lam'][mine]) < 1e-6
+        tag = f'it{FULL_SHARD_SWEEPS}'
+        assert rel_err_rows(r['ce'], g9b[tag + '_cam_eta']) < 1e-6 and rel_err_rows(r['cl'], g9b[tag + '_cam_lam']) < 1e-6
+        s = g9b['lmk_sample']
+        mine = (s >= a) & (s < b)
+        assert mine.any()
+        assert rel_err_rows(r['le'][s[mine] - a], g9b[tag + '_lmk_eta'][mine]) < 1e-6
+        assert rel_err_rows(r['ll'][s[mine] - a], g9b[tag + '_lmk_lam'][mine]) < 1e-6
     assert lo == p.n_lmks
     assert ref['relin'][7] > p.n_factors // 2 and not ref['relin'][:7].any()
 
