@@ -89,10 +89,10 @@ static int scratch_alloc(gbp_ba *h, std::vector<void *> &scratch, T **out, size_
 
 }  // extern "C++"
 
-// GBP_BUILD_TIMING=1: wall time of the stages of gbp_ba_create on stderr (each mark synchronises the stream: diagnostic only)
+// GBP_BUILD_TIMING: wall time of the stages of gbp_ba_create on stderr (each mark synchronises the stream: diagnostic only)
 struct BuildClock {
     bool on; hipStream_t s; std::chrono::steady_clock::time_point t0;
-    BuildClock(hipStream_t st) : on(getenv("GBP_BUILD_TIMING") != nullptr), s(st), t0(std::chrono::steady_clock::now()) {}
+    BuildClock(bool on_, hipStream_t st) : on(on_), s(st), t0(std::chrono::steady_clock::now()) {}
     void mark(const char *what)
     {
         if (!on) return;
@@ -105,7 +105,7 @@ struct BuildClock {
 
 static int build_graph(gbp_ba *h, const gbp_ba_desc_t *d, std::vector<void *> &scratch, int n_cus)
 {
-    BuildClock clk(h->stream);
+    BuildClock clk(h->ovr.build_timing, h->stream);
     const int C = d->n_cams, L = d->n_lmks, F = d->n_factors;
     Params &p = h->p;
     const bool dev_in = (d->flags & GBP_FLAG_DEVICE_INPUT) != 0;
@@ -196,15 +196,7 @@ static int build_graph(gbp_ba *h, const gbp_ba_desc_t *d, std::vector<void *> &s
     HIPCHK(hipMemcpyAsync(&min_deg, d_mindeg, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     if (L == 0) T = 0;
-    // Whole landmarks per tile (T tiles from the list ranking above), or -- when that would leave more than 15 % of the slots empty
-    // and every landmark has at least three factors -- the dense packing: tile t = factors [64 t, 64 t + 64), landmarks may span tiles
-    // (gbp_build.hpp).  One million factors at 40 per landmark: 25 000 tiles of 40 -> 15 625 full ones.  GBP_PACK=whole|dense overrides
-    // (tests, A/B runs); "dense" still needs the three factors per landmark.
-    bool dense = false;
-    if (T > 0 && F > 0 && min_deg >= 3) {
-        const char *e = getenv("GBP_PACK");
-        dense = e ? strcmp(e, "dense") == 0 : (double)F < 0.85 * 64.0 * (double)T;
-    }
+    const bool dense = dense_packing(F, T, min_deg, h->ovr);
     if (dense) T = (F + WTILE - 1) / WTILE;
     if (T < 0 || (int64_t)T * WTILE > INT32_MAX) return fail(GBP_EINVAL, "the graph needs %d tiles: slot indices would not fit 32 bits", T);
     const size_t S = std::max<size_t>((size_t)T * WTILE, 1);
@@ -230,18 +222,16 @@ static int build_graph(gbp_ba *h, const gbp_ba_desc_t *d, std::vector<void *> &s
 
     clk.mark("tile packing");
     // 5. per-slot data
-    bool general_sweep = false;
+    bool general = false;                   // the general sweep may run: its staging buffer comes out of the arena
     {
-        int n_wg = std::max(1, std::min(T, n_cus));
-        if (const char *nb = getenv("GBP_FUSED_BLOCKS")) n_wg = std::max(1, std::min(n_wg, atoi(nb)));      // (experiment switch, as in fused_plan)
+        const int n_wg = fused_workgroups(T, n_cus, h->ovr);
         const int cgmax = fused_max_cams();      // (host arithmetic on the LDS budget: gbp_fused_plan.hpp)
         // Camera WINDOWS.  Workgroup b of the fused sweep walks the tiles [b T / n, (b + 1) T / n) and needs table rows for the cameras
         // of THOSE tiles only.  In a sequence -- landmarks numbered along the trajectory, each seen from neighbouring cameras, now and
         // then from a place visited before -- that is a few dozen cameras however many the graph has: the table becomes [set][27] per
         // workgroup (k_wg_cam_sets: the distinct cameras of its tiles; a 16-bit map over the interval they lie in turns a camera into
         // its table row), more cameras than fit the LDS as a whole still run the fused sweep, and the tables written and reduced every
-        // sweep shrink from workgroups x cameras rows to the sum of the sets.  Taken when the whole table would not fit, or when the sets
-        // add up to at most 0.7 of it; GBP_WINDOWS=0 / 1: never / whenever they fit.
+        // sweep shrink from workgroups x cameras rows to the sum of the sets.  When they are taken: camera_windows (gbp_policy.hpp).
         h->wg_win.clear(); h->wg_cams.clear();
         long long rows = (long long)n_wg * C;
         if (T > 0 && C > 0 && !(h->flags & GBP_FLAG_NO_FUSED) && p.num_undamped != 0) {
@@ -269,11 +259,7 @@ static int build_graph(gbp_ba *h, const gbp_ba_desc_t *d, std::vector<void *> &s
                 long long sum = 0;
                 int max_set = 0;
                 for (int n : counts) { sum += n; max_set = std::max(max_set, n); }
-                const char *e = getenv("GBP_WINDOWS");
-                // (a 125k-factor share of the headline graph, 500 random cameras: sets 0.63 of the whole tables, 26.6 against 29.2 us per
-                //  sweep; a 250k share: 0.86, 36.6 against 34.4 -- tools/sparse_probe.sh)
-                const bool want = e ? atoi(e) != 0 : (C > cgmax || 10 * sum <= 7 * rows);
-                if (want && max_set <= cap && fused_shmem_windows(max_set, max_width) <= (size_t)LDS_BYTES) {
+                if (camera_windows(C, cgmax, sum, rows, h->ovr) && max_set <= cap && fused_shmem_windows(max_set, max_width) <= (size_t)LDS_BYTES) {
                     std::vector<int> lists((size_t)n_wg * cap);
                     HIPCHK(hipMemcpyAsync(lists.data(), d_lists, sizeof(int) * lists.size(), hipMemcpyDeviceToHost, h->stream));
                     HIPCHK(hipStreamSynchronize(h->stream));
@@ -288,28 +274,18 @@ static int build_graph(gbp_ba *h, const gbp_ba_desc_t *d, std::vector<void *> &s
             }
         }
         const bool windowed = !h->wg_win.empty();
-        // Few factors per camera: the fused sweep writes (and its reduce reads back) one 224-byte table row per camera and WORKGROUP
-        // whatever the graph's size, the staged form one 128-byte row per FACTOR.  Below ~0.75 factors per (workgroup, camera) the
-        // staged sweep is the faster one -- 13k / 30k / 60k / 90k factors x 500 cameras: 18.6 / 20.5 / 24.2 / 29.1 against 26.3 /
-        // 28.6 / 28.9 / 30.2 us per sweep (profiles/r04_shards.json); round 5: 62.5k 22.1 against 28.6; 125k is a tie (30.6 against 31.4,
-        // with the peer-store exchange in the loop 34.5 against 35.3), 250k 44.6 against 36.9 (profiles/r05_shards.json) -- e.g. a rank's
-        // share of the headline graph at 16 ranks and beyond.  Not a byte count: fr1desk (13 298 factors, 63 cameras, 221 workgroups: 0.96
-        // per pair) runs 13.9 us fused against ~16 staged, so the threshold stays below 1.  GBP_STAGED_BELOW overrides it (0: never).
-        double staged_below = 0.75;
-        if (const char *e = getenv("GBP_STAGED_BELOW")) staged_below = atof(e);
-        const bool sparse = (double)F < staged_below * (double)rows;      // (windows: the rows the tables really have)
-        h->staged_auto = sparse && !(h->flags & (GBP_FLAG_FORCE_FUSED | GBP_FLAG_NO_FUSED));
+        h->staged_auto = staged_for_sparseness(F, rows, h->ovr) && !(h->flags & (GBP_FLAG_FORCE_FUSED | GBP_FLAG_NO_FUSED));
         if (h->staged_auto) h->flags |= GBP_FLAG_NO_FUSED;
         if (h->flags & GBP_FLAG_NO_FUSED) { h->wg_win.clear(); h->wg_cams.clear(); }
-        general_sweep = (h->flags & GBP_FLAG_NO_FUSED) || p.num_undamped == 0 || (C > cgmax && !windowed);   // its staging buffer is streamed every sweep too
-        const size_t need = (general_sweep ? std::max<size_t>(Fz, 1) * p.crow * sizeof(double) + (64 << 8) : 0) + S * (LIN_ROWS + MSG_ROWS + (p.num_undamped == 0 ? XTRA_ROW : 0) + (p.loss != 0 ? 1 : 0)) * sizeof(double) + S * sizeof(int)
+        general = general_sweep((h->flags & GBP_FLAG_NO_FUSED) != 0, p.num_undamped == 0, C, cgmax, windowed);
+        const size_t need = (general ? std::max<size_t>(Fz, 1) * p.crow * sizeof(double) + (64 << 8) : 0) + S * (LIN_ROWS + MSG_ROWS + (p.num_undamped == 0 ? XTRA_ROW : 0) + (p.loss != 0 ? 1 : 0)) * sizeof(double) + S * sizeof(int)
                           + (size_t)std::max(L, 1) * LREC * sizeof(double) + (size_t)std::max<long long>(rows, 1) * (TROW * sizeof(double) + 2 * sizeof(int)) + (size_t)n_wg * sizeof(int4) + (size_t)std::max(C, 1) * sizeof(int2) + 4 * 4096
                           + (size_t)std::max(C, 1) * (CAMREC + CBEL + 27 + 27 + 1) * sizeof(double) + (size_t)std::max(L, 1) * sizeof(double)
                           + 2 * (size_t)grid_for(S) * sizeof(double) + (size_t)RELIN_RING * RELIN_LANES * sizeof(int)
                           + (size_t)(n_wg + 1) * sizeof(int) + (h->pack_mode ? 2 * (size_t)std::max(T, 1) * PART_ROW * sizeof(double) : 0) + (64 << 12);
         CHK(arena_reserve(h, need));
     }
-    if (general_sweep && F > 0) { CHK(dev_alloc(h, &p.cstage, Fz * p.crow)); h->cstage_cap = p.crow; }   // out of the same arena (else: on first use, ensure_staging)
+    if (general && F > 0) { CHK(dev_alloc(h, &p.cstage, Fz * p.crow)); h->cstage_cap = p.crow; }   // out of the same arena (else: on first use, ensure_staging)
     CHK(dev_alloc(h, &p.lin, S * LIN_ROWS)); CHK(dev_alloc(h, &p.msg, S * MSG_ROWS));
     if (p.num_undamped == 0) CHK(dev_alloc(h, &p.xtra, S * XTRA_ROW));      // damped in the relinearising sweep: gbp_math.hpp header
     if (p.loss != 0) CHK(dev_alloc(h, &p.avar, S));         // adaptive variances: robust losses only
@@ -335,7 +311,7 @@ static int build_graph(gbp_ba *h, const gbp_ba_desc_t *d, std::vector<void *> &s
     CHK(dev_alloc(h, &h->d_varmax, (size_t)std::max(C + L, 1), false));
 
     clk.mark("vars + small allocs");
-    if (getenv("GBP_DEBUG_LAYOUT")) {
+    if (h->ovr.debug_layout) {
         int bad = 0;
         CHK(gbp_ba_check_layout(h, &bad));
         if (bad) return fail(GBP_ESTATE, "internal layout error: %d slots do not decode to their reference factor", bad);
@@ -349,9 +325,6 @@ static int build_graph(gbp_ba *h, const gbp_ba_desc_t *d, std::vector<void *> &s
     }
     HIPCHK(hipStreamSynchronize(h->stream));                // the staged inputs are released by the caller
     clk.mark("fused plan");
-    if (getenv("GBP_PRINT_PTRS"))
-        fprintf(stderr, "[gbp ptrs] lin %p msg %p lrec %p cbel %p tables %p\n", (void *)p.lin, (void *)p.msg, (void *)p.lrec, (void *)p.cbel,
-                (void *)h->fused.args.block_partials);
     return GBP_OK;
 }
 
@@ -419,6 +392,7 @@ int gbp_ba_create(gbp_ba_t **out, const gbp_ba_desc_t *d)
     if (!h) return fail(GBP_ENOMEM, "out of host memory");
     int rc;
     try {
+        h->ovr = env_overrides();
         rc = create_impl(h, d);
     } catch (const std::bad_alloc &) {
         rc = fail(GBP_ENOMEM, "out of host memory");

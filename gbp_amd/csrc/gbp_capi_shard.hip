@@ -109,7 +109,7 @@ int gbp_ba_comm_unique_id(void *id128, const char *rccl_path)
 {
     if (!id128) return fail(GBP_EINVAL, "null argument");
     // (test switch: a node whose RCCL cannot come up -- the callers' fallbacks, ShardedBA and bench.py's line, are exercised with it)
-    if (getenv("GBP_RCCL_FAIL")) return fail(GBP_ESTATE, "RCCL switched off by GBP_RCCL_FAIL (test switch)");
+    if (env_overrides().rccl_fail) return fail(GBP_ESTATE, "RCCL switched off by GBP_RCCL_FAIL (test switch)");
     CHK(rccl_load(rccl_path));
     ncclUniqueId id;
     const ncclResult_t rc = g_rccl.GetUniqueId(&id);
@@ -153,21 +153,13 @@ int gbp_ba_peer_export(gbp_ba_t *h, int32_t n_ranks, void *handle64, int32_t fla
     peer_release(h);
     if (pe.mailbox) { HIPCHK(hipFree(pe.mailbox)); pe.mailbox = nullptr; }
     const size_t bytes = peer_bytes(h, n_ranks);
-    // fine-grained (uncached across devices) when the runtime grants it: peers store into it over xGMI while this rank polls it
     // Fine-grained (uncached across devices): peers store into it over xGMI while this rank polls it, and the protocol has no fences --
-    // on coarse-grained pages a polling load may keep hitting a stale L2 line.  No silent fallback: GBP_PEER_COARSE=1 is a debug switch
-    // for ranks that share ONE device.
-    if (getenv("GBP_PEER_COARSE")) {
-        pe.finegrained = false;
-        HIPCHK(hipMalloc(&pe.mailbox, bytes));
-    } else {
-        const hipError_t fe = hipExtMallocWithFlags(&pe.mailbox, bytes, hipDeviceMallocFinegrained);
-        if (fe != hipSuccess) {
-            (void)hipGetLastError();
-            pe.mailbox = nullptr;
-            return fail(GBP_EHIP, "peer exchange: fine-grained device memory for the mailbox is not available (%s); use the RCCL exchange", hipGetErrorString(fe));
-        }
-        pe.finegrained = true;
+    // on coarse-grained pages a polling load may keep hitting a stale L2 line.  No silent fallback.
+    const hipError_t fe = hipExtMallocWithFlags(&pe.mailbox, bytes, hipDeviceMallocFinegrained);
+    if (fe != hipSuccess) {
+        (void)hipGetLastError();
+        pe.mailbox = nullptr;
+        return fail(GBP_EHIP, "peer exchange: fine-grained device memory for the mailbox is not available (%s); use the RCCL exchange", hipGetErrorString(fe));
     }
     HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(pe.mailbox), (int)PEER_EMPTY32, bytes / 4, h->stream));      // every slot empty (gbp_kernels.hpp: the data is its own arrival flag)
     if (!pe.d_ctl) HIPCHK(hipMalloc(reinterpret_cast<void **>(&pe.d_ctl), 4 * sizeof(int)));
@@ -209,8 +201,7 @@ int gbp_ba_peer_connect(gbp_ba_t *h, int32_t rank, int32_t n_ranks, const void *
     }
     CHK(shard_buffers(h, 1));                                // d_send: the partial sums of the general sweep on their way to the mailboxes
     pe.rank = rank;
-    double ms = 20000.0;                                     // how long a finish kernel waits for a peer before it gives up
-    if (const char *e = getenv("GBP_PEER_TIMEOUT_MS")) ms = std::max(1.0, atof(e));
+    const double ms = h->ovr.peer_timeout_ms;                // how long a finish kernel waits for a peer before it gives up
     int clk_khz = 0;
     if (hipDeviceGetAttribute(&clk_khz, hipDeviceAttributeWallClockRate, h->device) != hipSuccess || clk_khz <= 0) clk_khz = 100000;
     pe.timeout_ticks = (long long)(ms * (double)clk_khz);    // wall_clock64 ticks (100 MHz on MI355X)
@@ -258,9 +249,7 @@ static int sharded_step_peer(gbp_ba *h, int with_messages, int robustify, int lo
     po.stale = peer_data(h, pe.mailbox, n, half ^ 1, 0);      // what the previous exchange delivered here: read then, emptied by this push
     for (int r = 0; r < n; ++r) po.dst[r] = peer_data(h, pe.base[r], n, half, pe.rank);
     PeerWait w{peer_data(h, pe.mailbox, n, half, 0), pe.seq, pe.timeout_ticks, pe.d_ctl + 1, nullptr};
-    // Without a rendezvous hook everything behind the fused sweep is ONE launch (k_cam_reduce_xchg); logical ranks on one device
-    // (the hook is set) keep reduce / push and finish apart, with the hook between them, so that they never spin on each other.
-    const bool merged = !h->xch_fn && with_messages && !getenv("GBP_PEER_SPLIT");      // (fused: k_cam_reduce_xchg; general: k_cam_staged_xchg)
+    const bool merged = merged_exchange(h->xch_fn != nullptr, with_messages, h->ovr);      // (fused: k_cam_reduce_xchg; general: k_cam_staged_xchg)
     bool finished = false;
     // The beliefs of the landmarks that span tiles (k_lmk_finish_parts) go out on THIS stream, as a short launch between the sweep
     // kernel and the reduce (1.3 us, EXPERIMENTS.md round 5).  Round 5 forked them onto a side stream "beside the exchange" -- but the

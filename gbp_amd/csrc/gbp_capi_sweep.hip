@@ -9,7 +9,7 @@
 #include <cmath>
 #include <thread>
 
-int gbp::plan_fused_sweep(gbp_ba *h, int n_cus) { return fused_plan(h->fused, h->p, h->stream, n_cus, h->wg_win.data(), h->wg_cams.data(), (int)h->wg_win.size()); }
+int gbp::plan_fused_sweep(gbp_ba *h, int n_cus) { return fused_plan(h->fused, h->p, h->stream, n_cus, h->ovr, h->wg_win.data(), h->wg_cams.data(), (int)h->wg_win.size()); }
 int gbp::fused_max_cams_of_this_build() { return fused_max_cams(); }
 
 // ------------------------------------------------------------------------------ launches --
@@ -147,14 +147,12 @@ int gbp::sweep_begin(gbp_ba *h, int with_messages, int robustify, int local_reli
             h->ev_used += 2;
         }
         // Every other sweep walks each workgroup's tile range backwards: what the last sweep touched last is touched first, so
-        // whatever part of the state the Infinity Cache still holds is used before it is evicted (GBP_NO_REVERSE: experiment
-        // switch).  With arena_reserve this removed the slow mode of the 1M-factor graph (12 of 12 fresh processes at
-        // 11.6-12.1k sweeps/s; 7 of 12 at 10.0-10.7k without both).
-        static const bool no_rev = getenv("GBP_NO_REVERSE") != nullptr;
-        const int reverse = no_rev ? 0 : (int)(h->walk_parity & 1u);
+        // whatever part of the state the Infinity Cache still holds is used before it is evicted.  With arena_reserve this removed
+        // the slow mode of the 1M-factor graph (12 of 12 fresh processes at 11.6-12.1k sweeps/s; 7 of 12 at 10.0-10.7k without both).
+        const int reverse = (int)(h->walk_parity & 1u);
         h->walk_parity ^= 1u;
         h->cstage_x0_ok = false;                            // (a fused sweep moves linearisation points without staging them)
-        int rc = fused_launch(h->fused, h->p, robustify, local_relin, partial, h->stream, finish, e0, e1, defer_big, reverse, peer, h->clk_cur, merged);
+        int rc = fused_launch(h->fused, h->p, h->ovr, robustify, local_relin, partial, h->stream, finish, e0, e1, defer_big, reverse, peer, h->clk_cur, merged);
         if (merged && peer && finished) *finished = true;
         if (rc != 0) return fail(GBP_EHIP, "fused sweep launch failed: %s", hipGetErrorString((hipError_t)rc));
         if (finished && !(merged && peer)) *finished = finish != 0;
@@ -163,11 +161,10 @@ int gbp::sweep_begin(gbp_ba *h, int with_messages, int robustify, int local_reli
     if (with_messages) {
         // tile sweep: messages + the tiles' landmark beliefs + camera messages staged camera-major.  Every other sweep backwards,
         // like the fused sweep (what the memory-side cache still holds is used first; the results do not depend on the order)
-        static const bool no_rev_g = getenv("GBP_NO_REVERSE") != nullptr;
-        h->p.reverse_walk = no_rev_g ? 0 : (int)(h->gen_parity & 1u);
+        h->p.reverse_walk = (int)(h->gen_parity & 1u);
         h->gen_parity ^= 1u;
         CHK(ensure_staging(h));
-        if (h->p.xtra || getenv("GBP_TILE_KERNEL")) {       // the dense remainder rides in k_factor_tile (one wave per tile)
+        if (h->p.xtra) {       // the dense remainder rides in k_factor_tile (one wave per tile)
             h->dominant = "k_factor_tile";
             h->cstage_x0_ok = false;                        // (its rows may be the wide ones: the next staged sweep writes whole rows)
             CHK(launch_factor_stage(h, robustify, local_relin));
@@ -181,14 +178,8 @@ int gbp::sweep_begin(gbp_ba *h, int with_messages, int robustify, int local_reli
         }
         if (!defer_big) CHK(launch_finish_parts(h, h->stream));
         if (h->p.C) {
-            // One workgroup per camera.  Short runs (a camera with a few hundred factors: graphs with thousands of cameras) leave most
-            // of a 256-thread block idle through its reduction and 6x6 solve: 128 threads do 1M factors x 2 000 / 3 000 cameras in
-            // 125.6 / 127.4 us per sweep against 134.5 / 143.7, 3M factors x 13 682 cameras in 439 against 509; from ~700 factors per
-            // camera on the two are equal, at 2 000 per camera 256 threads win (122.9 against 128.0).  The block size fixes the order of
-            // the sums, so it depends on the graph's shape alone (GBP_CAM_BLOCK overrides, experiments).
-            static const int forced = getenv("GBP_CAM_BLOCK") ? atoi(getenv("GBP_CAM_BLOCK")) : 0;
-            // (and one wave per camera below 200 factors per camera: 1M factors x 20 000 cameras 176 against 243 us, 200k x 5 000 50.5 against 65.8)
-            const int cam_block = forced ? forced : ((long long)h->p.F < 200LL * h->p.C ? 64 : (long long)h->p.F < 640LL * h->p.C ? 128 : BLOCK);
+            const int cam_block = gbp::cam_block(h->p.F, h->p.C, h->ovr);
+            static_assert(BLOCK == 256, "cam_block's widest choice is the BLOCK variant");
             if (merged && peer) {
                 // peer-store exchange: sum -> push -> wait -> finish in this one launch; the grid must be resident at once (its workgroups
                 // wait for other ranks' workgroups), so never more workgroups than the occupancy query admits on this device
@@ -198,9 +189,7 @@ int gbp::sweep_begin(gbp_ba *h, int with_messages, int robustify, int local_reli
                                    : cam_block == 128 ? reinterpret_cast<const void *>(&k_cam_staged_xchg<128>) : reinterpret_cast<const void *>(&k_cam_staged_xchg<BLOCK>);
                     HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, cam_block, 0));
                     if (per_cu < 1 || h->n_cus < 1) return fail(GBP_EHIP, "occupancy query of the staged exchange kernel failed");
-                    int xb = per_cu * h->n_cus;
-                    if (const char *e = getenv("GBP_XCHG_BLOCKS")) xb = std::max(1, std::min(xb, atoi(e)));
-                    h->staged_xchg_blocks[cam_block >> 7] = xb;
+                    h->staged_xchg_blocks[cam_block >> 7] = xchg_blocks(per_cu * h->n_cus, INT32_MAX, h->ovr);
                 }
                 const dim3 grid(std::min(h->p.C, h->staged_xchg_blocks[cam_block >> 7]));
                 PeerWait w = *merged;

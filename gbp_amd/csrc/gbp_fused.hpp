@@ -56,6 +56,7 @@
 #pragma once
 #include "gbp_kernels.hpp"
 #include "gbp_fused_plan.hpp"
+#include "gbp_policy.hpp"
 #include <mutex>
 
 namespace gbp {
@@ -107,40 +108,6 @@ GBP_DEV double2 ld2_nt(const double *__restrict__ base, unsigned byte_off)
     const v2d v = __builtin_nontemporal_load(reinterpret_cast<const v2d *>(reinterpret_cast<const char *>(base) + byte_off));
     return make_double2(v.x, v.y);
 }
-
-// L2 TOUCH-PREFETCH (round 6).  The sweep takes 65 us where its memory traffic alone takes 44 and its arithmetic 27: a wave has loads
-// in flight only between the top of an iteration and the arrival of its streams, and none while it does its maths -- eight waves per
-// CU are then too few requests in flight to keep the memory system busy.  Loading the NEXT tile's streams into registers during the
-// maths was built three times (rounds 2, 3, 4: 84-108 us: 44 more live registers, the stores queue behind eleven more 1 KB loads).
-// This needs neither: after its own stream loads a wave touches one byte of every 64 bytes of the tile that will be taken
-// GBP_PF_DIST tickets later (three instructions, the loaded bytes are thrown away), so that the 11 KB block is on its way into the
-// XCD's L2 -- 4 MB, 128 KB per CU: eight tiles ahead is 88 KB -- while this wave and its neighbours compute; whichever wave draws
-// that ticket finds its streams one L2 hit away instead of one trip to the memory side.
-#ifndef GBP_PF_DIST
-#define GBP_PF_DIST 0
-#endif
-#ifndef GBP_PF_STRIDE
-#define GBP_PF_STRIDE 64
-#endif
-struct Touch { unsigned v[3]; };
-template <bool NT>
-GBP_DEV void touch_tile(const Params &p, int t, int lane, Touch &o)
-{
-    constexpr int LIN_B = LIN_ROWS * WTILE * 8, MSG_B = MSG_ROWS * WTILE * 8, N_LIN = LIN_B / GBP_PF_STRIDE, N = (LIN_B + MSG_B) / GBP_PF_STRIDE;
-    const char *lin_t = reinterpret_cast<const char *>(p.lin + (size_t)t * (LIN_ROWS * WTILE));
-    const char *msg_t = reinterpret_cast<const char *>(p.msg + (size_t)t * (MSG_ROWS * WTILE));
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const int i = j * 64 + lane;
-        o.v[j] = 0;
-        if (j * 64 < N && i < N) {
-            const unsigned char *q = reinterpret_cast<const unsigned char *>(i < N_LIN ? lin_t + i * GBP_PF_STRIDE : msg_t + (i - N_LIN) * GBP_PF_STRIDE);
-            o.v[j] = NT ? __builtin_nontemporal_load(q) : *q;
-        }
-    }
-}
-// the loaded bytes must be waited for somewhere (their registers are dead otherwise and would be handed out while the loads are in flight)
-GBP_DEV void touch_retire(const Touch &o) { asm volatile("" ::"v"(o.v[0]), "v"(o.v[1]), "v"(o.v[2])); }
 
 // nt: bit 0 = the lin rows (x0 | z | variance) stream PAST the memory-side cache, bit 1 = the message rows too (nontemporal loads:
 // no allocation in the 256 MiB Infinity Cache).  The fused sweep of a graph whose whole working set fits that cache uses neither (at the
@@ -218,15 +185,11 @@ __global__ __launch_bounds__(NWAVES * 64) void k_sweep_wat(Params p, FusedArgs a
     // memory lands at or below the old fast mode (2M factors 158.5-161.0 us per step against 165.0-171.1, 10M 698 against 722).  The tiles
     // a workgroup keeps cacheable (FusedArgs::pin) are then one contiguous piece of the graph.  Not with camera windows: a workgroup's
     // camera set lives on its tiles being neighbours.  Not below the cache size: there the contiguous walk is as fast (round 5: 74.6
-    // against 74.3 us) and the plain kernel stays as it is.  (-DGBP_CONTIGUOUS_PINNED: the old walk everywhere, for A/B runs.)
-#if defined(GBP_CONTIGUOUS_PINNED)
-    constexpr bool STRIDED = false;
-#else
+    // against 74.3 us) and the plain kernel stays as it is.
     // (the general sweep -- STAGED: every stream nontemporal, the working set far beyond the cache at any size that matters -- the same:
     //  117.7-119.8 -> 113.6-113.9 us per sweep at 1M factors x 500 cameras, 123.9-125.1 -> 118.4-118.9 at 2 000; its camera sums are made in
     //  the cameras' own order by another kernel, so its results do not change by a bit)
     constexpr bool STRIDED = (PINNED && !WINDOWED) || STAGED;
-#endif
     const int tb = STRIDED ? 0 : (int)((long long)blockIdx.x * p.T / gridDim.x);
     const int ntl = STRIDED ? (p.T - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x : (int)((long long)(blockIdx.x + 1) * p.T / gridDim.x) - tb;
 
@@ -273,18 +236,6 @@ __global__ __launch_bounds__(NWAVES * 64) void k_sweep_wat(Params p, FusedArgs a
         // camera rows: nontemporal message stores as well as loads, 116.6-117.3 against 119.4-119.7 us per sweep with plain stores)
         const bool past = STAGED || (PINNED && li >= a.pin);
         issue_streams<LOSS, STAGED>(p, t, lane, S, past ? 3 : (PINNED ? a.nt : 0));      // (FusedArgs::nt: experiments with the pinned variant only)
-#if GBP_PF_DIST > 0
-        Touch pf;
-        bool pf_on = false;
-        if (!STAGED) {
-            const int tip = ti + GBP_PF_DIST;                  // (wave-uniform)
-            if (tip < ntl) {
-                const int tp = tb + (a.reverse ? ntl - 1 - tip : tip);
-                if (PINNED && (tp - tb) >= a.pin) touch_tile<true>(p, tp, lane, pf); else touch_tile<false>(p, tp, lane, pf);
-                pf_on = true;
-            }
-        }
-#endif
         const unsigned lo = (unsigned)lane * 16u;
         double x0[9], z[2], avar = p.sigma2, qC[2], qL[2], WC[3], VL[3], muC[6], PC[21];
         const unsigned long long words = (unsigned long long)__double_as_longlong(S.a[5].y);      // meta (low) | state (high): gbp_kernels.hpp ROW_SM
@@ -339,9 +290,6 @@ __global__ __launch_bounds__(NWAVES * 64) void k_sweep_wat(Params p, FusedArgs a
         }
         asm volatile("" ::: "memory");
         GBP_PH(4);                                         // camera gather
-#if GBP_PF_DIST > 0
-        if (pf_on) touch_retire(pf);                       // (issued right behind the streams: long since back when the gather has arrived)
-#endif
 
         // landmark heads -> wave scratch -> the lanes of their factors
 #pragma unroll
@@ -566,9 +514,7 @@ __global__ __launch_bounds__(RED_THREADS) void k_cam_reduce_tree(Params p, const
 // Camera windows leave a camera a handful of rows (those of the workgroups whose camera set holds it: two to five in a sequence, where
 // k_cam_reduce_tree's 1024 threads per camera took 43.7 us for 10 000 cameras): one WAVE per camera.  Lane (g, pair) = (lane / 14,
 // lane % 14), g < 4, adds the 16-byte piece `pair` of rows g, g + 4, ...; the four partial sums are added in the order of g.  Returns
-// entry `lane` (< 27) of the sum.  fused_plan picks this form when the cameras have at most ROWS_WAVE_MAX rows on average (fr1desk_small
-// with windows forced: 41 rows per camera, 5.1 us in this form against 3.6 in the tree form).
-constexpr int ROWS_WAVE_MAX = 16;
+// entry `lane` (< 27) of the sum.  fused_plan picks this form by rows_wave (gbp_policy.hpp).
 constexpr int ROWS_THREADS = 256;
 GBP_DEV double cam_rows_sum_wave(const double *__restrict__ src, int n_rows, int lane)
 {
@@ -620,7 +566,6 @@ __global__ __launch_bounds__(ROWS_THREADS) void k_cam_reduce_rows(Params p, cons
 // reduce -> finish as two launches this saves a kernel boundary and the global "all rows are out" hand-off; against RCCL also the
 // collective's launch and sync.
 constexpr int XCHG_THREADS = 256;
-constexpr int XCHG_BLOCKS = 2048;
 template <bool WAVE_ROWS>                                   // WAVE_ROWS: one wave per camera adds its few rows (camera windows, cam_rows_sum_wave)
 __global__ __launch_bounds__(XCHG_THREADS) void k_cam_reduce_xchg(Params p, const double *__restrict__ block_partials, int n_blocks,
                                                                   double *__restrict__ partial, PeerOut peer, PeerWait wait, unsigned long long *clk,
@@ -702,7 +647,7 @@ __global__ __launch_bounds__(64) void k_single_probe(int *out)
 }
 
 // 1: the device adds same-address lanes in lane order, 0: it does not (mask of failing patterns in *mask), < 0: the probe could not run
-inline int single_probe(hipStream_t stream, int *mask)
+inline int single_probe(hipStream_t stream, const Overrides &o, int *mask)
 {
     static std::mutex mtx;
     static std::vector<int> cache;                          // per device: -1 unknown, else the failing-pattern mask
@@ -720,8 +665,7 @@ inline int single_probe(hipStream_t stream, int *mask)
         if (!ok) return -1;
         cache[dev] = v;
     }
-    int v = cache[dev];
-    if (const char *e = getenv("GBP_SINGLE_PROBE_FAIL")) v = atoi(e);          // test switch: pretend the probe saw this mask
+    const int v = single_probe_mask(cache[dev], o);
     if (mask) *mask = v;
     return v == 0 ? 1 : 0;
 }
@@ -760,11 +704,11 @@ inline SweepKernel sweep_variant(int loss, bool pinned, bool single, bool window
 
 // wg_win / wg_cams (n_win = workgroups, or 0): the workgroups' camera windows -- build_graph's decision (k_wg_cam_sets: per workgroup
 // {lowest camera, cameras in its set, offset into wg_cams, width of its interval}); without them every workgroup's table covers all cameras.
-inline int fused_plan(FusedPlan &pl, const Params &p, hipStream_t stream, int n_cus, const int4 *wg_win = nullptr, const int *wg_cams = nullptr, int n_win = 0)
+inline int fused_plan(FusedPlan &pl, const Params &p, hipStream_t stream, int n_cus, const Overrides &o, const int4 *wg_win = nullptr,
+                      const int *wg_cams = nullptr, int n_win = 0)
 {
     if (p.F == 0 || p.C == 0 || p.T == 0) return 0;
-    pl.n_blocks = std::max(1, std::min(p.T, n_cus));
-    if (const char *nb = getenv("GBP_FUSED_BLOCKS")) pl.n_blocks = std::max(1, std::min(pl.n_blocks, atoi(nb)));   // experiment switch
+    pl.n_blocks = fused_workgroups(p.T, n_cus, o);
     pl.windowed = (wg_win && wg_cams && n_win == pl.n_blocks) ? 1 : 0;
     pl.rows_wave = 0;
     // the sweep's table shares the LDS with the waves' scratch: more cameras than fit run the general sweep (STAGED form of the same loop)
@@ -798,14 +742,7 @@ inline int fused_plan(FusedPlan &pl, const Params &p, hipStream_t stream, int n_
                 int2 &cr = cam_rows[(size_t)wg_cams[(size_t)wg_win[b].z + k]];
                 rowidx[(size_t)wg_win[b].z + k] = cr.x + cr.y++;
             }
-        // few rows per camera ON AVERAGE: one wave adds them (k_cam_reduce_rows).  A wave takes 32 rows per round trip, so one camera
-        // with many rows costs that launch microseconds where the tree form costs every camera a 1024-thread workgroup -- which is also
-        // why MANY cameras take the wave form whatever their rows (tools/manycam_probe.sh, random cameras, us per launch tree / wave:
-        // 2 000 cameras x 29 rows 11.4 / 6.8, x 56 rows 12.1 / 8.1; 5 000 x 24 24.8 / 9.6; 1 000 x 99 8.3 / 7.7; 500 x 100 5.4 / 6.5, x 160
-        // 5.9 / 7.7: tree ~ 2.6 + 0.004 C + 0.017 R, wave ~ 5.2 + 0.0003 C + 0.025 R with R in thousands of rows).
-        const char *e = getenv("GBP_ROWS_WAVE_MAX");        // (tests: 0 keeps the tree form)
-        const int wave_max = e ? atoi(e) : ROWS_WAVE_MAX;
-        pl.rows_wave = (table_rows <= (size_t)wave_max * (size_t)p.C || (!e && (double)p.C > 662.0 + 2.16e-3 * (double)table_rows)) ? 1 : 0;
+        pl.rows_wave = rows_wave(table_rows, p.C, o) ? 1 : 0;      // few rows per camera: one wave adds them (k_cam_reduce_rows)
         if (fused_shmem_windows(pl.max_window, pl.max_width) > (size_t)LDS_BYTES) { pl.windowed = 0; return 0; }
     }
     if (!pl.windowed && p.C > cmax) return 0;
@@ -828,43 +765,21 @@ inline int fused_plan(FusedPlan &pl, const Params &p, hipStream_t stream, int n_
 #if defined(GBP_FUSED_DBG_SWITCHES) || defined(GBP_PHASE_TIMING)
     if (instrument_plan(pl, stream)) return -1;             // experimental/gbp_instrument.hpp: GBP_FUSED_DBG, the phase buffer
 #endif
-    {
-        // What a sweep touches, against the 256 MiB memory-side cache.  Everything fits: nothing bypasses it.  Beyond it the first
-        // tiles of every workgroup's range -- 160 MiB worth, tables and records included -- keep using the cache and stay resident
-        // from sweep to sweep; the remaining tiles stream PAST it, loads and message stores (nontemporal), instead of everything
-        // thrashing: 72.8 against 78.0 ps per factor at 1.35M factors, 72.8 / 75.8 at 2M, 68.5 / 69.2 at 10M against the round's
-        // earlier policy (lin rows of ALL tiles past the cache, bit 0 of nt, which had brought 1.2M-1.5M from 83 to 76-78), and
-        // WORSE below the cache size (71.3 against 67.3 at 1.1M): profiles/r04_size_sweep.jsonl, EXPERIMENTS.md.  The split is
-        // per workgroup so that all of them finish together.
-        const double S = (double)p.T * WTILE, MiB = 1024.0 * 1024.0;
-        const double fixed = (double)table_rows * TROW * 8 + (double)p.C * (CAMREC + CBEL + 27) * 8;
-        const double touched = S * (LIN_ROWS + MSG_ROWS) * 8 + S * 8 + (double)p.L * LREC * 8 + fixed;
-        const double per_tile = WTILE * (LIN_ROWS + MSG_ROWS) * 8.0 + (double)p.L * LREC * 8 / std::max(p.T, 1);
-        // (the share that pays shrinks with the distance from the cache size: 200 MiB just beyond it -- 67.1 against 70.7 ps per factor at
-        //  1.15M factors with 160 -- 140 from 1.5M factors on: 73.4 against 76.2 / 78.3 with 180 / 220)
-        // (round 6, with the strided walk of the pinned variant -- the cacheable tiles are one contiguous piece of the graph then -- a larger
-        //  share pays than the 140-200 MiB above: 1.15M factors 73.6 us per launch with 240 MiB against 76.9 with 200; 1.35M 88.1 with 220,
-        //  89.0 with 240, 90.9 with 200, 93.0 with 140; 2M 134.4 with 200, 137.0 with 220, 139.0 with 140, 141.3 with 240; 3M 205.4 with
-        //  200, 210.5 with 220; 10M flat: profiles/r06_keep_sweep.txt)
-        double keep_mib = touched > 256.0 * MiB ? (touched < 350.0 * MiB ? 230.0 : 200.0) : -1.0;      // < 0: everything stays cacheable
-        if (const char *e = getenv("GBP_FUSED_PIN_MIB")) keep_mib = atof(e);
-        pl.args.nt = 0;
-        pl.args.pin = 0x7fffffff;
-        if (keep_mib >= 0.0) pl.args.pin = (int)(std::max(0.0, keep_mib * MiB - fixed) / per_tile / pl.n_blocks);
-        // few cameras: many factors of a 60-factor tile share one (fr1desk: 63 cameras, up to eight) -- the SINGLE variant of the accumulation
-        pl.single = getenv("GBP_ACC_SINGLE") ? atoi(getenv("GBP_ACC_SINGLE")) : (pl.group_cams <= (pl.args.pin != 0x7fffffff ? 200 : 350) ? 1 : 0);      // (1M factors: 66.1 against 75.1 us per step at 64 cameras, 68.0 / 72.4 at 128, 69.7 / 71.6 at 200, 72.7 / 73.4 at 300, equal at 400, 75.2 / 74.3 at 500; beyond the cache size -- the pinned variant -- 2M factors: 135.4 / 148.3 at 100 cameras, 151.0 / 143.7 at 300)
-        if (pl.single) {                                    // the order SINGLE relies on is verified on this device before it is used (single_probe)
-            pl.single_probe = single_probe(stream, &pl.single_probe_mask);
-            if (pl.single_probe < 0) return -1;
-            if (pl.single_probe == 0) {
-                pl.single = 0;
-                fprintf(stderr, "[gbp] this device does not apply same-address LDS atomics of one instruction in lane order (probe mask 0x%x): "
-                                "the fused sweep uses one accumulation round per rank instead\n", pl.single_probe_mask);
-            }
+    const SweepBytes sb = sweep_bytes(p.T, p.L, p.C, table_rows);
+    const double keep_mib = cache_keep_mib(sb.touched, o);
+    pl.args.pin = pinned_tiles(keep_mib, sb.fixed, sb.per_tile, pl.n_blocks);
+    pl.single = single_accumulation(pl.group_cams, pl.args.pin != 0x7fffffff, o);
+    if (pl.single) {                                    // the order SINGLE relies on is verified on this device before it is used (single_probe)
+        pl.single_probe = single_probe(stream, o, &pl.single_probe_mask);
+        if (pl.single_probe < 0) return -1;
+        if (pl.single_probe == 0) {
+            pl.single = 0;
+            fprintf(stderr, "[gbp] this device does not apply same-address LDS atomics of one instruction in lane order (probe mask 0x%x): "
+                            "the fused sweep uses one accumulation round per rank instead\n", pl.single_probe_mask);
         }
-        if (const char *e = getenv("GBP_FUSED_NT")) pl.args.nt = atoi(e);      // experiments: bit 0 lin rows, bit 1 message rows of the cacheable tiles
-        if (getenv("GBP_PLAN_DEBUG")) fprintf(stderr, "[gbp] fused plan: T %d blocks %d touched %.1f MiB keep %.1f MiB pin %d tiles per workgroup\n", p.T, pl.n_blocks, touched / MiB, keep_mib, pl.args.pin);
     }
+    pl.args.nt = o.fused_nt.value_or(0);                 // (experiments: bit 0 lin rows, bit 1 message rows of the cacheable tiles)
+    if (o.plan_debug) fprintf(stderr, "[gbp] fused plan: T %d blocks %d touched %.1f MiB keep %.1f MiB pin %d tiles per workgroup\n", p.T, pl.n_blocks, sb.touched / (1024.0 * 1024.0), keep_mib, pl.args.pin);
     pl.shmem = shmem;
     // (the attribute belongs to the FUNCTION, not to this plan: every handle asks for the whole LDS, so that a later handle with a smaller
     //  table cannot lower what an earlier one launches with)
@@ -876,7 +791,7 @@ inline int fused_plan(FusedPlan &pl, const Params &p, hipStream_t stream, int n_
 }
 
 // returns 0 or a hipError_t value
-inline int fused_launch(FusedPlan &pl, const Params &p0, int robustify, int local_relin, double *partial, hipStream_t stream,
+inline int fused_launch(FusedPlan &pl, const Params &p0, const Overrides &o, int robustify, int local_relin, double *partial, hipStream_t stream,
                         int finish, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr, bool defer_big = false, int reverse = 0,
                         const PeerOut *peer = nullptr, unsigned long long *clk = nullptr, const PeerWait *merged = nullptr)
 {
@@ -903,9 +818,7 @@ inline int fused_launch(FusedPlan &pl, const Params &p0, int robustify, int loca
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, XCHG_THREADS, red_shmem) != hipSuccess ||
                 hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || per_cu < 1 || cus < 1)
                 return (int)hipErrorUnknown;
-            xb = std::min(XCHG_BLOCKS, per_cu * cus);
-            if (const char *e = getenv("GBP_XCHG_BLOCKS")) xb = std::max(1, std::min(xb, atoi(e)));
-            pl.xchg_blocks = xb;
+            xb = pl.xchg_blocks = xchg_blocks(per_cu * cus, XCHG_BLOCKS, o);
         }
         if (pl.rows_wave)
             hipLaunchKernelGGL(k_cam_reduce_xchg<true>, dim3(std::min((p.C + XCHG_THREADS / 64 - 1) / (XCHG_THREADS / 64), xb)), dim3(XCHG_THREADS), red_shmem, stream, p,

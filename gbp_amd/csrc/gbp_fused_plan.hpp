@@ -11,6 +11,7 @@
 namespace gbp {
 
 constexpr int LDS_BYTES = 160 * 1024;
+constexpr int XCHG_BLOCKS = 2048;                   // most workgroups of the merged reduce-exchange-finish launch (k_cam_reduce_xchg, fused_launch)
 constexpr int TROW = 28;                            // doubles per row of the workgroup tables in HBM (27 + pad: 16-byte stores / loads)
 #ifndef GBP_WAT_WAVES
 #define GBP_WAT_WAVES 8
@@ -69,7 +70,7 @@ struct FusedPlan {
     long long table_rows = 0;                        // rows of block_partials
     int windowed = 0, max_window = 0, max_width = 0; // camera WINDOWS: every workgroup's table covers the cameras its own tiles meet (fused_plan): the largest
                                                      // set, and the widest interval lowest .. highest camera (the 16-bit map camera -> table row covers it)
-    int rows_wave = 0;                               // windowed and at most ROWS_WAVE_MAX rows per camera on average: the reduce runs one wave per camera
+    int rows_wave = 0;                               // windowed and few rows per camera (rows_wave, gbp_policy.hpp): the reduce runs one wave per camera
     const int2 *d_cam_rows = nullptr;                // windowed: per camera {first row, rows} of block_partials, else NULL (camera c: rows c n .. c n + n - 1)
     int single = 0;                                  // launch the SINGLE variant (all same-camera lanes of a tile in one ds_add_f64 per entry)
     int single_probe = -1;                           // -1: SINGLE not wanted, no probe; 1: the device's lane order was verified; 0: it failed, rounds variant instead
@@ -120,6 +121,14 @@ __host__ __device__ constexpr int win_rows_ints(int set) { return (set + 1) & ~1
 inline size_t fused_shmem_windows(int set, int width)
 {
     return fused_shmem(std::max(set, 1)) + (size_t)win_rows_ints(std::max(set, 1)) * sizeof(int) + (((size_t)width * 2 + 7) & ~(size_t)7);
+}
+
+// bytes one fused sweep touches (fused_plan: against the memory-side cache): tables + camera records, everything, one tile's share
+struct SweepBytes { double fixed, touched, per_tile; };
+inline SweepBytes sweep_bytes(int T, int L, int C, size_t table_rows)
+{
+    const double S = (double)T * WTILE, fixed = (double)table_rows * TROW * 8 + (double)C * (CAMREC + CBEL + 27) * 8;
+    return {fixed, S * (LIN_ROWS + MSG_ROWS) * 8 + S * 8 + (double)L * LREC * 8 + fixed, WTILE * (LIN_ROWS + MSG_ROWS) * 8.0 + (double)L * LREC * 8 / std::max(T, 1)};
 }
 
 // most cameras whose table + the per-wave scratch fit the LDS (the plan falls back to the general sweep above it)

@@ -12,6 +12,7 @@
 #include "../../include/gbp_ba.h"
 #include "gbp_kernels.hpp"
 #include "gbp_fused_plan.hpp"
+#include "gbp_policy.hpp"
 
 #include <rccl/rccl.h>      // types only: the library is dlopen()ed when a communicator is asked for (no link-time dependency)
 
@@ -48,6 +49,7 @@ struct gbp_ba {
     Params p{};
     int device = 0;
     int flags = 0;
+    Overrides ovr;                               // the environment's overrides of the sweep policy, read once by gbp_ba_create (gbp_policy.hpp)
     hipStream_t own_stream = nullptr, stream = nullptr;
     // order maps: on the device (built there, gbp_build.hpp); the host keeps only what is L- or C-sized
     int *d_ref_cam = nullptr, *d_ref_lmk = nullptr;   // per reference factor (p.cadj = reference id -> slot, p.cpos = slot -> reference id)
@@ -113,7 +115,7 @@ struct gbp_ba {
     ncclComm_t comm = nullptr;
     // peer-store exchange (gbp_ba_peer_export / gbp_ba_peer_connect): this rank's mailbox and the peers' mapped ones
     struct Peer {
-        void *mailbox = nullptr; bool finegrained = false;
+        void *mailbox = nullptr;
         int n_ranks = 0, rank = 0; bool connected = false;
         void *base[MAX_PEERS] = {}; bool opened[MAX_PEERS] = {};
         unsigned long long seq = 0;
@@ -154,7 +156,7 @@ inline int dev_alloc(gbp_ba *h, T **out, size_t n, bool zero = true)
 // mode becomes rare.  It also saves a dozen allocation calls (most of what is left of gbp_ba_create's time).
 inline int arena_reserve(gbp_ba *h, size_t bytes)
 {
-    if (h->arena || getenv("GBP_NO_ARENA")) return GBP_OK;
+    if (h->arena) return GBP_OK;
     HIPCHK(hipMalloc(&h->arena, bytes));
     h->allocs.push_back(h->arena);
     h->arena_bytes = bytes;

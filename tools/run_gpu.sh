@@ -10,7 +10,6 @@ PY
 }
 python bench.py --full --no-cpu-baseline --no-hbm-size --steps 20 --warmup 5 2>/dev/null > $O/b.json; show $O/b.json fused
 python bench.py --full --no-cpu-baseline --no-fused --steps 20 --warmup 5 2>/dev/null > $O/b.json; show $O/b.json nofused
-GBP_TILE_KERNEL=1 python bench.py --full --no-cpu-baseline --no-fused --steps 20 --warmup 5 2>/dev/null > $O/b.json; show $O/b.json nofused-tile-kernel
 python bench.py --full --no-cpu-baseline --cams 2000 --steps 20 --warmup 5 2>/dev/null > $O/b.json; show $O/b.json cams2000
 python bench.py --full --no-cpu-baseline --cams 1000 --steps 20 --warmup 5 2>/dev/null > $O/b.json; show $O/b.json cams1000
 python bench.py --full --no-cpu-baseline --cams 3000 --steps 20 --warmup 5 2>/dev/null > $O/b.json; show $O/b.json cams3000
