@@ -53,6 +53,13 @@ class Desc(ct.Structure):
                 ('nstds', ct.c_double), ('beta', ct.c_double), ('eta_damping', ct.c_double)]
 
 
+class Ext(ct.Structure):
+    """gbp_ba_ext_t (include/gbp_ba.h): the batch gbp_ba_extend appends."""
+    _fields_ = [('n_new_cams', ct.c_int32), ('n_new_lmks', ct.c_int32), ('n_new_factors', ct.c_int32), ('flags', ct.c_int32),
+                ('cam_means', _dp), ('lmk_means', _dp), ('meas', _dp), ('cam_idx', _ip), ('lmk_idx', _ip),
+                ('prior_weaker_factor', ct.c_double), ('cam_prior_lambda', _dp), ('lmk_prior_lambda', _dp)]
+
+
 class GbpError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libgbp_hip error {code}: {msg}")
@@ -67,6 +74,7 @@ SIGNATURES = {
     'gbp_ba_destroy': (None, [ct.c_void_p]),
     'gbp_ba_set_stream': (ct.c_int, [ct.c_void_p, ct.c_void_p]),
     'gbp_ba_sync': (ct.c_int, [ct.c_void_p]),
+    'gbp_ba_extend': (ct.c_int, [ct.c_void_p, ct.POINTER(Ext), _ip]),
     'gbp_ba_generate_priors': (ct.c_int, [ct.c_void_p, ct.c_double]),
     'gbp_ba_factor_lambda_max': (ct.c_int, [ct.c_void_p, _dp, _dp]),
     'gbp_ba_set_prior_scalars': (ct.c_int, [ct.c_void_p, _dp, _dp]),

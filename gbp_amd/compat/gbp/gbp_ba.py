@@ -348,6 +348,41 @@ class BAFactorGraph:
         order, ptr = (self._adj[0], self._adj[1]) if kind == 0 else (self._adj[2], self._adj[3])
         return order[ptr[i]:ptr[i + 1]]
 
+    # ---- growth (BAEngine.extend, include/gbp_ba.h gbp_ba_extend) -----------------------------------------------
+    def extend(self, cam_means, lmk_means, meas, cam_idx, lmk_idx, *, prior_weaker_factor=50.0, cam_prior_lambda=None,
+               lmk_prior_lambda=None, device_pointers=None):
+        """Append cameras, landmarks and observations (ids in the union numbering) the way a reference script appends nodes and factors
+        (gbp_ba.py:114-141), with priors for the new nodes and update_all_beliefs; every node and factor view is rebuilt over the union.
+        Returns old_to_new (the union id of every old factor).
+
+        Node and factor views taken BEFORE extend are stale afterwards: they index the old numbering (factor ids move when observations
+        of old cameras arrive, see old_to_new) and are no longer kept current.  Take them again from cam_nodes / lmk_nodes / factors."""
+        self._flush()
+        if device_pointers is not None:
+            raise ValueError("BAFactorGraph keeps a host copy of the factor ids: pass host arrays")
+        ci, li = np.asarray(cam_idx, np.int32).reshape(-1), np.asarray(lmk_idx, np.int32).reshape(-1)
+        o2n = self._engine.extend(cam_means, lmk_means, meas, ci, li, prior_weaker_factor=prior_weaker_factor,
+                                  cam_prior_lambda=cam_prior_lambda, lmk_prior_lambda=lmk_prior_lambda)
+        cam_of = np.empty(self._engine.F, np.int32)
+        lmk_of = np.empty(self._engine.F, np.int32)
+        keep = np.ones(self._engine.F, bool)
+        keep[o2n] = False
+        cam_of[o2n], lmk_of[o2n] = self._cam_of, self._lmk_of
+        order = reference_factor_order(ci)                  # new factors take the free ids in batch order inside each camera
+        new_ids = np.flatnonzero(keep)
+        cam_of[new_ids], lmk_of[new_ids] = ci[order], li[order]
+        self._cam_of, self._lmk_of = cam_of, lmk_of
+        self._C, self._L, self._F = self._engine.C, self._engine.L, self._engine.F
+        self.cam_nodes = _Lazy(self._C, lambda i: _VariableView(self, 0, i))
+        self.lmk_nodes = _Lazy(self._L, lambda i: _VariableView(self, 1, i))
+        self.factors = _FactorSeq(self, self._F)
+        self.var_nodes = _Concat(self.cam_nodes, self.lmk_nodes)
+        self.n_var_nodes, self.n_factor_nodes, self.n_edges = self._C + self._L, self._F, 2 * self._F
+        self._cache = {}
+        self._iters_dev, self._iters_fresh, self._views_out = None, False, False
+        self._adj = None
+        return o2n
+
     # ---- priors (gbp_ba.py:20-52) ------------------------------------------------------------------------------
     def generate_priors_var(self, weaker_factor=100):
         self._flush()

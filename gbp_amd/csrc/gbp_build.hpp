@@ -399,11 +399,13 @@ __global__ __launch_bounds__(BLOCK) void k_cam_max(Params p, const double *__res
     }
 }
 
-// prior Lambda = (lambda / w2) I, eta = Lambda mu   (gbp_ba.py:32-34; w2 = weaker_factor^2, 1 when the caller gives Lambda)
+// prior Lambda = (lambda / w2) I, eta = Lambda mu   (gbp_ba.py:32-34; w2 = weaker_factor^2, 1 when the caller gives Lambda), on cameras
+// [c0, c1) and landmarks [l0, l1) (all of them but after gbp_ba_extend, which sets the new variables' priors alone)
 __global__ __launch_bounds__(BLOCK) void k_prior_scalars(Params p, const double *__restrict__ cam_lambda, const double *__restrict__ lmk_lambda,
-                                                         double w2)
+                                                         double w2, int c0, int c1, int l0, int l1)
 {
     const int v = blockIdx.x * BLOCK + threadIdx.x;
+    if (v < p.C ? (v < c0 || v >= c1) : (v - p.C < l0 || v - p.C >= l1)) return;
     if (v < p.C) {
         const double lam = cam_lambda[v] / w2;
         double *pr = p.cprior + (size_t)v * 27;

@@ -89,6 +89,7 @@ static int scratch_alloc(gbp_ba *h, std::vector<void *> &scratch, T **out, size_
 
 }  // extern "C++"
 
+extern "C++" {
 // GBP_BUILD_TIMING: wall time of the stages of gbp_ba_create on stderr (each mark synchronises the stream: diagnostic only)
 struct BuildClock {
     bool on; hipStream_t s; std::chrono::steady_clock::time_point t0;
@@ -103,7 +104,9 @@ struct BuildClock {
     }
 };
 
-static int build_graph(gbp_ba *h, const gbp_ba_desc_t *d, std::vector<void *> &scratch, int n_cus)
+// The graph of a descriptor onto a handle whose Params scalars, flags, overrides and stream are set.  ref_file_out (may be NULL) receives
+// the reference id -> file index map the build used, a scratch buffer, or NULL when the file order is camera-major already (identity).
+int gbp::build_graph(gbp_ba *h, const gbp_ba_desc_t *d, std::vector<void *> &scratch, int n_cus, const int **ref_file_out)
 {
     BuildClock clk(h->ovr.build_timing, h->stream);
     const int C = d->n_cams, L = d->n_lmks, F = d->n_factors;
@@ -152,6 +155,7 @@ static int build_graph(gbp_ba *h, const gbp_ba_desc_t *d, std::vector<void *> &s
         HIPCHK(hipMemcpyAsync(h->d_ref_cam, cam_idx, Fz * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
         HIPCHK(hipMemcpyAsync(h->d_ref_lmk, lmk_idx, Fz * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
     }
+    if (ref_file_out) *ref_file_out = ref_file;
     hipLaunchKernelGGL(k_lower_bounds, dim3(grid_for((size_t)C + 1)), dim3(BLOCK), 0, h->stream, h->d_ref_cam, F, cptr, C);
     // 3. landmark-major, stable in reference id (= VariableNode.adj_factors order, gbp_ba.py:139)
     if (F) HIPCHK((hipError_t)sort_pairs(sort_tmp, sort_bytes, h->d_ref_lmk, lm_key, iota, lm2ref, Fz, bits_l, h->stream));
@@ -327,6 +331,7 @@ static int build_graph(gbp_ba *h, const gbp_ba_desc_t *d, std::vector<void *> &s
     clk.mark("fused plan");
     return GBP_OK;
 }
+}  // extern "C++"
 
 static int create_impl(gbp_ba *h, const gbp_ba_desc_t *d)
 {
@@ -435,19 +440,6 @@ int gbp_ba_sync(gbp_ba_t *h)
 
 // ------------------------------------------------------------------------------- priors ---
 
-// max over the adjacent factors of every variable of max(Lambda_f) (gbp_ba.py:27-31) into d_varmax = cameras | landmarks
-static int variable_lambda_max(gbp_ba *h)
-{
-    const Params &p = h->p;
-    const size_t S = n_slots(h);
-    CHK(ensure_tmp(h, sizeof(double) * S));
-    if (p.T) hipLaunchKernelGGL(k_factor_lambda_max, dim3(grid_for(S)), dim3(BLOCK), 0, h->stream, p, h->d_tmp);
-    if (p.C) hipLaunchKernelGGL(k_cam_max, dim3(p.C), dim3(BLOCK), 0, h->stream, p, h->d_tmp, h->d_varmax);
-    if (p.L) hipLaunchKernelGGL(k_lmk_max, dim3(grid_for((size_t)p.L)), dim3(BLOCK), 0, h->stream, p, h->d_tmp, h->d_varmax + p.C);
-    HIPCHK(hipGetLastError());
-    return GBP_OK;
-}
-
 int gbp_ba_factor_lambda_max(gbp_ba_t *h, double *cam_max, double *lmk_max)
 {
     ENTER(h);
@@ -467,7 +459,8 @@ int gbp_ba_set_prior_scalars(gbp_ba_t *h, const double *cam_lambda, const double
     if (!cam_lambda || !lmk_lambda) return fail(GBP_EINVAL, "null argument");
     if (p.C) HIPCHK(hipMemcpyAsync(h->d_varmax, cam_lambda, sizeof(double) * (size_t)p.C, hipMemcpyHostToDevice, h->stream));
     if (p.L) HIPCHK(hipMemcpyAsync(h->d_varmax + p.C, lmk_lambda, sizeof(double) * (size_t)p.L, hipMemcpyHostToDevice, h->stream));
-    if (p.C + p.L) hipLaunchKernelGGL(k_prior_scalars, dim3(grid_for((size_t)p.C + p.L)), dim3(BLOCK), 0, h->stream, p, h->d_varmax, h->d_varmax + p.C, 1.0);
+    if (p.C + p.L) hipLaunchKernelGGL(k_prior_scalars, dim3(grid_for((size_t)p.C + p.L)), dim3(BLOCK), 0, h->stream, p, h->d_varmax, h->d_varmax + p.C, 1.0,
+                                      0, p.C, 0, p.L);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));               // the arrays are the caller's
     return GBP_OK;
@@ -481,7 +474,7 @@ int gbp_ba_generate_priors(gbp_ba_t *h, double weaker_factor)
     const Params &p = h->p;
     CHK(variable_lambda_max(h));                           // nothing F-sized leaves the device
     if (p.C + p.L) hipLaunchKernelGGL(k_prior_scalars, dim3(grid_for((size_t)p.C + p.L)), dim3(BLOCK), 0, h->stream, p, h->d_varmax,
-                                      h->d_varmax + p.C, weaker_factor * weaker_factor);
+                                      h->d_varmax + p.C, weaker_factor * weaker_factor, 0, p.C, 0, p.L);
     HIPCHK(hipGetLastError());
     return GBP_OK;
 }
@@ -598,6 +591,32 @@ int gbp_ba_info(gbp_ba_t *h, int32_t *fused_path, int32_t *n_tiles, int32_t *n_b
 
 
 }  // extern "C"
+
+// max over the adjacent factors of every variable of max(Lambda_f) (gbp_ba.py:27-31) into d_varmax = cameras | landmarks
+int gbp::variable_lambda_max(gbp_ba *h)
+{
+    const Params &p = h->p;
+    const size_t S = n_slots(h);
+    CHK(ensure_tmp(h, sizeof(double) * S));
+    if (p.T) hipLaunchKernelGGL(k_factor_lambda_max, dim3(grid_for(S)), dim3(BLOCK), 0, h->stream, p, h->d_tmp);
+    if (p.C) hipLaunchKernelGGL(k_cam_max, dim3(p.C), dim3(BLOCK), 0, h->stream, p, h->d_tmp, h->d_varmax);
+    if (p.L) hipLaunchKernelGGL(k_lmk_max, dim3(grid_for((size_t)p.L)), dim3(BLOCK), 0, h->stream, p, h->d_tmp, h->d_varmax + p.C);
+    HIPCHK(hipGetLastError());
+    return GBP_OK;
+}
+
+// prior Lambda = (lambda / w2) I, eta = Lambda mu on cameras [c0, C) and landmarks [l0, L) only, lambda from d_varmax (gbp_ba_extend: the NEW
+// variables; w2 = weaker_factor^2 for the rule, 1 for given scalars)
+int gbp::prior_scalars_range(gbp_ba *h, int c0, int l0, double w2_cam, double w2_lmk)
+{
+    const Params &p = h->p;
+    if (p.C > c0) hipLaunchKernelGGL(k_prior_scalars, dim3(grid_for((size_t)p.C)), dim3(BLOCK), 0, h->stream, p, h->d_varmax, h->d_varmax + p.C, w2_cam,
+                                     c0, p.C, p.L, p.L);
+    if (p.L > l0) hipLaunchKernelGGL(k_prior_scalars, dim3(grid_for((size_t)p.C + p.L)), dim3(BLOCK), 0, h->stream, p, h->d_varmax, h->d_varmax + p.C,
+                                     w2_lmk, p.C, p.C, l0, p.L);
+    HIPCHK(hipGetLastError());
+    return GBP_OK;
+}
 
 // digest of the layout: a state blob restores only into a handle of the same graph
 int gbp::graph_hash(gbp_ba *h, uint64_t *out)

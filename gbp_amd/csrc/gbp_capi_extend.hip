@@ -1,0 +1,280 @@
+// gbp_capi_extend.hip -- libgbp_hip.so, growth of a live handle (gbp_ba_extend, include/gbp_ba.h): the reference appends variable
+// and factor objects to Python lists and every piece of solver state survives (gbp_ba.py:114-141); here the union graph is BUILT
+// beside the handle by the create path (gbp::build_graph, from arrays assembled on the device), the old factors' and variables' state
+// is transplanted into the union's layout, and the union is swapped in only when everything has succeeded.
+//
+// The union's "file order" is the old factors in the old reference order followed by the batch: create's stable camera-major sort then
+// gives exactly the reference's union order (old factors before new ones inside a camera), the new factors are linearised at the right
+// points for free (old variables contribute their current means), and the build's ref_file map tells which union factor was which old
+// one (file index < F_old: old reference id = file index).
+#include "gbp_handle.hpp"
+
+#include <new>
+
+namespace {
+
+// the union's factor arrays in file order: the old factors in reference order (measurement = the z rows of their slot), then the batch
+__global__ __launch_bounds__(BLOCK) void k_union_factors(Params o, const int *__restrict__ ref_cam, const int *__restrict__ ref_lmk,
+                                                         const double *__restrict__ bmeas, const int *__restrict__ bcam, const int *__restrict__ blmk,
+                                                         int n_new, double *__restrict__ meas, int *__restrict__ cam, int *__restrict__ lmk)
+{
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i < o.F) {
+        const int s = o.cadj[i];
+        meas[(size_t)i * 2] = o.lin[lin_at(s, ROW_Z)];
+        meas[(size_t)i * 2 + 1] = o.lin[lin_at(s, ROW_Z + 1)];
+        cam[i] = ref_cam[i];
+        lmk[i] = ref_lmk[i];
+    } else if (i < o.F + n_new) {
+        const int j = i - o.F;
+        meas[(size_t)i * 2] = bmeas[(size_t)j * 2];
+        meas[(size_t)i * 2 + 1] = bmeas[(size_t)j * 2 + 1];
+        cam[i] = bcam[j];
+        lmk[i] = blmk[j];
+    }
+}
+
+// the union's initial means: the old variables' current belief means (node.mu), then the batch's
+__global__ __launch_bounds__(BLOCK) void k_union_means(Params o, const double *__restrict__ bcam, const double *__restrict__ blmk, int dC, int dL,
+                                                       double *__restrict__ cam_means, double *__restrict__ lmk_means)
+{
+    const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    const size_t nc = (size_t)(o.C + dC) * 6, nl = (size_t)(o.L + dL) * 3;
+    if (i < nc) {
+        const size_t c = i / 6, k = i % 6;
+        cam_means[i] = c < (size_t)o.C ? o.cbel[c * CAMREC + CAM_MU + k] : bcam[i - (size_t)o.C * 6];
+    } else if (i < nc + nl) {
+        const size_t j = i - nc, l = j / 3, k = j % 3;
+        lmk_means[j] = l < (size_t)o.L ? o.lrec[l * LREC + LR_MU + k] : blmk[j - (size_t)o.L * 3];
+    }
+}
+
+// One lane per slot of the union: an old factor's whole state moves from its old slot (gathered) to its new one (written as the
+// tile-contiguous row pairs of gbp_kernels.hpp: 16 contiguous bytes per lane and pair, 1 KB per wave and pair).  The meta word and the
+// rank field of the state word are the new layout's (k_build_tiles wrote them); everything else is the old factor's: linearisation point,
+// measurement, clock stamp, pending / robust / damped bits, messages, adaptive variance, dense remainder.  New factors keep what the build
+// gave them (create's initialisation: iters_since_relin = 1 at the handle's clock, zero messages, sigma^2).
+__global__ __launch_bounds__(BLOCK) void k_transplant_slots(Params n, Params o, const int *__restrict__ ref_file, int *__restrict__ old_to_new)
+{
+    const int slot = blockIdx.x * BLOCK + threadIdx.x;
+    if (slot >= n.T * WTILE || (slot & 63) >= n.tiles[slot >> 6].z) return;
+    const int r = n.cpos[slot];
+    const int f = ref_file ? ref_file[r] : r;
+    if (f >= o.F) return;
+    const int os = o.cadj[f];
+    old_to_new[f] = r;
+    double2 *nl = reinterpret_cast<double2 *>(n.lin);
+    const double2 *ol = reinterpret_cast<const double2 *>(o.lin);
+#pragma unroll
+    for (int k = 0; k < LIN_ROWS / 2 - 1; ++k) nl[lin_at(slot, 2 * k) / 2] = ol[lin_at(os, 2 * k) / 2];
+    {
+        const size_t nix = lin_at(slot, ROW_Z + 1) / 2;     // z[1] | meta, state
+        double2 v = ol[lin_at(os, ROW_Z + 1) / 2];
+        const double2 mine = nl[nix];
+        const unsigned *mw = reinterpret_cast<const unsigned *>(&mine.y);
+        unsigned *w = reinterpret_cast<unsigned *>(&v.y);
+        w[0] = mw[0];
+        w[1] = (w[1] & ~(STATE_RANK_MASK << 2)) | (mw[1] & (STATE_RANK_MASK << 2));
+        nl[nix] = v;
+    }
+    double2 *nm = reinterpret_cast<double2 *>(n.msg);
+    const double2 *om = reinterpret_cast<const double2 *>(o.msg);
+#pragma unroll
+    for (int k = 0; k < MSG_ROWS / 2; ++k) nm[msg_at(slot, 2 * k) / 2] = om[msg_at(os, 2 * k) / 2];
+    if (o.avar && n.avar) n.avar[slot] = o.avar[os];
+    if (o.xtra && n.xtra) {
+#pragma unroll
+        for (int k = 0; k < XTRA_ROW; ++k) n.xtra[(size_t)slot * XTRA_ROW + k] = o.xtra[(size_t)os * XTRA_ROW + k];
+    }
+}
+
+// per-variable state of the old variables: camera records, belief views and priors; landmark mean | covariance and prior (the slot range
+// of a landmark record is the new layout's)
+__global__ __launch_bounds__(BLOCK) void k_transplant_vars(Params n, Params o)
+{
+    const int v = blockIdx.x * BLOCK + threadIdx.x;
+    if (v < o.C) {
+#pragma unroll
+        for (int k = 0; k < CAMREC; ++k) n.cbel[(size_t)v * CAMREC + k] = o.cbel[(size_t)v * CAMREC + k];
+#pragma unroll
+        for (int k = 0; k < CBEL; ++k) n.cbelief[(size_t)v * CBEL + k] = o.cbelief[(size_t)v * CBEL + k];
+#pragma unroll
+        for (int k = 0; k < 27; ++k) n.cprior[(size_t)v * 27 + k] = o.cprior[(size_t)v * 27 + k];
+    } else if (v < o.C + o.L) {
+        const size_t l = (size_t)(v - o.C);
+        double *nr = n.lrec + l * LREC;
+        const double *orr = o.lrec + l * LREC;
+#pragma unroll
+        for (int k = 0; k < LR_ROWS; ++k) nr[k] = orr[k];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) nr[LR_PRIOR + k] = orr[LR_PRIOR + k];
+    }
+}
+
+template <typename T>
+int stage(gbp_ba *h, const T *src, size_t n, bool on_device, std::vector<void *> &scratch, const T **out)
+{
+    if (on_device || !n) { *out = src; return GBP_OK; }
+    void *q = nullptr;
+    HIPCHK(hipMallocAsync(&q, n * sizeof(T), h->stream));
+    scratch.push_back(q);
+    HIPCHK(hipMemcpyAsync(q, src, n * sizeof(T), hipMemcpyHostToDevice, h->stream));
+    *out = static_cast<const T *>(q);
+    return GBP_OK;
+}
+
+template <typename T>
+int scratch_buf(gbp_ba *h, std::vector<void *> &scratch, T **out, size_t n)
+{
+    void *q = nullptr;
+    HIPCHK(hipMallocAsync(&q, std::max<size_t>(n, 1) * sizeof(T), h->stream));
+    scratch.push_back(q);
+    *out = static_cast<T *>(q);
+    return GBP_OK;
+}
+
+// the union built beside the old handle `o` into the fresh handle `n` (which owns nothing of o's)
+int extend_into(gbp_ba *o, gbp_ba *n, const gbp_ba_ext_t *e, std::vector<void *> &scratch, std::vector<int> &old_to_new)
+{
+    const Params &op = o->p;
+    const int dC = e->n_new_cams, dL = e->n_new_lmks, dF = e->n_new_factors;
+    const int C = op.C + dC, L = op.L + dL, F = op.F + dF;
+    const bool dev_in = (e->flags & GBP_FLAG_DEVICE_INPUT) != 0;
+    // what create sets from the descriptor, taken from the old handle as it is (no double -> descriptor -> double round trip)
+    n->device = o->device; n->ovr = o->ovr; n->n_cus = o->n_cus;
+    n->stream = o->stream;                                    // (not owned: the handle keeps its streams)
+    n->flags = o->staged_auto ? (o->flags & ~GBP_FLAG_NO_FUSED) : o->flags;     // the flags of create, before the sparseness rule added NO_FUSED
+    Params &p = n->p;
+    p = Params{};
+    p.F = F; p.L = L; p.C = C; p.T = 0;
+    p.K = op.K; p.sigma2 = op.sigma2; p.nstds = op.nstds; p.beta = op.beta; p.eta_damping = op.eta_damping;
+    p.num_undamped = op.num_undamped; p.min_linear = op.min_linear; p.loss = op.loss;
+    p.robustify = 0; p.local_relin = 1;
+    p.crow = op.num_undamped == 0 ? CSTAGE_ROW : CSTAGE_PLAIN;
+    p.clk = op.clk; p.clk_inc = 0;                             // new factors are stamped iters_since_relin = 1 against the handle's clock
+    p.reverse_walk = op.reverse_walk;
+
+    // 1. the union's inputs, on the device
+    const double *bcm = nullptr, *blm = nullptr, *bmeas = nullptr;
+    const int *bcam = nullptr, *blmk = nullptr;
+    CHK(stage(n, e->cam_means, (size_t)dC * 6, dev_in, scratch, &bcm)); CHK(stage(n, e->lmk_means, (size_t)dL * 3, dev_in, scratch, &blm));
+    CHK(stage(n, e->meas, (size_t)dF * 2, dev_in, scratch, &bmeas));
+    CHK(stage(n, e->cam_idx, (size_t)dF, dev_in, scratch, &bcam)); CHK(stage(n, e->lmk_idx, (size_t)dF, dev_in, scratch, &blmk));
+    double *u_meas = nullptr, *u_cm = nullptr, *u_lm = nullptr;
+    int *u_cam = nullptr, *u_lmk = nullptr;
+    CHK(scratch_buf(n, scratch, &u_meas, (size_t)F * 2)); CHK(scratch_buf(n, scratch, &u_cam, (size_t)F)); CHK(scratch_buf(n, scratch, &u_lmk, (size_t)F));
+    CHK(scratch_buf(n, scratch, &u_cm, (size_t)C * 6)); CHK(scratch_buf(n, scratch, &u_lm, (size_t)L * 3));
+    if (F) hipLaunchKernelGGL(k_union_factors, dim3(grid_for((size_t)F)), dim3(BLOCK), 0, n->stream, op, o->d_ref_cam, o->d_ref_lmk, bmeas, bcam, blmk, dF,
+                              u_meas, u_cam, u_lmk);
+    const size_t nv = (size_t)C * 6 + (size_t)L * 3;
+    if (nv) hipLaunchKernelGGL(k_union_means, dim3(grid_for(nv)), dim3(BLOCK), 0, n->stream, op, bcm, blm, dC, dL, u_cm, u_lm);
+    HIPCHK(hipGetLastError());
+
+    // 2. the union's graph by the create path (ids are checked there: out of range -> GBP_EINVAL)
+    gbp_ba_desc_t d{};
+    d.n_cams = C; d.n_lmks = L; d.n_factors = F; d.device = o->device;
+    d.cam_means = u_cm; d.lmk_means = u_lm; d.meas = u_meas; d.cam_idx = u_cam; d.lmk_idx = u_lmk;
+    d.flags = GBP_FLAG_DEVICE_INPUT;                           // (the sweep flags are n->flags)
+    const int *ref_file = nullptr;
+    CHK(build_graph(n, &d, scratch, n->n_cus, &ref_file));
+
+    // 3. a remainder switched on on demand stays on (the fresh handle allocates it exactly as the old one did)
+    if (o->lazy_xtra && op.xtra) CHK(enable_remainder(n));
+
+    // 4. the state transplant
+    int *d_o2n = nullptr;
+    CHK(scratch_buf(n, scratch, &d_o2n, (size_t)op.F));
+    const size_t S = n_slots(n);
+    if (p.T && op.F) hipLaunchKernelGGL(k_transplant_slots, dim3(grid_for(S)), dim3(BLOCK), 0, n->stream, p, op, ref_file, d_o2n);
+    if (op.C + op.L) hipLaunchKernelGGL(k_transplant_vars, dim3(grid_for((size_t)op.C + op.L)), dim3(BLOCK), 0, n->stream, p, op);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(n->d_relin_ring, o->d_relin_ring, sizeof(int) * (size_t)RELIN_RING * RELIN_LANES, hipMemcpyDeviceToDevice, n->stream));
+    n->sweep_count = o->sweep_count; n->walk_parity = o->walk_parity; n->gen_parity = o->gen_parity;
+    n->pending_possible = o->pending_possible; n->lazy_since = o->lazy_since;
+
+    // 5. priors of the new variables: the rule over their factors (all of them new), or the given scalars
+    const double wf = e->prior_weaker_factor;
+    const bool rule = wf > 0.0;
+    if (rule && ((dC && !e->cam_prior_lambda) || (dL && !e->lmk_prior_lambda))) CHK(variable_lambda_max(n));
+    if (!rule) {
+        if (dC && !e->cam_prior_lambda) HIPCHK(hipMemsetAsync(n->d_varmax + op.C, 0, sizeof(double) * (size_t)dC, n->stream));
+        if (dL && !e->lmk_prior_lambda) HIPCHK(hipMemsetAsync(n->d_varmax + C + op.L, 0, sizeof(double) * (size_t)dL, n->stream));
+    }
+    if (dC && e->cam_prior_lambda)
+        HIPCHK(hipMemcpyAsync(n->d_varmax + op.C, e->cam_prior_lambda, sizeof(double) * (size_t)dC, hipMemcpyHostToDevice, n->stream));
+    if (dL && e->lmk_prior_lambda)
+        HIPCHK(hipMemcpyAsync(n->d_varmax + C + op.L, e->lmk_prior_lambda, sizeof(double) * (size_t)dL, hipMemcpyHostToDevice, n->stream));
+    CHK(prior_scalars_range(n, op.C, op.L, e->cam_prior_lambda || !rule ? 1.0 : wf * wf, e->lmk_prior_lambda || !rule ? 1.0 : wf * wf));
+
+    // 6. update_all_beliefs over the union
+    CHK(gbp_ba_update_beliefs(n));
+    old_to_new.resize((size_t)op.F);
+    if (op.F) HIPCHK(hipMemcpyAsync(old_to_new.data(), d_o2n, sizeof(int) * (size_t)op.F, hipMemcpyDeviceToHost, n->stream));
+    HIPCHK(hipStreamSynchronize(n->stream));
+    return GBP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gbp_ba_extend(gbp_ba_t *h, const gbp_ba_ext_t *e, int32_t *old_to_new)
+{
+    ENTER(h);
+    if (!e) return fail(GBP_EINVAL, "null argument");
+    if (h->xch_fn || h->comm || h->peer.mailbox || h->peer.connected)
+        return fail(GBP_ESTATE, "a sharded handle (communicator, exchange callback or peer mailbox) cannot grow");
+    if (!h->has_beliefs) return fail(GBP_ESTATE, "the handle has no beliefs yet (gbp_ba_update_beliefs first)");
+    const int dC = e->n_new_cams, dL = e->n_new_lmks, dF = e->n_new_factors;
+    if (dC < 0 || dL < 0 || dF < 0) return fail(GBP_EINVAL, "negative size");
+    if (e->flags & ~GBP_FLAG_DEVICE_INPUT) return fail(GBP_EINVAL, "unknown flags 0x%x (only GBP_FLAG_DEVICE_INPUT)", e->flags);
+    if ((dC && !e->cam_means) || (dL && !e->lmk_means)) return fail(GBP_EINVAL, "null initial means");
+    if (dF && (!e->meas || !e->cam_idx || !e->lmk_idx)) return fail(GBP_EINVAL, "null observation arrays");
+    const Params &op = h->p;
+    if ((int64_t)op.C + dC > INT32_MAX || (int64_t)op.L + dL > INT32_MAX || (int64_t)op.F + dF > INT32_MAX) return fail(GBP_EINVAL, "sizes exceed int32");
+    if (op.C + dC >= (1 << (32 - META_LMK_BITS))) return fail(GBP_EINVAL, "more than %d cameras are not supported", (1 << (32 - META_LMK_BITS)) - 1);
+    if (!(e->flags & GBP_FLAG_DEVICE_INPUT)) {            // host ids: checked here, before anything is allocated
+        for (int i = 0; i < dF; ++i)
+            if (e->cam_idx[i] < 0 || e->cam_idx[i] >= op.C + dC || e->lmk_idx[i] < 0 || e->lmk_idx[i] >= op.L + dL)
+                return fail(GBP_EINVAL, "new observation %d references a camera outside [0,%d) or a landmark outside [0,%d)", i, op.C + dC, op.L + dL);
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    gbp_ba *n = new (std::nothrow) gbp_ba;
+    if (!n) return fail(GBP_ENOMEM, "out of host memory");
+    std::vector<void *> scratch;
+    std::vector<int> o2n;
+    int rc;
+    try {
+        rc = extend_into(h, n, e, scratch, o2n);
+    } catch (const std::bad_alloc &) {
+        rc = fail(GBP_ENOMEM, "out of host memory");
+    }
+    for (void *q : scratch) (void)hipFreeAsync(q, h->stream);
+    (void)hipStreamSynchronize(h->stream);
+    if (rc != GBP_OK) {
+        n->stream = nullptr;                                  // (the stream is the old handle's)
+        const std::string keep = gbp_last_error();            // (as gbp_ba_create does: the message outlives the clean-up)
+        gbp_ba_destroy(n);
+        return fail(rc, "%s", keep.c_str());
+    }
+    // what the handle keeps: its streams, timing settings and instrumentation buffers (the rest of it is the union's now)
+    std::swap(n->own_stream, h->own_stream);
+    std::swap(n->timing, h->timing); std::swap(n->timing_every, h->timing_every); std::swap(n->timing_tick, h->timing_tick);
+    std::swap(n->timing_now, h->timing_now); std::swap(n->ev, h->ev); std::swap(n->ev_used, h->ev_used);
+    std::swap(n->clk_used, h->clk_used); std::swap(n->clk_rate_khz, h->clk_rate_khz);
+    std::swap(n->clk_calibrated, h->clk_calibrated); std::swap(n->clk_rate_khz_measured, h->clk_rate_khz_measured);
+    std::swap(n->side_stream, h->side_stream); std::swap(n->ev_fork, h->ev_fork); std::swap(n->ev_join, h->ev_join);
+    if (h->d_clk) {
+        h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), static_cast<void *>(h->d_clk)), h->allocs.end());
+        n->allocs.push_back(h->d_clk);
+        n->d_clk = h->d_clk; h->d_clk = nullptr;
+    }
+    std::swap(*h, *n);                                        // h: the union; n: what is left of the old handle
+    h->fused.alloc_ctx = h;
+    n->stream = h->stream;                                    // (synchronised by destroy, not destroyed: own_stream went over)
+    gbp_ba_destroy(n);
+    if (old_to_new && !o2n.empty()) std::memcpy(old_to_new, o2n.data(), o2n.size() * sizeof(int32_t));
+    return GBP_OK;
+}
+
+}  // extern "C"

@@ -5,6 +5,7 @@
 //   gbp_capi_shard.hip  the landmark-sharded loop: RCCL, peer-store mailboxes, the exchange between reduce and finish
 //   gbp_capi_views.hip  state views (beliefs, messages, factors, relinearisation state), streaming means, eval_fn
 //   gbp_capi_state.hip  checkpoints (host blob, device slot)
+//   gbp_capi_extend.hip growth of a live handle (gbp_ba_extend): the union's inputs, the state transplant
 //
 // Kernels live with the unit that launches them (a __global__ defined in a header may be instantiated by one unit only: the
 // dynamic-LDS attributes of the fused sweep are set on the very function objects that are launched).
@@ -230,6 +231,10 @@ namespace gbp {
 // gbp_capi.hip
 int peer_check(gbp_ba *h, bool clear);               // a finish wave of the peer-store exchange gave up waiting: GBP_ESTATE until gbp_ba_sync has reported it
 int graph_hash(gbp_ba *h, uint64_t *out);            // digest of the factor -> (slot, camera, landmark) maps (state blobs)
+int build_graph(gbp_ba *h, const gbp_ba_desc_t *d, std::vector<void *> &scratch, int n_cus, const int **ref_file_out = nullptr);
+                                                     // the graph of a descriptor onto a handle (gbp_ba_create, gbp_ba_extend)
+int variable_lambda_max(gbp_ba *h);                  // d_varmax = max over each variable's factors of max(Lambda_f) (gbp_ba.py:27-31)
+int prior_scalars_range(gbp_ba *h, int c0, int l0, double w2_cam, double w2_lmk);   // priors from d_varmax for cameras >= c0, landmarks >= l0
 // gbp_capi_sweep.hip
 int plan_fused_sweep(gbp_ba *h, int n_cus);          // fused_plan on the handle (the kernels whose attributes it sets live in that unit)
 int fused_max_cams_of_this_build();

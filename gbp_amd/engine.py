@@ -99,6 +99,46 @@ class BAEngine:
         self._h = ct.c_void_p()
         check(self._lib.gbp_ba_create(ct.byref(self._h), ct.byref(d)))
 
+    # ---- growth (include/gbp_ba.h: gbp_ba_extend) -------------------------------------------------
+    def extend(self, cam_means, lmk_means, meas, cam_idx, lmk_idx, *, prior_weaker_factor=50.0, cam_prior_lambda=None,
+               lmk_prior_lambda=None, device_pointers=None):
+        """Append dC cameras, dL landmarks and dF factors (ids in the UNION numbering) without losing any solver state: what the reference's
+        graph is after the same appends, generate_priors_var over the new variables only (or Lambda = lambda I from the scalars) and
+        update_all_beliefs.  Returns old_to_new (int32, one entry per old factor: its id in the union's reference order).
+        device_pointers = (dC, dL, dF): the five arrays are integer DEVICE addresses (GBP_FLAG_DEVICE_INPUT)."""
+        e = _capi.Ext()
+        keep = []
+        if device_pointers is not None:
+            dC, dL, dF = (int(v) for v in device_pointers)
+            e.flags = _capi.FLAG_DEVICE_INPUT
+            e.cam_means = ct.cast(ct.c_void_p(int(cam_means)), _capi._dp)
+            e.lmk_means = ct.cast(ct.c_void_p(int(lmk_means)), _capi._dp)
+            e.meas = ct.cast(ct.c_void_p(int(meas)), _capi._dp)
+            e.cam_idx = ct.cast(ct.c_void_p(int(cam_idx)), _capi._ip)
+            e.lmk_idx = ct.cast(ct.c_void_p(int(lmk_idx)), _capi._ip)
+        else:
+            cm, lm = f64(cam_means).reshape(-1, 6), f64(lmk_means).reshape(-1, 3)
+            z, ci, li = f64(meas).reshape(-1, 2), i32(cam_idx).reshape(-1), i32(lmk_idx).reshape(-1)
+            dC, dL, dF = cm.shape[0], lm.shape[0], z.shape[0]
+            if ci.shape[0] != dF or li.shape[0] != dF:
+                raise ValueError("cam_idx / lmk_idx / meas length mismatch")
+            keep += [cm, lm, z, ci, li]
+            e.cam_means, e.lmk_means, e.meas, e.cam_idx, e.lmk_idx = dptr(cm), dptr(lm), dptr(z), iptr(ci), iptr(li)
+        e.n_new_cams, e.n_new_lmks, e.n_new_factors = dC, dL, dF
+        e.prior_weaker_factor = float(prior_weaker_factor) if prior_weaker_factor else 0.0
+        if cam_prior_lambda is not None:
+            a = f64(cam_prior_lambda, (dC,))
+            keep.append(a)
+            e.cam_prior_lambda = dptr(a)
+        if lmk_prior_lambda is not None:
+            a = f64(lmk_prior_lambda, (dL,))
+            keep.append(a)
+            e.lmk_prior_lambda = dptr(a)
+        o2n = np.empty(self.F, np.int32)
+        check(self._lib.gbp_ba_extend(self._h, ct.byref(e), iptr(o2n)))
+        self.C, self.L, self.F = self.C + dC, self.L + dL, self.F + dF
+        return o2n
+
     @classmethod
     def from_problem(cls, p, **kw):
         return cls(p.K, p.cam_means, p.lmk_means, p.meas, p.cam_idx, p.lmk_idx, **kw)

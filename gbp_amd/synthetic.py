@@ -195,6 +195,67 @@ def make_synthetic(n_cams=500, n_lmks=100_000, obs_per_lmk=10, seed=0, K=FR1DESK
                      meas=meas, cam_idx=cam_idx, lmk_idx=lmk_idx)
 
 
+@dataclasses.dataclass
+class KeyframeSplit:
+    """A problem cut into a base problem and batches for BAEngine.extend (keyframe_batches)."""
+    base: BAProblem
+    batches: list          # dicts cam_means (dC,6), lmk_means (dL,3), meas (dF,2), cam_idx / lmk_idx (dF,) in UNION numbering
+    lmk_order: np.ndarray  # (L,) original landmark id of every landmark in the split's numbering
+    deferred: int          # observations held back to a later batch than their camera's
+
+
+def keyframe_batches(problem, sizes, defer=0.0, seed=0):
+    """Cut `problem` into a base problem and batches in SLAM order.  sizes = [cameras of the base, cameras of batch 1, ...] (cameras
+    join in index order; the sum may be less than the problem's, the rest is left out).  A landmark joins with the first camera that
+    observes it (landmarks are renumbered in joining order, first appearance in file order inside a camera), and a batch carries every
+    observation of its cameras, in file order.  Ids are given in the union numbering of the graph the batch grows.
+
+    defer = q > 0: a fraction q of the observations of the cameras of every batch but the last -- never a landmark's first one -- is held
+    back and appended to the NEXT batch, after that batch's own observations: observations of old cameras arrive late (the case in which
+    extend moves old factor ids)."""
+    sizes = [int(n) for n in sizes]
+    if not sizes or min(sizes) < 0 or sum(sizes) > problem.n_cams:
+        raise ValueError("sizes must be non-negative camera counts that sum to at most the problem's cameras")
+    cam_idx, lmk_idx = np.asarray(problem.cam_idx), np.asarray(problem.lmk_idx)
+    bounds = np.cumsum([0] + sizes)
+    n_used = int(bounds[-1])
+    keep = np.flatnonzero(cam_idx < n_used)
+    order = keep[np.argsort(cam_idx[keep], kind='stable')]           # camera-major, file order inside a camera
+    first = np.full(problem.n_lmks, -1, np.int64)                    # position in `order` of each landmark's first observation
+    lm = lmk_idx[order]
+    uniq, pos = np.unique(lm, return_index=True)
+    first[uniq] = pos
+    lmk_order = uniq[np.argsort(pos, kind='stable')]                 # joining order
+    new_id = np.full(problem.n_lmks, -1, np.int64)
+    new_id[lmk_order] = np.arange(lmk_order.size)
+    batch_of_cam = np.searchsorted(bounds, np.arange(n_used), side='right') - 1
+    obs_batch = batch_of_cam[cam_idx[order]]
+    if defer > 0:
+        rng = np.random.default_rng(seed)
+        is_first = np.zeros(order.size, bool)
+        is_first[pos] = True
+        pick = (~is_first) & (obs_batch < len(sizes) - 1) & (rng.random(order.size) < defer)
+        obs_batch = obs_batch + pick
+        deferred = int(pick.sum())
+    else:
+        deferred = 0
+    lmk_batch = batch_of_cam[cam_idx[order[first[lmk_order]]]] if lmk_order.size else np.zeros(0, np.int64)
+    parts = []
+    for b in range(len(sizes)):
+        own = np.flatnonzero((obs_batch == b) & (batch_of_cam[cam_idx[order]] == b))
+        late = np.flatnonzero((obs_batch == b) & (batch_of_cam[cam_idx[order]] < b))
+        sel = order[np.concatenate([own, late])]
+        lsel = lmk_order[lmk_batch == b]
+        parts.append(dict(cam_means=np.asarray(problem.cam_means[bounds[b]:bounds[b + 1]], np.float64).copy(),
+                          lmk_means=np.asarray(problem.lmk_means[lsel], np.float64).copy(),
+                          meas=np.asarray(problem.meas[sel], np.float64).copy(),
+                          cam_idx=cam_idx[sel].astype(np.int32), lmk_idx=new_id[lmk_idx[sel]].astype(np.int32)))
+    b0 = parts[0]
+    base = BAProblem(K=np.asarray(problem.K, np.float64).copy(), cam_means=b0['cam_means'], lmk_means=b0['lmk_means'], meas=b0['meas'],
+                     cam_idx=b0['cam_idx'], lmk_idx=b0['lmk_idx'])
+    return KeyframeSplit(base=base, batches=parts[1:], lmk_order=lmk_order, deferred=deferred)
+
+
 def write_bal(problem: BAProblem, path, header="synthetic"):
     """Write `problem` in the text layout the reference parses (utils/read_balfile.py:4-37)."""
     with open(path, 'w') as f:

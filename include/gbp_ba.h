@@ -80,6 +80,42 @@ void gbp_ba_destroy(gbp_ba_t *h);
 int gbp_ba_set_stream(gbp_ba_t *h, void *hip_stream);     /* NULL = the handle's own stream */
 int gbp_ba_sync(gbp_ba_t *h);
 
+/* growth: append cameras, landmarks and factors to a live handle (a SLAM keyframe) without losing any solver state.  The reference
+ * grows its graph by list appends (gbp_ba.py:114-141); after gbp_ba_extend the handle is exactly what the reference's graph is after
+ *   1. cameras C..C+dC-1 and landmarks L..L+dL-1 are appended;
+ *   2. the union's factor order is the reference's own (gbp_ba.py:128-130): camera-major, inside a camera the old factors first, then
+ *      the new ones in batch order (what create_ba_graph gives on the old file with the batch appended).  When every new factor
+ *      belongs to a new camera (a keyframe) old factor ids do not change; otherwise old_to_new reports how they moved:
+ *      new = old + #(new factors whose camera < cam(old)).  Inside a landmark factors follow the union order;
+ *   3. each new factor is linearised at concat(cam.mu, lmk.mu) -- the current belief mean of an old variable, the given initial mean
+ *      of a new one -- with zero messages, iters_since_relin = 1, eta_damping = 0, not robust, adaptive variance = gauss_noise_std^2
+ *      (gbp.py:201-249);
+ *   4. every old factor keeps its linearisation point, measurement, both messages, adaptive variance, robust and damped flags,
+ *      relinearisation age (against the same clock), the pending mark of a stage-wise relinearise and its dense message remainder
+ *      when the handle carries one; every old variable keeps its prior;
+ *   5. new variables get priors: by generate_priors_var's rule (gbp_ba.py:20-34) over the NEW variables only when
+ *      prior_weaker_factor > 0 (else Lambda = 0), or Lambda = lambda I, eta = lambda mu from the optional scalars;
+ *   6. update_all_beliefs runs over the union (new factors carry zero messages: old beliefs are unchanged up to summation order);
+ *   7. the handle keeps its stream, its environment overrides (read at create, not again), its create flags, timing settings,
+ *      relinearisation clock, walk parity, sweep count and relinearisation-count ring.  The sweep's plan (fused / camera windows /
+ *      general sweep, tiles, packing) is chosen for the union exactly as gbp_ba_create would choose it;
+ *   8. dropped: the device snapshot slot (gbp_ba_restore_snapshot then returns GBP_ESTATE) and the streaming-means mirrors.
+ * Errors leave the handle untouched (the union is built beside it and swapped in at the end): GBP_ESTATE for a handle with a
+ * communicator, an exchange callback or a peer mailbox (sharded growth is not supported) or without beliefs yet; GBP_EINVAL for ids
+ * out of range, negative counts, NULL arrays with a non-zero count or sizes gbp_ba_create would reject; GBP_ENOMEM when the union
+ * does not fit -- peak device memory is the old handle's plus the union's.  old_to_new (NULL to skip) receives F_old entries. */
+typedef struct gbp_ba_ext {
+    int32_t n_new_cams, n_new_lmks, n_new_factors;   /* dC, dL, dF (any may be 0) */
+    int32_t flags;                                   /* GBP_FLAG_DEVICE_INPUT allowed (the five arrays below are then device pointers) */
+    const double *cam_means;                         /* dC*6 initial means of the new cameras */
+    const double *lmk_means;                         /* dL*3 */
+    const double *meas;                              /* dF*2 */
+    const int32_t *cam_idx, *lmk_idx;                /* dF, ids in the UNION numbering: cameras 0..C+dC-1, landmarks 0..L+dL-1 */
+    double prior_weaker_factor;                      /* > 0: generate_priors_var (gbp_ba.py:20-34) on the NEW variables only */
+    const double *cam_prior_lambda, *lmk_prior_lambda;   /* optional host dC / dL scalars: Lambda = l I, eta = l mu (override the rule) */
+} gbp_ba_ext_t;
+int gbp_ba_extend(gbp_ba_t *h, const gbp_ba_ext_t *ext, int32_t *old_to_new);
+
 /* priors */
 int gbp_ba_generate_priors(gbp_ba_t *h, double weaker_factor);          /* BAFactorGraph.generate_priors_var gbp_ba.py:20-34 */
 int gbp_ba_factor_lambda_max(gbp_ba_t *h, double *cam_max, double *lmk_max);  /* the max_f max(Lambda_f) half of it (sharded set-up) */
