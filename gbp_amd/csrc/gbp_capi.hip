@@ -325,7 +325,6 @@ int gbp::build_graph(gbp_ba *h, const gbp_ba_desc_t *d, std::vector<void *> &scr
         h->fused.alloc = arena_take; h->fused.alloc_ctx = h;
         int rc = plan_fused_sweep(h, n_cus);
         if (rc < 0) return fail(GBP_EHIP, "building the fused sweep plan failed (%d)", rc);
-        if (h->fused.enabled) h->dominant = "k_sweep_fused";
     }
     HIPCHK(hipStreamSynchronize(h->stream));                // the staged inputs are released by the caller
     clk.mark("fused plan");
@@ -583,7 +582,7 @@ int gbp_ba_plan_info(gbp_ba_t *h, int32_t *out, int32_t n)
 int gbp_ba_info(gbp_ba_t *h, int32_t *fused_path, int32_t *n_tiles, int32_t *n_blocks)
 {
     if (!h) return fail(GBP_EINVAL, "null handle");
-    if (fused_path) *fused_path = h->fused.enabled ? h->fused.n_groups : 0;
+    if (fused_path) *fused_path = h->fused.enabled ? 1 : 0;
     if (n_tiles) *n_tiles = h->p.T;
     if (n_blocks) *n_blocks = h->fused.n_blocks;
     return GBP_OK;

@@ -260,7 +260,7 @@ int gbp_ba_extend(gbp_ba_t *h, const gbp_ba_ext_t *e, int32_t *old_to_new)
     // what the handle keeps: its streams, timing settings and instrumentation buffers (the rest of it is the union's now)
     std::swap(n->own_stream, h->own_stream);
     std::swap(n->timing, h->timing); std::swap(n->timing_every, h->timing_every); std::swap(n->timing_tick, h->timing_tick);
-    std::swap(n->timing_now, h->timing_now); std::swap(n->ev, h->ev); std::swap(n->ev_used, h->ev_used);
+    std::swap(n->ev, h->ev); std::swap(n->ev_used, h->ev_used);
     std::swap(n->clk_used, h->clk_used); std::swap(n->clk_rate_khz, h->clk_rate_khz);
     std::swap(n->clk_calibrated, h->clk_calibrated); std::swap(n->clk_rate_khz_measured, h->clk_rate_khz_measured);
     std::swap(n->side_stream, h->side_stream); std::swap(n->ev_fork, h->ev_fork); std::swap(n->ev_join, h->ev_join);

@@ -240,7 +240,7 @@ int gbp_ba_peer_selftest(gbp_ba_t *h, int32_t timeout_ms)
 // the reduce launch itself, exactly like gbp_ba_iterate.
 // one sharded sweep under the peer-store exchange: no collective, no host synchronisation -- the wave that finishes a camera's partial
 // sums stores the row into every rank's mailbox and raises its tag; whoever finishes the camera waits for the n_ranks tags of its row
-static int sharded_step_peer(gbp_ba *h, int with_messages, int robustify, int local_relin)
+static int sharded_step_peer(gbp_ba *h, const SweepStep &step)
 {
     gbp_ba::Peer &pe = h->peer;
     const int n = pe.n_ranks, half = (int)(++pe.seq & 1ull);
@@ -249,37 +249,29 @@ static int sharded_step_peer(gbp_ba *h, int with_messages, int robustify, int lo
     po.stale = peer_data(h, pe.mailbox, n, half ^ 1, 0);      // what the previous exchange delivered here: read then, emptied by this push
     for (int r = 0; r < n; ++r) po.dst[r] = peer_data(h, pe.base[r], n, half, pe.rank);
     PeerWait w{peer_data(h, pe.mailbox, n, half, 0), pe.seq, pe.timeout_ticks, pe.d_ctl + 1, nullptr};
-    const bool merged = merged_exchange(h->xch_fn != nullptr, with_messages, h->ovr);      // (fused: k_cam_reduce_xchg; general: k_cam_staged_xchg)
-    bool finished = false;
+    const bool merged = merged_exchange(h->xch_fn != nullptr, step.messages, h->ovr);      // (fused: k_cam_reduce_xchg; general: k_cam_staged_xchg)
     // The beliefs of the landmarks that span tiles (k_lmk_finish_parts) go out on THIS stream, as a short launch between the sweep
     // kernel and the reduce (1.3 us, EXPERIMENTS.md round 5).  Round 5 forked them onto a side stream "beside the exchange" -- but the
     // fork event was recorded behind the merged reduce -> push -> wait -> finish launch, so they ran strictly after it, plus two event
     // hops.  Here the exchange IS that one launch: there is nothing to run beside.
-    CHK(sweep_begin(h, with_messages, robustify, local_relin, h->d_send, 0, &finished, false, &po, merged ? &w : nullptr));
-    if (!finished) {
-        if (h->xch_fn) {                                     // rendezvous hook (logical ranks on ONE device: tests)
-            int rc = h->xch_fn(h->xch_ctx, nullptr, nullptr, 0, h->stream);
-            if (rc != GBP_OK) return rc < 0 ? rc : fail(GBP_EHIP, "the rendezvous function returned %d", rc);
-        }
-        CHK(launch_cam_finish(h, nullptr, n, 0, &w));
+    if (merged) return run_sweep(h, SweepCall::peer_merged(step, h->d_send, &po, &w));
+    CHK(run_sweep(h, SweepCall::peer_push(step, h->d_send, &po)));
+    if (h->xch_fn) {                                         // rendezvous hook (logical ranks on ONE device: tests)
+        int rc = h->xch_fn(h->xch_ctx, nullptr, nullptr, 0, h->stream);
+        if (rc != GBP_OK) return rc < 0 ? rc : fail(GBP_EHIP, "the rendezvous function returned %d", rc);
     }
-    return GBP_OK;
+    return launch_cam_finish(h, nullptr, n, 0, &w);          // the waiting finish
 }
 
-static int sharded_step(gbp_ba *h, int with_messages, int robustify, int local_relin)
+static int sharded_step(gbp_ba *h, const SweepStep &step)
 {
-    if (h->peer.connected) return sharded_step_peer(h, with_messages, robustify, local_relin);
+    if (h->peer.connected) return sharded_step_peer(h, step);
     const bool exchange = h->xch_ranks > 1 || ((h->xch_flags & GBP_XCH_ALWAYS) && h->xch_fn);
-    if (!exchange) {
-        bool finished = false;
-        CHK(sweep_begin(h, with_messages, robustify, local_relin, h->d_partial, 1, &finished));
-        if (!finished) CHK(launch_cam_finish(h, h->d_partial, 1, 0));
-        return GBP_OK;
-    }
+    if (!exchange) return run_sweep(h, SweepCall::finish(step, h->d_partial));
     // landmarks that span tiles: their beliefs need nothing from the exchange.  The side stream picks them up behind the reduce launch
     // (the fork event follows it) and runs them while the exchange function -- an RCCL all-gather, a caller's MPI -- owns this stream.
-    const bool big = with_messages && h->p.parts != nullptr;
-    CHK(sweep_begin(h, with_messages, robustify, local_relin, h->d_send, 0, nullptr, big));
+    const bool big = step.messages && h->p.parts != nullptr;
+    CHK(run_sweep(h, SweepCall::partials(step, h->d_send, big)));
     if (big) {
         if (!h->side_stream) {
             HIPCHK(hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking));
@@ -293,7 +285,7 @@ static int sharded_step(gbp_ba *h, int with_messages, int robustify, int local_r
     }
     int rc = h->xch_fn(h->xch_ctx, h->d_send, h->d_recv, (uint64_t)h->p.C * 27, h->stream);
     if (rc != GBP_OK) return rc < 0 ? rc : fail(GBP_EHIP, "the exchange function returned %d", rc);
-    CHK(launch_cam_finish(h, h->d_recv, h->xch_ranks, (size_t)h->p.C * 27));
+    CHK(launch_cam_finish(h, h->d_recv, h->xch_ranks, (size_t)h->p.C * 27, nullptr));
     if (big) HIPCHK(hipStreamWaitEvent(h->stream, h->ev_join, 0));
     return GBP_OK;
 }
@@ -304,12 +296,8 @@ int gbp_ba_iterate_sharded(gbp_ba_t *h, int32_t n_iters, int32_t robustify, int3
     h->resid_ok = false;
     if (n_iters < 0) return fail(GBP_EINVAL, "n_iters < 0");
     if (!h->d_send) return fail(GBP_ESTATE, "no exchange set (gbp_ba_comm_init_rccl / gbp_ba_set_exchange / gbp_ba_peer_connect)");
-    for (int it = 0; it < n_iters; ++it) {
-        CHK(remainder_guard(h, local_relin, 0));
-        CHK(sharded_step(h, 1, robustify, local_relin));
-        h->pending_possible = false;
-        CHK(remainder_release(h));
-    }
+    const SweepStep step{true, robustify, local_relin};
+    for (int it = 0; it < n_iters; ++it) CHK(guarded_sweep(h, local_relin, [&] { return sharded_step(h, step); }));
     h->has_beliefs = true;
     return GBP_OK;
 }
@@ -319,7 +307,7 @@ int gbp_ba_update_beliefs_sharded(gbp_ba_t *h)
     ENTER(h);
     h->resid_ok = false;
     if (!h->d_send) return fail(GBP_ESTATE, "no exchange set (gbp_ba_comm_init_rccl / gbp_ba_set_exchange)");
-    CHK(sharded_step(h, 0, 0, 0));
+    CHK(sharded_step(h, {false, 0, 0}));
     h->has_beliefs = true;
     return GBP_OK;
 }

@@ -14,55 +14,62 @@ int gbp::fused_max_cams_of_this_build() { return fused_max_cams(); }
 
 // ------------------------------------------------------------------------------ launches --
 
-static bool timing_sample(gbp_ba *h)
+// HIP events around the dominant kernel of every timing_every-th sweep while gbp_ba_set_kernel_timing is on (pairs in h->ev)
+template <typename Launch>
+static int timed(gbp_ba *h, Launch &&launch)
 {
-    if (!h->timing) return false;
-    const bool now = (h->timing_tick % h->timing_every) == 0;
-    h->timing_tick++;
-    return now;
-}
-
-static int time_begin(gbp_ba *h)
-{
-    h->timing_now = timing_sample(h);
-    if (!h->timing_now) return GBP_OK;
-    if (h->ev_used + 2 > h->ev.size()) {
-        for (int i = 0; i < 2; ++i) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); h->ev.push_back(e); }
+    const bool now = h->timing && (h->timing_tick++ % h->timing_every) == 0;
+    if (now) {
+        if (h->ev_used + 2 > h->ev.size())
+            for (int i = 0; i < 2; ++i) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); h->ev.push_back(e); }
+        HIPCHK(hipEventRecord(h->ev[h->ev_used], h->stream));
     }
-    HIPCHK(hipEventRecord(h->ev[h->ev_used], h->stream));
-    return GBP_OK;
+    const int rc = launch();
+    if (now) {
+        HIPCHK(hipEventRecord(h->ev[h->ev_used + 1], h->stream));
+        h->ev_used += 2;
+    }
+    return rc;
 }
 
-static int time_end(gbp_ba *h)
+// this sweep's slot of the relinearisation-count ring; half of the ring is cleared whenever the sweep index enters it
+static int relin_slot_advance(gbp_ba *h)
 {
-    if (!h->timing_now) return GBP_OK;
-    HIPCHK(hipEventRecord(h->ev[h->ev_used + 1], h->stream));
-    h->ev_used += 2;
+    const int slot = (int)(h->sweep_count % RELIN_RING);
+    if (slot % (RELIN_RING / 2) == 0)
+        HIPCHK(hipMemsetAsync(h->d_relin_ring + (size_t)slot * RELIN_LANES, 0, sizeof(int) * (RELIN_RING / 2) * RELIN_LANES, h->stream));
+    h->p.relin_slot = h->d_relin_ring + (size_t)slot * RELIN_LANES;
+    h->sweep_count++;
     return GBP_OK;
 }
 
-static int launch_factor_stage(gbp_ba *h, int robustify, int local_relin)
+// the kernel templates' instantiations by loss (GBP_LOSS_*: None, Huber, else Constant) and by the staged reduce's block (cam_block)
+static int loss_class(int loss) { return loss == GBP_LOSS_NONE ? 0 : loss == GBP_LOSS_HUBER ? 1 : 2; }
+using FactorTileKernel = void (*)(Params);
+static constexpr FactorTileKernel FACTOR_TILE[2][3] = {{k_factor_tile<0, true>, k_factor_tile<1, true>, k_factor_tile<2, true>},       // [0: with the dense remainder]
+                                                       {k_factor_tile<0, false>, k_factor_tile<1, false>, k_factor_tile<2, false>}};
+static_assert(BLOCK == 256, "cam_block's widest choice is the BLOCK variant");
+static int cam_class(int cam_block) { return cam_block == 64 ? 0 : cam_block == 128 ? 1 : 2; }
+static constexpr int CAM_THREADS[3] = {64, 128, BLOCK};
+using CamXchgKernel = void (*)(Params, double *, PeerOut, PeerWait);
+using CamPartialKernel = void (*)(Params, double *, int);
+static constexpr CamXchgKernel CAM_STAGED_XCHG[3] = {k_cam_staged_xchg<64>, k_cam_staged_xchg<128>, k_cam_staged_xchg<BLOCK>};
+static constexpr CamPartialKernel CAM_PARTIAL_STAGED[3] = {k_cam_partial_staged<64>, k_cam_partial_staged<128>, k_cam_partial_staged<BLOCK>};
+
+static Params params_for(const gbp_ba *h, const SweepStep &s)
 {
     Params p = h->p;
-    p.robustify = robustify; p.local_relin = local_relin;
+    p.robustify = s.robustify; p.local_relin = s.local_relin;
+    return p;
+}
+
+static int launch_factor_stage(gbp_ba *h, const SweepStep &s)
+{
+    const Params p = params_for(h, s);
     if (!p.T) return GBP_OK;
     const int nb = (p.T + BLOCK / 64 - 1) / (BLOCK / 64);
     h->cstage_x0_ok = false;                                // (this kernel's rows may be the wide ones: the next staged sweep writes whole rows)
-    CHK(time_begin(h));
-    if (p.xtra) {
-        switch (p.loss) {
-        case GBP_LOSS_NONE: hipLaunchKernelGGL((k_factor_tile<0, true>), dim3(nb), dim3(BLOCK), 0, h->stream, p); break;
-        case GBP_LOSS_HUBER: hipLaunchKernelGGL((k_factor_tile<1, true>), dim3(nb), dim3(BLOCK), 0, h->stream, p); break;
-        default: hipLaunchKernelGGL((k_factor_tile<2, true>), dim3(nb), dim3(BLOCK), 0, h->stream, p); break;
-        }
-    } else {
-        switch (p.loss) {
-        case GBP_LOSS_NONE: hipLaunchKernelGGL((k_factor_tile<0, false>), dim3(nb), dim3(BLOCK), 0, h->stream, p); break;
-        case GBP_LOSS_HUBER: hipLaunchKernelGGL((k_factor_tile<1, false>), dim3(nb), dim3(BLOCK), 0, h->stream, p); break;
-        default: hipLaunchKernelGGL((k_factor_tile<2, false>), dim3(nb), dim3(BLOCK), 0, h->stream, p); break;
-        }
-    }
-    CHK(time_end(h));
+    CHK(timed(h, [&] { hipLaunchKernelGGL(FACTOR_TILE[p.xtra ? 0 : 1][loss_class(p.loss)], dim3(nb), dim3(BLOCK), 0, h->stream, p); return GBP_OK; }));
     HIPCHK(hipGetLastError());
     return GBP_OK;
 }
@@ -123,96 +130,70 @@ static int launch_peer_push(gbp_ba *h, const double *partial, const PeerOut &pee
     return GBP_OK;
 }
 
-// defer_big: leave the beliefs of the landmarks that span tiles (k_lmk_finish_parts) to the caller, who runs them beside the
-// camera exchange (launch_finish_parts)
-int gbp::sweep_begin(gbp_ba *h, int with_messages, int robustify, int local_relin, double *partial, int finish, bool *finished, bool defer_big,
-                     const PeerOut *peer, const PeerWait *merged)
+// the general sweep's factor kernel: messages + the tiles' landmark beliefs + camera messages staged camera-major
+static int launch_general_sweep(gbp_ba *h, const SweepStep &s, const SweepLaunch &at)
 {
-    if (finished) *finished = false;
-    h->clk_cur = (h->timing && h->d_clk && h->clk_used < CLK_RING) ? h->d_clk + 6 * (size_t)h->clk_used++ : nullptr;
-    if (with_messages) {
-        clock_tick(h, local_relin != 0);
-        const int slot = (int)(h->sweep_count % RELIN_RING);
-        if (slot % (RELIN_RING / 2) == 0)
-            HIPCHK(hipMemsetAsync(h->d_relin_ring + (size_t)slot * RELIN_LANES, 0, sizeof(int) * (RELIN_RING / 2) * RELIN_LANES, h->stream));
-        h->p.relin_slot = h->d_relin_ring + (size_t)slot * RELIN_LANES;
-        h->sweep_count++;
-    }
-    if (with_messages && h->fused.enabled) {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (timing_sample(h)) {
-            if (h->ev_used + 2 > h->ev.size())
-                for (int i = 0; i < 2; ++i) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); h->ev.push_back(e); }
-            e0 = h->ev[h->ev_used]; e1 = h->ev[h->ev_used + 1];
-            h->ev_used += 2;
-        }
-        // Every other sweep walks each workgroup's tile range backwards: what the last sweep touched last is touched first, so
-        // whatever part of the state the Infinity Cache still holds is used before it is evicted.  With arena_reserve this removed
-        // the slow mode of the 1M-factor graph (12 of 12 fresh processes at 11.6-12.1k sweeps/s; 7 of 12 at 10.0-10.7k without both).
-        const int reverse = (int)(h->walk_parity & 1u);
-        h->walk_parity ^= 1u;
-        h->cstage_x0_ok = false;                            // (a fused sweep moves linearisation points without staging them)
-        int rc = fused_launch(h->fused, h->p, h->ovr, robustify, local_relin, partial, h->stream, finish, e0, e1, defer_big, reverse, peer, h->clk_cur, merged);
-        if (merged && peer && finished) *finished = true;
-        if (rc != 0) return fail(GBP_EHIP, "fused sweep launch failed: %s", hipGetErrorString((hipError_t)rc));
-        if (finished && !(merged && peer)) *finished = finish != 0;
-        return GBP_OK;
-    }
-    if (with_messages) {
-        // tile sweep: messages + the tiles' landmark beliefs + camera messages staged camera-major.  Every other sweep backwards,
-        // like the fused sweep (what the memory-side cache still holds is used first; the results do not depend on the order)
-        h->p.reverse_walk = (int)(h->gen_parity & 1u);
-        h->gen_parity ^= 1u;
-        CHK(ensure_staging(h));
-        if (h->p.xtra) {       // the dense remainder rides in k_factor_tile (one wave per tile)
-            h->dominant = "k_factor_tile";
-            h->cstage_x0_ok = false;                        // (its rows may be the wide ones: the next staged sweep writes whole rows)
-            CHK(launch_factor_stage(h, robustify, local_relin));
-        } else {                                             // the persistent loop, staging instead of a camera table
-            h->dominant = "k_sweep_staged";
-            CHK(time_begin(h));
-            const int rc = staged_launch(h->p, robustify, local_relin, h->n_cus, h->p.reverse_walk, h->stream, nullptr, h->cstage_x0_ok ? 0 : 1, &h->staged_attr_set);
-            h->cstage_x0_ok = true;
-            CHK(time_end(h));
-            if (rc != 0) return fail(GBP_EHIP, "general sweep launch failed: %s", hipGetErrorString((hipError_t)rc));
-        }
-        if (!defer_big) CHK(launch_finish_parts(h, h->stream));
-        if (h->p.C) {
-            const int cam_block = gbp::cam_block(h->p.F, h->p.C, h->ovr);
-            static_assert(BLOCK == 256, "cam_block's widest choice is the BLOCK variant");
-            if (merged && peer) {
-                // peer-store exchange: sum -> push -> wait -> finish in this one launch; the grid must be resident at once (its workgroups
-                // wait for other ranks' workgroups), so never more workgroups than the occupancy query admits on this device
-                if (!h->staged_xchg_blocks[cam_block >> 7]) {
-                    int per_cu = 0;
-                    const void *fn = cam_block == 64 ? reinterpret_cast<const void *>(&k_cam_staged_xchg<64>)
-                                   : cam_block == 128 ? reinterpret_cast<const void *>(&k_cam_staged_xchg<128>) : reinterpret_cast<const void *>(&k_cam_staged_xchg<BLOCK>);
-                    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, cam_block, 0));
-                    if (per_cu < 1 || h->n_cus < 1) return fail(GBP_EHIP, "occupancy query of the staged exchange kernel failed");
-                    h->staged_xchg_blocks[cam_block >> 7] = xchg_blocks(per_cu * h->n_cus, INT32_MAX, h->ovr);
-                }
-                const dim3 grid(std::min(h->p.C, h->staged_xchg_blocks[cam_block >> 7]));
-                PeerWait w = *merged;
-                w.clk = h->clk_cur ? h->clk_cur + 2 : nullptr;
-                if (cam_block == 64) hipLaunchKernelGGL(k_cam_staged_xchg<64>, grid, dim3(64), 0, h->stream, h->p, partial, *peer, w);
-                else if (cam_block == 128) hipLaunchKernelGGL(k_cam_staged_xchg<128>, grid, dim3(128), 0, h->stream, h->p, partial, *peer, w);
-                else hipLaunchKernelGGL(k_cam_staged_xchg<BLOCK>, grid, dim3(BLOCK), 0, h->stream, h->p, partial, *peer, w);
-                HIPCHK(hipGetLastError());
-                if (finished) *finished = true;
-                return GBP_OK;
-            }
-            if (cam_block == 64) hipLaunchKernelGGL(k_cam_partial_staged<64>, dim3(h->p.C), dim3(64), 0, h->stream, h->p, partial, finish);
-            else if (cam_block == 128) hipLaunchKernelGGL(k_cam_partial_staged<128>, dim3(h->p.C), dim3(128), 0, h->stream, h->p, partial, finish);
-            else hipLaunchKernelGGL(k_cam_partial_staged<BLOCK>, dim3(h->p.C), dim3(BLOCK), 0, h->stream, h->p, partial, finish);
-        }
+    h->p.reverse_walk = at.reverse;
+    CHK(ensure_staging(h));
+    if (h->p.xtra) return launch_factor_stage(h, s);        // the dense remainder rides in k_factor_tile (one wave per tile)
+    const Params p = params_for(h, s);                       // the persistent loop, staging instead of a camera table
+    const int rc = timed(h, [&] { return staged_launch(p, at, h->cstage_x0_ok ? 0 : 1, &h->staged_attr_set); });
+    h->cstage_x0_ok = true;
+    if (rc > 0) return fail(GBP_EHIP, "general sweep launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return rc;
+}
+
+// the camera messages a general sweep staged camera-major -> the camera sums, left where c.sink says
+static int staged_cameras(gbp_ba *h, const SweepCall &c, const SweepLaunch &at)
+{
+    if (!h->p.C) return GBP_OK;
+    const int cls = cam_class(gbp::cam_block(h->p.F, h->p.C, h->ovr));
+    const dim3 block(CAM_THREADS[cls]);
+    if (c.sink == CamSink::PeerMerged) {                    // sum -> push -> wait -> finish in this one launch (peer-store exchange)
+        const int xb = resident_blocks(&h->staged_xchg_blocks[cls], reinterpret_cast<const void *>(CAM_STAGED_XCHG[cls]), CAM_THREADS[cls], INT32_MAX, at);
+        if (!xb) return fail(GBP_EHIP, "occupancy query of the staged exchange kernel failed");
+        PeerWait w = *c.wait;
+        w.clk = h->clk_cur ? h->clk_cur + 2 : nullptr;
+        hipLaunchKernelGGL(CAM_STAGED_XCHG[cls], dim3(std::min(h->p.C, xb)), block, 0, h->stream, h->p, c.partial, *c.peer, w);
         HIPCHK(hipGetLastError());
-        if (peer) CHK(launch_peer_push(h, partial, *peer));
-        if (finished) *finished = finish != 0 && h->p.C > 0;
         return GBP_OK;
     }
-    CHK(launch_lmk_beliefs(h));                 // update_all_beliefs: from the stored messages
-    CHK(launch_cam_partial(h, partial));
-    if (peer) CHK(launch_peer_push(h, partial, *peer));
+    hipLaunchKernelGGL(CAM_PARTIAL_STAGED[cls], dim3(h->p.C), block, 0, h->stream, h->p, c.partial, c.sink == CamSink::Finish ? 1 : 0);
+    HIPCHK(hipGetLastError());
+    return c.sink == CamSink::PeerPush ? launch_peer_push(h, c.partial, *c.peer) : GBP_OK;
+}
+
+int gbp::run_sweep(gbp_ba *h, const SweepCall &c)
+{
+    h->clk_cur = (h->timing && h->d_clk && h->clk_used < CLK_RING) ? h->d_clk + 6 * (size_t)h->clk_used++ : nullptr;
+    if (!c.step.messages) {                                  // update_all_beliefs: from the stored messages
+        CHK(launch_lmk_beliefs(h));
+        CHK(launch_cam_partial(h, c.partial));
+        if (c.sink == CamSink::PeerPush || c.sink == CamSink::PeerMerged) CHK(launch_peer_push(h, c.partial, *c.peer));
+        if (c.sink == CamSink::Finish) return launch_cam_finish(h, c.partial, 1, 0, nullptr);
+        return c.sink == CamSink::PeerMerged ? launch_cam_finish(h, nullptr, c.peer->n, 0, c.wait) : GBP_OK;
+    }
+    clock_tick(h, c.step.local_relin != 0);
+    CHK(relin_slot_advance(h));
+    // Every other sweep walks each workgroup's tile range backwards: what the last sweep touched last is touched first, so
+    // whatever part of the state the Infinity Cache still holds is used before it is evicted.  With arena_reserve this removed
+    // the slow mode of the 1M-factor graph (12 of 12 fresh processes at 11.6-12.1k sweeps/s; 7 of 12 at 10.0-10.7k without both).
+    // (The fused sweep's parity is part of the state, gbp_handle.hpp; the general sweep's sums do not depend on the order.)
+    const bool fused = h->fused.enabled;
+    uint32_t &parity = fused ? h->walk_parity : h->gen_parity;
+    const SweepLaunch at{h->stream, (int)(parity & 1u), fused ? h->clk_cur : nullptr, h->n_cus, &h->ovr};
+    parity ^= 1u;
+    if (!fused) {
+        CHK(launch_general_sweep(h, c.step, at));
+        if (!c.defer_parts) CHK(launch_finish_parts(h, h->stream));
+        return staged_cameras(h, c, at);
+    }
+    h->cstage_x0_ok = false;                                // (a fused sweep moves linearisation points without staging them)
+    const Params p = params_for(h, c.step);
+    CHK(timed(h, [&] { fused_launch(h->fused, p, at); return GBP_OK; }));
+    if (!c.defer_parts) CHK(launch_finish_parts(h, h->stream));
+    const int rc = fused_cameras(h->fused, p, c, at);
+    if (rc != 0) return fail(GBP_EHIP, "fused sweep launch failed: %s", hipGetErrorString((hipError_t)rc));
     return GBP_OK;
 }
 
@@ -249,7 +230,6 @@ int gbp::enable_remainder(gbp_ba *h)
     h->lazy_xtra = true; h->lazy_since = 0;
     h->fused_suspended = h->fused.enabled;
     h->fused.enabled = false;
-    h->dominant = "k_factor_tile";
     return GBP_OK;
 }
 
@@ -278,22 +258,18 @@ int gbp::remainder_release(gbp_ba *h)
     int c = 0;
     HIPCHK(hipMemcpyAsync(&c, h->d_count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (c) return GBP_OK;
-    h->p.xtra = nullptr;                                     // (the buffer stays for the next time)
-    h->p.crow = CSTAGE_PLAIN;                                // the staged rows are 16 doubles wide again (the buffer keeps its size)
-    h->lazy_xtra = false;
-    if (h->fused_suspended) { h->fused.enabled = true; h->dominant = "k_sweep_fused"; }
-    return GBP_OK;
+    return c ? GBP_OK : remainder_drop(h);
 }
 
-// a handle whose remainder was switched on on demand goes back to the state "no remainder" (a checkpoint without one is restored)
+// a handle whose remainder was switched on on demand goes back to the state "no remainder" (nothing is left of it, or a checkpoint
+// without one is restored) and to the fused sweep if it ran one
 int gbp::remainder_drop(gbp_ba *h)
 {
     if (!h->lazy_xtra || !h->p.xtra) return GBP_OK;
-    h->p.xtra = nullptr;
-    h->p.crow = CSTAGE_PLAIN;
+    h->p.xtra = nullptr;                                     // (the buffer stays for the next time)
+    h->p.crow = CSTAGE_PLAIN;                                // the staged rows are 16 doubles wide again (the buffer keeps its size)
     h->lazy_xtra = false;
-    if (h->fused_suspended) { h->fused.enabled = true; h->dominant = "k_sweep_fused"; }
+    if (h->fused_suspended) h->fused.enabled = true;
     return GBP_OK;
 }
 
@@ -303,8 +279,7 @@ int gbp_ba_update_beliefs(gbp_ba_t *h)
 {
     ENTER(h);
     h->resid_ok = false;
-    CHK(sweep_begin(h, 0, 0, 0, h->d_partial));
-    CHK(launch_cam_finish(h, h->d_partial, 1, 0));
+    CHK(run_sweep(h, SweepCall::finish({false, 0, 0}, h->d_partial)));
     h->has_beliefs = true;
     return GBP_OK;
 }
@@ -314,14 +289,8 @@ int gbp_ba_iterate(gbp_ba_t *h, int32_t n_iters, int32_t robustify, int32_t loca
     ENTER(h);
     h->resid_ok = false;
     if (n_iters < 0) return fail(GBP_EINVAL, "n_iters < 0");
-    for (int it = 0; it < n_iters; ++it) {
-        CHK(remainder_guard(h, local_relin, 0));
-        bool finished = false;
-        CHK(sweep_begin(h, 1, robustify, local_relin, h->d_partial, 1, &finished));
-        if (!finished) CHK(launch_cam_finish(h, h->d_partial, 1, 0));
-        h->pending_possible = false;                         // every pending relinearisation has been applied
-        CHK(remainder_release(h));
-    }
+    const SweepCall call = SweepCall::finish({true, robustify, local_relin}, h->d_partial);
+    for (int it = 0; it < n_iters; ++it) CHK(guarded_sweep(h, local_relin, [&] { return run_sweep(h, call); }));
     h->has_beliefs = true;
     return GBP_OK;
 }
@@ -375,15 +344,11 @@ int gbp_ba_compute_messages(gbp_ba_t *h, int32_t local_relin)
     h->resid_ok = false;
     if (!h->has_beliefs) return fail(GBP_ESTATE, "compute_all_messages needs beliefs (call update_all_beliefs first)");
     CHK(remainder_guard(h, local_relin, 1));
-    const int slot = (int)(h->sweep_count % RELIN_RING);
-    if (slot % (RELIN_RING / 2) == 0)
-        HIPCHK(hipMemsetAsync(h->d_relin_ring + (size_t)slot * RELIN_LANES, 0, sizeof(int) * (RELIN_RING / 2) * RELIN_LANES, h->stream));
-    h->p.relin_slot = h->d_relin_ring + (size_t)slot * RELIN_LANES;
-    h->sweep_count++;
+    CHK(relin_slot_advance(h));
     h->p.stage = STAGE_NO_TEST | STAGE_NO_BELIEFS;
     clock_tick(h, false);                                    // (no relinearisation test in this call: nobody ages)
     h->p.reverse_walk = 0;
-    const int rc = launch_factor_stage(h, 0, local_relin);
+    const int rc = launch_factor_stage(h, {true, 0, local_relin});
     h->p.stage = 0;
     h->pending_possible = false;
     return rc;
@@ -394,10 +359,8 @@ int gbp_ba_shard_begin(gbp_ba_t *h, int32_t with_messages, int32_t robustify, in
     ENTER(h);
     h->resid_ok = false;
     if (!partial_dev) return fail(GBP_EINVAL, "null partial buffer");
-    if (with_messages) CHK(remainder_guard(h, local_relin, 0));
-    CHK(sweep_begin(h, with_messages, robustify, local_relin, partial_dev));
-    if (with_messages) { h->pending_possible = false; CHK(remainder_release(h)); }
-    return GBP_OK;
+    const SweepCall call = SweepCall::partials({with_messages != 0, robustify, local_relin}, partial_dev, false);
+    return with_messages ? guarded_sweep(h, local_relin, [&] { return run_sweep(h, call); }) : run_sweep(h, call);
 }
 
 int gbp_ba_shard_end(gbp_ba_t *h, const double *gathered_dev, int32_t n_ranks)
@@ -405,7 +368,7 @@ int gbp_ba_shard_end(gbp_ba_t *h, const double *gathered_dev, int32_t n_ranks)
     ENTER(h);
     h->resid_ok = false;
     if (!gathered_dev || n_ranks < 1) return fail(GBP_EINVAL, "bad gathered buffer / rank count");
-    CHK(launch_cam_finish(h, gathered_dev, n_ranks, (size_t)h->p.C * 27));
+    CHK(launch_cam_finish(h, gathered_dev, n_ranks, (size_t)h->p.C * 27, nullptr));
     h->has_beliefs = true;
     return GBP_OK;
 }
@@ -533,7 +496,7 @@ int gbp_ba_get_kernel_timing(gbp_ba_t *h, double *total_ms, int32_t *n_launches,
     }
     if (total_ms) *total_ms = tot;
     if (n_launches) *n_launches = (int32_t)(h->ev_used / 2);
-    if (kernel_name) *kernel_name = h->dominant;
+    if (kernel_name) *kernel_name = dominant_kernel(h);
     h->ev_used = 0;
     return GBP_OK;
 }

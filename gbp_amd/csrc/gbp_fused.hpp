@@ -51,12 +51,13 @@
 //
 // Landmarks that span tiles (more than 64 factors: chunk tiles; or the dense packing, gbp_kernels.hpp header): every tile adds up its
 // part of their messages, and their beliefs are formed afterwards by k_lmk_finish_parts.  If acc + the per-wave scratch do not fit the LDS
-// (C > 516) the cameras are split into two groups (516 + up to 758): the sweep adds up the first, k_cam_pass the others; beyond that the
-// plan stays disabled and the general sweep runs.
+// (fused_max_cams) and the workgroups' camera windows do not either, the plan stays disabled and the general sweep runs: its persistent
+// STAGED form has no camera limit (C = 1000: 127 us per sweep, against 138.7 for a second camera group in an extra pass, rounds 2-3).
 #pragma once
 #include "gbp_kernels.hpp"
 #include "gbp_fused_plan.hpp"
 #include "gbp_policy.hpp"
+#include "gbp_handle.hpp"     // SweepCall, SweepLaunch
 #include <mutex>
 
 namespace gbp {
@@ -560,7 +561,7 @@ __global__ __launch_bounds__(ROWS_THREADS) void k_cam_reduce_rows(Params p, cons
 // workgroups first reduces and PUSHES all of its cameras (workgroup tables -> 27 sums -> row c of every rank's mailbox + tag),
 // then finishes them, one wave per camera: wait for the n_ranks tags of row c, add the parts in rank order, prior, mean | covariance.
 // Every workgroup of every rank pushes before it waits, and the grid is never larger than what is resident at once (256-thread
-// workgroups: eight per CU of an MI355X; one camera per workgroup up to 2048 cameras, several beyond; fused_launch caps the grid at
+// workgroups: eight per CU of an MI355X; one camera per workgroup up to 2048 cameras, several beyond; fused_cameras caps the grid at
 // what the occupancy query admits), so ranks cannot wait for each other in a cycle.  (Round 3 ran 1024-thread workgroups bound to 64
 // VGPRs so that two fit a CU; the seven-lane mean | covariance solve of the finish spilled 55 of them: +4 us per sweep.)  Against
 // reduce -> finish as two launches this saves a kernel boundary and the global "all rows are out" hand-off; against RCCL also the
@@ -672,40 +673,36 @@ inline int single_probe(hipStream_t stream, const Overrides &o, int *mask)
 
 // ------------------------------------------------------------------------------------ host --
 
-// (Rounds 2-3 added the messages to a second group of up to 758 cameras in an extra pass over the stored messages, k_cam_pass: 138.7 us
-//  per sweep at C = 1000.  The general sweep's persistent STAGED form does the same graph in 127 us and has no camera limit: removed.)
-
-// Workgroup tile ranges + per-workgroup camera tables.
-// The fused sweep's variants -- loss x PINNED x SINGLE x WINDOWED (each a compile-time property of the persistent loop: a run-time
-// test per tile cost the headline 0.8-1.5 us per sweep) -- as one table, for the plan (LDS attribute) and the launch.
+// The persistent loop's variants -- loss x STAGED | PINNED x SINGLE x WINDOWED (each a compile-time property: a run-time test per tile
+// cost the headline 0.8-1.5 us per sweep) -- as one table, for the plan (LDS attribute) and the launches.
 using SweepKernel = void (*)(Params, FusedArgs, const int4 *);
-template <bool PINNED, bool SINGLE, bool WINDOWED>
+template <bool STAGED, bool PINNED, bool SINGLE, bool WINDOWED>
 inline SweepKernel sweep_variant_of_loss(int loss)
 {
     switch (loss) {
-    case 0: return k_sweep_wat<0, WAT_WAVES, false, PINNED, SINGLE, WINDOWED>;
-    case 1: return k_sweep_wat<1, WAT_WAVES, false, PINNED, SINGLE, WINDOWED>;
-    default: return k_sweep_wat<2, WAT_WAVES, false, PINNED, SINGLE, WINDOWED>;
+    case 0: return k_sweep_wat<0, WAT_WAVES, STAGED, PINNED, SINGLE, WINDOWED>;
+    case 1: return k_sweep_wat<1, WAT_WAVES, STAGED, PINNED, SINGLE, WINDOWED>;
+    default: return k_sweep_wat<2, WAT_WAVES, STAGED, PINNED, SINGLE, WINDOWED>;
     }
 }
 inline SweepKernel sweep_variant(int loss, bool pinned, bool single, bool windowed)
 {
     switch ((pinned ? 1 : 0) + (single ? 2 : 0) + (windowed ? 4 : 0)) {
-    case 0: return sweep_variant_of_loss<false, false, false>(loss);
-    case 1: return sweep_variant_of_loss<true, false, false>(loss);
-    case 2: return sweep_variant_of_loss<false, true, false>(loss);
-    case 3: return sweep_variant_of_loss<true, true, false>(loss);
-    case 4: return sweep_variant_of_loss<false, false, true>(loss);
-    case 5: return sweep_variant_of_loss<true, false, true>(loss);
-    case 6: return sweep_variant_of_loss<false, true, true>(loss);
-    default: return sweep_variant_of_loss<true, true, true>(loss);
+    case 0: return sweep_variant_of_loss<false, false, false, false>(loss);
+    case 1: return sweep_variant_of_loss<false, true, false, false>(loss);
+    case 2: return sweep_variant_of_loss<false, false, true, false>(loss);
+    case 3: return sweep_variant_of_loss<false, true, true, false>(loss);
+    case 4: return sweep_variant_of_loss<false, false, false, true>(loss);
+    case 5: return sweep_variant_of_loss<false, true, false, true>(loss);
+    case 6: return sweep_variant_of_loss<false, false, true, true>(loss);
+    default: return sweep_variant_of_loss<false, true, true, true>(loss);
     }
 }
 
 // wg_win / wg_cams (n_win = workgroups, or 0): the workgroups' camera windows -- build_graph's decision (k_wg_cam_sets: per workgroup
 // {lowest camera, cameras in its set, offset into wg_cams, width of its interval}); without them every workgroup's table covers all cameras.
-inline int fused_plan(FusedPlan &pl, const Params &p, hipStream_t stream, int n_cus, const Overrides &o, const int4 *wg_win = nullptr,
-                      const int *wg_cams = nullptr, int n_win = 0)
+inline int fused_plan(FusedPlan &pl, const Params &p, hipStream_t stream, int n_cus, const Overrides &o, const int4 *wg_win,
+                      const int *wg_cams, int n_win)
 {
     if (p.F == 0 || p.C == 0 || p.T == 0) return 0;
     pl.n_blocks = fused_workgroups(p.T, n_cus, o);
@@ -746,15 +743,14 @@ inline int fused_plan(FusedPlan &pl, const Params &p, hipStream_t stream, int n_
         if (fused_shmem_windows(pl.max_window, pl.max_width) > (size_t)LDS_BYTES) { pl.windowed = 0; return 0; }
     }
     if (!pl.windowed && p.C > cmax) return 0;
-    pl.group_cams = pl.windowed ? std::max(pl.max_window, 1) : p.C;
-    pl.n_groups = 1;
-    const int acc_doubles = pl.group_cams * 27;
-    const size_t shmem = pl.windowed ? fused_shmem_windows(pl.group_cams, pl.max_width) : fused_shmem(pl.group_cams);
+    const int table_cams = pl.windowed ? std::max(pl.max_window, 1) : p.C;      // cameras of a workgroup's LDS table
+    const int acc_doubles = table_cams * 27;
+    const size_t shmem = pl.windowed ? fused_shmem_windows(table_cams, pl.max_width) : fused_shmem(table_cams);
     double *d_bp = nullptr;                                 // (workgroup b walks tiles [b T / n_blocks, (b + 1) T / n_blocks): computed in the kernels)
     pl.table_rows = (long long)table_rows;
     if (fused_upload<double>(pl, &d_bp, nullptr, table_rows * TROW, stream)) return -1;
     pl.args = FusedArgs{};
-    pl.args.block_partials = d_bp; pl.args.acc_doubles = acc_doubles; pl.args.cam_base = 0; pl.args.cam_count = std::min(p.C, pl.group_cams);
+    pl.args.block_partials = d_bp; pl.args.acc_doubles = acc_doubles; pl.args.cam_base = 0; pl.args.cam_count = std::min(p.C, table_cams);
     pl.d_cam_rows = nullptr;
     if (pl.windowed) {
         int4 *d_win = nullptr; int *d_rowidx = nullptr, *d_wgcams = nullptr; int2 *d_cam_rows = nullptr;
@@ -768,7 +764,7 @@ inline int fused_plan(FusedPlan &pl, const Params &p, hipStream_t stream, int n_
     const SweepBytes sb = sweep_bytes(p.T, p.L, p.C, table_rows);
     const double keep_mib = cache_keep_mib(sb.touched, o);
     pl.args.pin = pinned_tiles(keep_mib, sb.fixed, sb.per_tile, pl.n_blocks);
-    pl.single = single_accumulation(pl.group_cams, pl.args.pin != 0x7fffffff, o);
+    pl.single = single_accumulation(table_cams, pl.args.pin != 0x7fffffff, o);
     if (pl.single) {                                    // the order SINGLE relies on is verified on this device before it is used (single_probe)
         pl.single_probe = single_probe(stream, o, &pl.single_probe_mask);
         if (pl.single_probe < 0) return -1;
@@ -790,78 +786,68 @@ inline int fused_plan(FusedPlan &pl, const Params &p, hipStream_t stream, int n_
     return 0;
 }
 
-// returns 0 or a hipError_t value
-inline int fused_launch(FusedPlan &pl, const Params &p0, const Overrides &o, int robustify, int local_relin, double *partial, hipStream_t stream,
-                        int finish, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr, bool defer_big = false, int reverse = 0,
-                        const PeerOut *peer = nullptr, unsigned long long *clk = nullptr, const PeerWait *merged = nullptr)
+// The fused sweep's factor kernel; p carries the call's robustify / local_relin.  (Its launch error is collected by fused_cameras.)
+inline void fused_launch(FusedPlan &pl, const Params &p, const SweepLaunch &at)
 {
-    pl.args.reverse = reverse;
-    pl.args.clk = clk;                                      // [0..1] the sweep kernel's stamps, [2..3] the reduce kernel's
-    Params p = p0;
-    p.robustify = robustify; p.local_relin = local_relin;
-    const dim3 grid(pl.n_blocks), block(WAT_WAVES * 64);
-    if (e0) (void)hipEventRecord(e0, stream);
+    pl.args.reverse = at.reverse;
+    pl.args.clk = at.clk;                                   // [0..1] the sweep kernel's stamps, [2..3] the reduce kernel's
     const bool pinned = pl.args.pin != 0x7fffffff;
-    hipLaunchKernelGGL(sweep_variant(p.loss, pinned, pl.single != 0, pl.windowed != 0), grid, block, pl.shmem, stream, p, pl.args, p.tiles);
-    if (e1) (void)hipEventRecord(e1, stream);
-    if (p.parts && !defer_big) hipLaunchKernelGGL(k_lmk_finish_parts, dim3((p.T + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, p);
-    const size_t red_shmem = 0;                             // (static LDS)
-    PeerOut po{};
-    if (peer) po = *peer;
-    if (merged && peer) {                                   // reduce -> push -> wait -> finish in one launch (peer-store exchange)
-        // The grid must be resident at once (its workgroups wait for other ranks' workgroups of the same index, and the dispatch order
-        // is nobody's contract): never more workgroups than the occupancy query admits on this device.
-        int xb = pl.xchg_blocks;
-        if (xb == 0) {
-            int per_cu = 0, dev = 0, cus = 0;
-            const void *fn = pl.rows_wave ? reinterpret_cast<const void *>(&k_cam_reduce_xchg<true>) : reinterpret_cast<const void *>(&k_cam_reduce_xchg<false>);
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, XCHG_THREADS, red_shmem) != hipSuccess ||
-                hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || per_cu < 1 || cus < 1)
-                return (int)hipErrorUnknown;
-            xb = pl.xchg_blocks = xchg_blocks(per_cu * cus, XCHG_BLOCKS, o);
-        }
-        if (pl.rows_wave)
-            hipLaunchKernelGGL(k_cam_reduce_xchg<true>, dim3(std::min((p.C + XCHG_THREADS / 64 - 1) / (XCHG_THREADS / 64), xb)), dim3(XCHG_THREADS), red_shmem, stream, p,
-                               pl.args.block_partials, pl.n_blocks, partial, po, *merged, clk ? clk + 2 : nullptr, pl.d_cam_rows);
-        else
-            hipLaunchKernelGGL(k_cam_reduce_xchg<false>, dim3(std::min(p.C, xb)), dim3(XCHG_THREADS), red_shmem, stream, p, pl.args.block_partials, pl.n_blocks, partial,
-                               po, *merged, clk ? clk + 2 : nullptr, pl.d_cam_rows);
+    hipLaunchKernelGGL(sweep_variant(p.loss, pinned, pl.single != 0, pl.windowed != 0), dim3(pl.n_blocks), dim3(WAT_WAVES * 64), pl.shmem, at.stream, p, pl.args, p.tiles);
+}
+
+// The grid of a merged exchange must be resident at once (its workgroups wait for other ranks' workgroups of the same index, and the
+// dispatch order is nobody's contract): never more workgroups than the occupancy query admits on this device, nor than the launch's own
+// `cap`.  Asked once per kernel and handle (*cached, 0: not asked yet).  Returns 0 when the query fails.
+inline int resident_blocks(int *cached, const void *fn, int threads, int cap, const SweepLaunch &at)
+{
+    if (!*cached) {
+        int per_cu = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, 0) != hipSuccess || per_cu < 1 || at.n_cus < 1) return 0;
+        *cached = xchg_blocks(per_cu * at.n_cus, cap, *at.ovr);
+    }
+    return *cached;
+}
+
+// The workgroup tables of a fused sweep -> the camera sums, left where c.sink says (one launch each).  Returns 0 or a hipError_t value.
+inline int fused_cameras(FusedPlan &pl, const Params &p, const SweepCall &c, const SweepLaunch &at)
+{
+    unsigned long long *clk = at.clk ? at.clk + 2 : nullptr;
+    const double *tables = pl.args.block_partials;
+    if (c.sink == CamSink::PeerMerged) {                    // reduce -> push -> wait -> finish (peer-store exchange)
+        const auto fn = pl.rows_wave ? k_cam_reduce_xchg<true> : k_cam_reduce_xchg<false>;
+        const int xb = resident_blocks(&pl.xchg_blocks, reinterpret_cast<const void *>(fn), XCHG_THREADS, XCHG_BLOCKS, at);
+        if (!xb) return (int)hipErrorUnknown;
+        const int cams_per_block = pl.rows_wave ? XCHG_THREADS / 64 : 1;
+        hipLaunchKernelGGL(fn, dim3(std::min((p.C + cams_per_block - 1) / cams_per_block, xb)), dim3(XCHG_THREADS), 0, at.stream, p, tables, pl.n_blocks, c.partial,
+                           *c.peer, *c.wait, clk, pl.d_cam_rows);
         return (int)hipGetLastError();
     }
-    if (pl.rows_wave) {
-        hipLaunchKernelGGL(k_cam_reduce_rows, dim3((p.C + ROWS_THREADS / 64 - 1) / (ROWS_THREADS / 64)), dim3(ROWS_THREADS), 0, stream, p, pl.args.block_partials,
-                           pl.d_cam_rows, partial, finish, po, clk ? clk + 2 : nullptr);
-        return (int)hipGetLastError();
-    }
-    hipLaunchKernelGGL(k_cam_reduce_tree, dim3(p.C), dim3(RED_THREADS), red_shmem, stream, p, pl.args.block_partials, pl.n_blocks, partial, finish, po, clk ? clk + 2 : nullptr, pl.d_cam_rows);
+    const int finish = c.sink == CamSink::Finish ? 1 : 0;
+    const PeerOut po = c.sink == CamSink::PeerPush ? *c.peer : PeerOut{};
+    if (pl.rows_wave)
+        hipLaunchKernelGGL(k_cam_reduce_rows, dim3((p.C + ROWS_THREADS / 64 - 1) / (ROWS_THREADS / 64)), dim3(ROWS_THREADS), 0, at.stream, p, tables, pl.d_cam_rows,
+                           c.partial, finish, po, clk);
+    else
+        hipLaunchKernelGGL(k_cam_reduce_tree, dim3(p.C), dim3(RED_THREADS), 0, at.stream, p, tables, pl.n_blocks, c.partial, finish, po, clk, pl.d_cam_rows);
     return (int)hipGetLastError();
 }
 
-// the general sweep's factor kernel: the persistent loop in its STAGED form (no table: any number of cameras)
+// The general sweep's factor kernel: the persistent loop in its STAGED form (no table: any number of cameras).  full_rows: FusedArgs.
 // attr_set: the caller's per-handle flag -- the dynamic-LDS attribute is a property of (kernel, device), and handles of one process may
-// sit on different devices (ranks as threads)
-inline int staged_launch(const Params &p0, int robustify, int local_relin, int n_cus, int reverse, hipStream_t stream, unsigned long long *clk, int full_rows,
-                         bool *attr_set)
+// sit on different devices (ranks as threads).  Returns 0 or a hipError_t value.
+inline int staged_launch(const Params &p, const SweepLaunch &at, int full_rows, bool *attr_set)
 {
-    Params p = p0;
-    p.robustify = robustify; p.local_relin = local_relin;
     FusedArgs a{};
-    a.reverse = reverse; a.clk = clk; a.full_rows = full_rows; a.pin = 0x7fffffff;
-    const int n_blocks = std::max(1, std::min(p.T, n_cus));
+    a.reverse = at.reverse; a.clk = at.clk; a.full_rows = full_rows; a.pin = 0x7fffffff;
     const size_t shmem = sizeof(double) * ((size_t)WAT_WAVES * STAGED_WAVE_DOUBLES + 1);
     if (!*attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sweep_wat<0, WAT_WAVES, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sweep_wat<1, WAT_WAVES, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sweep_wat<2, WAT_WAVES, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem) != hipSuccess)
-            return (int)hipErrorUnknown;
+        for (int loss = 0; loss < 3; ++loss)
+            if (hipFuncSetAttribute(reinterpret_cast<const void *>(sweep_variant_of_loss<true, false, false, false>(loss)), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)shmem) != hipSuccess) return (int)hipErrorUnknown;
         *attr_set = true;
     }
-    const dim3 grid(n_blocks), block(WAT_WAVES * 64);
-    switch (p.loss) {
-    case 0: hipLaunchKernelGGL((k_sweep_wat<0, WAT_WAVES, true>), grid, block, shmem, stream, p, a, p.tiles); break;
-    case 1: hipLaunchKernelGGL((k_sweep_wat<1, WAT_WAVES, true>), grid, block, shmem, stream, p, a, p.tiles); break;
-    default: hipLaunchKernelGGL((k_sweep_wat<2, WAT_WAVES, true>), grid, block, shmem, stream, p, a, p.tiles); break;
-    }
+    hipLaunchKernelGGL((sweep_variant_of_loss<true, false, false, false>(p.loss)), dim3(std::max(1, std::min(p.T, at.n_cus))), dim3(WAT_WAVES * 64), shmem, at.stream, p, a,
+                       p.tiles);
     return (int)hipGetLastError();
 }
 

@@ -11,7 +11,7 @@
 namespace gbp {
 
 constexpr int LDS_BYTES = 160 * 1024;
-constexpr int XCHG_BLOCKS = 2048;                   // most workgroups of the merged reduce-exchange-finish launch (k_cam_reduce_xchg, fused_launch)
+constexpr int XCHG_BLOCKS = 2048;                   // most workgroups of the merged reduce-exchange-finish launch (k_cam_reduce_xchg, fused_cameras)
 constexpr int TROW = 28;                            // doubles per row of the workgroup tables in HBM (27 + pad: 16-byte stores / loads)
 #ifndef GBP_WAT_WAVES
 #define GBP_WAT_WAVES 8
@@ -45,9 +45,9 @@ constexpr int NPHASE = 12;          // marks of the phase profile (experimental/
 struct FusedArgs {
     double *block_partials;     // [C][n_blocks][TROW]: 27 sums + one pad double, so that a row starts on 16 bytes (WINDOWED: the rows of a
                                 // camera are those of the workgroups whose camera set holds it, in workgroup order: FusedPlan::d_cam_rows)
-    int acc_doubles;            // cameras of the group * 27
-    int cam_base, cam_count;    // the cameras whose messages THIS launch adds up in its LDS table (all of them when C fits)
-    int reverse;                // walk the workgroup's tile range backwards (every other sweep: see fused_launch)
+    int acc_doubles;            // cameras of the workgroup's table * 27
+    int cam_base, cam_count;    // the cameras whose messages THIS launch adds up in its LDS table: always 0 / min(C, table cameras)
+    int reverse;                // walk the workgroup's tile range backwards (every other sweep: see run_sweep)
     int nt;                     // which factor streams bypass the memory-side cache (issue_streams)
     GBP_INSTRUMENT_ARGS         // (scratch builds of tools/ only: `int dbg; unsigned long long *phase;`)
     unsigned long long *clk;    // instrumented runs (gbp_ba_set_kernel_timing): where workgroup 0 stores the device's constant-rate clock
@@ -64,7 +64,6 @@ struct FusedArgs {
 
 struct FusedPlan {
     bool enabled = false;
-    int n_groups = 0, group_cams = 0;                // (one camera group: the whole table in LDS)
     int n_blocks = 0;
     int xchg_blocks = 0;                             // grid of the merged reduce-exchange-finish launch (0: not asked yet)
     long long table_rows = 0;                        // rows of block_partials

@@ -1,7 +1,8 @@
 // gbp_handle.hpp -- what the translation units of libgbp_hip.so share about a handle (private: include/gbp_ba.h is the boundary).
 //
 //   gbp_capi.hip        life cycle: errors, create / destroy (graph build), streams, priors, BAL reader, plan info, layout checks
-//   gbp_capi_sweep.hip  every launch of a sweep: fused + general + stage-wise, the dense remainder, diagnostics, kernel timing
+//   gbp_capi_sweep.hip  every launch of a sweep (run_sweep: one SweepCall in, the cameras left where its sink says): fused + general +
+//                       stage-wise, the dense remainder, diagnostics, kernel timing
 //   gbp_capi_shard.hip  the landmark-sharded loop: RCCL, peer-store mailboxes, the exchange between reduce and finish
 //   gbp_capi_views.hip  state views (beliefs, messages, factors, relinearisation state), streaming means, eval_fn
 //   gbp_capi_state.hip  checkpoints (host blob, device slot)
@@ -45,6 +46,38 @@ int set_error(int code, const char *fmt, ...);      // gbp_capi.hip: the thread-
     HIPCHK(hipSetDevice((h)->device))
 
 using namespace gbp;
+
+// ---- one sweep call ------------------------------------------------------------------------------------------------------------------
+// What a caller of run_sweep chooses: which of the reference's calls runs, and where the camera partial sums (27 per camera) go after
+// the factor kernel.  The sink names the state the cameras are in when run_sweep returns:
+//   Finish      the camera beliefs are complete (single GPU, or sharded with one rank)
+//   Partials    the sums lie in `partial` for a collective; the caller finishes from the gathered buffer (launch_cam_finish)
+//   PeerPush    the sums are on their way into every rank's mailbox; the caller owes the waiting finish (after its rendezvous hook)
+//   PeerMerged  reduce -> push -> wait -> finish in one launch: the camera beliefs are complete
+enum class CamSink { Finish, Partials, PeerPush, PeerMerged };
+struct SweepStep {
+    bool messages;                               // true: synchronous_iteration; false: update_all_beliefs from the stored messages
+    int robustify, local_relin;
+};
+struct SweepCall {
+    SweepStep step;
+    CamSink sink;
+    double *partial;                             // where the 27 sums per camera are written
+    bool defer_parts;                            // Partials only: k_lmk_finish_parts is the caller's, beside its exchange (launch_finish_parts)
+    const PeerOut *peer;                         // PeerPush / PeerMerged
+    const PeerWait *wait;                        // PeerMerged
+    static SweepCall finish(SweepStep s, double *partial) { return {s, CamSink::Finish, partial, false, nullptr, nullptr}; }
+    static SweepCall partials(SweepStep s, double *partial, bool defer_parts) { return {s, CamSink::Partials, partial, defer_parts, nullptr, nullptr}; }
+    static SweepCall peer_push(SweepStep s, double *partial, const PeerOut *peer) { return {s, CamSink::PeerPush, partial, false, peer, nullptr}; }
+    static SweepCall peer_merged(SweepStep s, double *partial, const PeerOut *peer, const PeerWait *wait) { return {s, CamSink::PeerMerged, partial, false, peer, wait}; }
+};
+// what a launch of the persistent loop takes from the handle (gbp_fused.hpp)
+struct SweepLaunch {
+    hipStream_t stream;
+    int reverse;                                 // walk every workgroup's tile range backwards
+    unsigned long long *clk;                     // instrumented runs: the sweep's row of device-clock stamps (gbp_ba::d_clk), or NULL
+    int n_cus; const Overrides *ovr;             // the grid cap of a merged exchange (resident_blocks)
+};
 
 struct gbp_ba {
     Params p{};
@@ -91,10 +124,8 @@ struct gbp_ba {
     bool timing = false;
     int timing_every = 1, timing_tick = 0;       // events around every n-th launch of the dominant kernel (two event
                                                  // records per sweep cost ~6 us of a 125 us sweep)
-    bool timing_now = false;
     std::vector<hipEvent_t> ev;                  // pairs
     size_t ev_used = 0;
-    const char *dominant = "k_factor_tile";
     // device-clock stamps of instrumented sweeps: [CLK_RING][6] = {sweep start, end, reduce start, end, finish start, end}
     unsigned long long *d_clk = nullptr, *clk_cur = nullptr;
     int clk_used = 0, clk_rate_khz = 0;
@@ -214,6 +245,9 @@ inline void clock_tick(gbp_ba *h, bool advance)
 }
 
 
+// the kernel whose launches are timed (gbp_ba_get_kernel_timing): the factor kernel of the sweep this handle runs now
+inline const char *dominant_kernel(const gbp_ba *h) { return h->fused.enabled ? "k_sweep_fused" : h->p.xtra ? "k_factor_tile" : "k_sweep_staged"; }
+
 inline size_t n_slots(const gbp_ba *h) { return std::max<size_t>((size_t)h->p.T * WTILE, 1); }
 
 // mailbox geometry: [2 halves][n_ranks][C] rows of PEER_ROW doubles (27 sums | tag), then [n_ranks] probe rows (gbp_ba_peer_selftest)
@@ -238,9 +272,8 @@ int prior_scalars_range(gbp_ba *h, int c0, int l0, double w2_cam, double w2_lmk)
 // gbp_capi_sweep.hip
 int plan_fused_sweep(gbp_ba *h, int n_cus);          // fused_plan on the handle (the kernels whose attributes it sets live in that unit)
 int fused_max_cams_of_this_build();
-int sweep_begin(gbp_ba *h, int with_messages, int robustify, int local_relin, double *partial, int finish = 0, bool *finished = nullptr,
-                bool defer_big = false, const PeerOut *peer = nullptr, const PeerWait *merged = nullptr);
-int launch_cam_finish(gbp_ba *h, const double *gathered, int n_parts, size_t stride, const PeerWait *wait = nullptr);
+int run_sweep(gbp_ba *h, const SweepCall &c);         // one sweep (or belief update) on the handle's stream; the cameras end where c.sink says
+int launch_cam_finish(gbp_ba *h, const double *gathered, int n_parts, size_t stride, const PeerWait *wait);     // wait: the peer-store mailbox rows, or NULL (plain arrays)
 int launch_finish_parts(gbp_ba *h, hipStream_t stream);      // beliefs of the landmarks that span tiles (after a sweep's factor kernel)
 int launch_peer_selftest(gbp_ba *h, const PeerOut &po, double *mine, int rank, long long ticks, int *d_out);
 int enable_remainder(gbp_ba *h);
@@ -251,3 +284,14 @@ int remainder_release(gbp_ba *h);
 void peer_release(gbp_ba *h);
 void shard_comm_release(gbp_ba *h);
 }  // namespace gbp
+
+// one sweep of an iterate entry point: a pending stage-wise relinearisation that meets a damping switches the dense remainder on before
+// it, and a remainder that has decayed to zero is switched off after it
+template <typename Sweep>
+inline int guarded_sweep(gbp_ba *h, int local_relin, Sweep &&sweep)
+{
+    CHK(remainder_guard(h, local_relin, 0));
+    CHK(sweep());
+    h->pending_possible = false;                 // every pending relinearisation has been applied
+    return remainder_release(h);
+}

@@ -101,7 +101,7 @@ inline int pinned_tiles(double keep_mib, double fixed, double per_tile, int n_bl
 // Few cameras: many factors of a 60-factor tile share one (fr1desk: 63 cameras, up to eight) -- the SINGLE variant of the accumulation.
 // 1M factors: 66.1 against 75.1 us per step at 64 cameras, 68.0 / 72.4 at 128, 69.7 / 71.6 at 200, 72.7 / 73.4 at 300, equal at 400,
 // 75.2 / 74.3 at 500; beyond the cache size -- the pinned variant -- 2M factors: 135.4 / 148.3 at 100 cameras, 151.0 / 143.7 at 300.
-inline int single_accumulation(int group_cams, bool pinned, const Overrides &o) { return o.acc_single ? *o.acc_single : (group_cams <= (pinned ? 200 : 350) ? 1 : 0); }
+inline int single_accumulation(int table_cams, bool pinned, const Overrides &o) { return o.acc_single ? *o.acc_single : (table_cams <= (pinned ? 200 : 350) ? 1 : 0); }
 inline int single_probe_mask(int measured, const Overrides &o) { return o.single_probe_fail.value_or(measured); }
 
 // Threads per camera of the staged reduce.  Short runs (a camera with a few hundred factors) leave most of a 256-thread block idle through

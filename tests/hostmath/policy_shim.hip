@@ -56,7 +56,7 @@ int policy_cam_block(long long F, int C) { return cam_block(F, C, g_o); }
 int policy_xchg_blocks(int resident, int cap) { return xchg_blocks(resident, cap, g_o); }
 int policy_merged_exchange(int has_hook, int with_messages) { return merged_exchange(has_hook, with_messages, g_o); }
 
-// what the launches pass: the caps of the two merged exchanges (fused_launch, sweep_begin), and the plan's arithmetic
+// what the launches pass: the caps of the two merged exchanges (fused_cameras, staged_cameras), and the plan's arithmetic
 int policy_xchg_cap_fused(void) { return XCHG_BLOCKS; }
 int policy_xchg_cap_staged(void) { return INT32_MAX; }
 int policy_fused_max_cams(void) { return fused_max_cams(); }
