@@ -75,6 +75,7 @@ SIGNATURES = {
     'gbp_ba_set_stream': (ct.c_int, [ct.c_void_p, ct.c_void_p]),
     'gbp_ba_sync': (ct.c_int, [ct.c_void_p]),
     'gbp_ba_extend': (ct.c_int, [ct.c_void_p, ct.POINTER(Ext), _ip]),
+    'gbp_ba_retire': (ct.c_int, [ct.c_void_p, ct.c_int32, _ip, _ip, _ip, _ip]),
     'gbp_ba_generate_priors': (ct.c_int, [ct.c_void_p, ct.c_double]),
     'gbp_ba_factor_lambda_max': (ct.c_int, [ct.c_void_p, _dp, _dp]),
     'gbp_ba_set_prior_scalars': (ct.c_int, [ct.c_void_p, _dp, _dp]),

@@ -383,6 +383,27 @@ class BAFactorGraph:
         self._adj = None
         return o2n
 
+    # ---- shrinking (BAEngine.retire, include/gbp_ba.h gbp_ba_retire) -------------------------------------------
+    def retire_keyframes(self, cam_ids):
+        """Retire cameras the way a fixed-lag front end drops old keyframes: their factors' messages are folded into the landmarks' priors,
+        the cameras, their factors and the landmarks left without a factor leave the graph, the rest is renumbered compactly and keeps
+        its state; every node and factor view is rebuilt over the survivors.  Returns (cam_map, lmk_map, factor_map): new id of every old
+        camera / landmark / factor, -1 for what is gone.  Views taken BEFORE the call are stale afterwards, as after extend."""
+        self._flush()
+        cm, lm, fm = self._engine.retire(cam_ids)
+        keep = fm >= 0
+        self._cam_of, self._lmk_of = cm[self._cam_of[keep]].astype(np.int32), lm[self._lmk_of[keep]].astype(np.int32)
+        self._C, self._L, self._F = self._engine.C, self._engine.L, self._engine.F
+        self.cam_nodes = _Lazy(self._C, lambda i: _VariableView(self, 0, i))
+        self.lmk_nodes = _Lazy(self._L, lambda i: _VariableView(self, 1, i))
+        self.factors = _FactorSeq(self, self._F)
+        self.var_nodes = _Concat(self.cam_nodes, self.lmk_nodes)
+        self.n_var_nodes, self.n_factor_nodes, self.n_edges = self._C + self._L, self._F, 2 * self._F
+        self._cache = {}
+        self._iters_dev, self._iters_fresh, self._views_out = None, False, False
+        self._adj = None
+        return cm, lm, fm
+
     # ---- priors (gbp_ba.py:20-52) ------------------------------------------------------------------------------
     def generate_priors_var(self, weaker_factor=100):
         self._flush()

@@ -7,9 +7,7 @@
 // gives exactly the reference's union order (old factors before new ones inside a camera), the new factors are linearised at the right
 // points for free (old variables contribute their current means), and the build's ref_file map tells which union factor was which old
 // one (file index < F_old: old reference id = file index).
-#include "gbp_handle.hpp"
-
-#include <new>
+#include "gbp_graft.hpp"
 
 namespace {
 
@@ -63,29 +61,7 @@ __global__ __launch_bounds__(BLOCK) void k_transplant_slots(Params n, Params o, 
     if (f >= o.F) return;
     const int os = o.cadj[f];
     old_to_new[f] = r;
-    double2 *nl = reinterpret_cast<double2 *>(n.lin);
-    const double2 *ol = reinterpret_cast<const double2 *>(o.lin);
-#pragma unroll
-    for (int k = 0; k < LIN_ROWS / 2 - 1; ++k) nl[lin_at(slot, 2 * k) / 2] = ol[lin_at(os, 2 * k) / 2];
-    {
-        const size_t nix = lin_at(slot, ROW_Z + 1) / 2;     // z[1] | meta, state
-        double2 v = ol[lin_at(os, ROW_Z + 1) / 2];
-        const double2 mine = nl[nix];
-        const unsigned *mw = reinterpret_cast<const unsigned *>(&mine.y);
-        unsigned *w = reinterpret_cast<unsigned *>(&v.y);
-        w[0] = mw[0];
-        w[1] = (w[1] & ~(STATE_RANK_MASK << 2)) | (mw[1] & (STATE_RANK_MASK << 2));
-        nl[nix] = v;
-    }
-    double2 *nm = reinterpret_cast<double2 *>(n.msg);
-    const double2 *om = reinterpret_cast<const double2 *>(o.msg);
-#pragma unroll
-    for (int k = 0; k < MSG_ROWS / 2; ++k) nm[msg_at(slot, 2 * k) / 2] = om[msg_at(os, 2 * k) / 2];
-    if (o.avar && n.avar) n.avar[slot] = o.avar[os];
-    if (o.xtra && n.xtra) {
-#pragma unroll
-        for (int k = 0; k < XTRA_ROW; ++k) n.xtra[(size_t)slot * XTRA_ROW + k] = o.xtra[(size_t)os * XTRA_ROW + k];
-    }
+    transplant_slot(n, o, slot, os);
 }
 
 // per-variable state of the old variables: camera records, belief views and priors; landmark mean | covariance and prior (the slot range
@@ -93,44 +69,8 @@ __global__ __launch_bounds__(BLOCK) void k_transplant_slots(Params n, Params o, 
 __global__ __launch_bounds__(BLOCK) void k_transplant_vars(Params n, Params o)
 {
     const int v = blockIdx.x * BLOCK + threadIdx.x;
-    if (v < o.C) {
-#pragma unroll
-        for (int k = 0; k < CAMREC; ++k) n.cbel[(size_t)v * CAMREC + k] = o.cbel[(size_t)v * CAMREC + k];
-#pragma unroll
-        for (int k = 0; k < CBEL; ++k) n.cbelief[(size_t)v * CBEL + k] = o.cbelief[(size_t)v * CBEL + k];
-#pragma unroll
-        for (int k = 0; k < 27; ++k) n.cprior[(size_t)v * 27 + k] = o.cprior[(size_t)v * 27 + k];
-    } else if (v < o.C + o.L) {
-        const size_t l = (size_t)(v - o.C);
-        double *nr = n.lrec + l * LREC;
-        const double *orr = o.lrec + l * LREC;
-#pragma unroll
-        for (int k = 0; k < LR_ROWS; ++k) nr[k] = orr[k];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) nr[LR_PRIOR + k] = orr[LR_PRIOR + k];
-    }
-}
-
-template <typename T>
-int stage(gbp_ba *h, const T *src, size_t n, bool on_device, std::vector<void *> &scratch, const T **out)
-{
-    if (on_device || !n) { *out = src; return GBP_OK; }
-    void *q = nullptr;
-    HIPCHK(hipMallocAsync(&q, n * sizeof(T), h->stream));
-    scratch.push_back(q);
-    HIPCHK(hipMemcpyAsync(q, src, n * sizeof(T), hipMemcpyHostToDevice, h->stream));
-    *out = static_cast<const T *>(q);
-    return GBP_OK;
-}
-
-template <typename T>
-int scratch_buf(gbp_ba *h, std::vector<void *> &scratch, T **out, size_t n)
-{
-    void *q = nullptr;
-    HIPCHK(hipMallocAsync(&q, std::max<size_t>(n, 1) * sizeof(T), h->stream));
-    scratch.push_back(q);
-    *out = static_cast<T *>(q);
-    return GBP_OK;
+    if (v < o.C) transplant_cam(n, o, v, v);
+    else if (v < o.C + o.L) transplant_lmk(n, o, v - o.C, v - o.C);
 }
 
 // the union built beside the old handle `o` into the fresh handle `n` (which owns nothing of o's)
@@ -140,30 +80,19 @@ int extend_into(gbp_ba *o, gbp_ba *n, const gbp_ba_ext_t *e, std::vector<void *>
     const int dC = e->n_new_cams, dL = e->n_new_lmks, dF = e->n_new_factors;
     const int C = op.C + dC, L = op.L + dL, F = op.F + dF;
     const bool dev_in = (e->flags & GBP_FLAG_DEVICE_INPUT) != 0;
-    // what create sets from the descriptor, taken from the old handle as it is (no double -> descriptor -> double round trip)
-    n->device = o->device; n->ovr = o->ovr; n->n_cus = o->n_cus;
-    n->stream = o->stream;                                    // (not owned: the handle keeps its streams)
-    n->flags = o->staged_auto ? (o->flags & ~GBP_FLAG_NO_FUSED) : o->flags;     // the flags of create, before the sparseness rule added NO_FUSED
+    graft_settings(o, n, C, L, F);
     Params &p = n->p;
-    p = Params{};
-    p.F = F; p.L = L; p.C = C; p.T = 0;
-    p.K = op.K; p.sigma2 = op.sigma2; p.nstds = op.nstds; p.beta = op.beta; p.eta_damping = op.eta_damping;
-    p.num_undamped = op.num_undamped; p.min_linear = op.min_linear; p.loss = op.loss;
-    p.robustify = 0; p.local_relin = 1;
-    p.crow = op.num_undamped == 0 ? CSTAGE_ROW : CSTAGE_PLAIN;
-    p.clk = op.clk; p.clk_inc = 0;                             // new factors are stamped iters_since_relin = 1 against the handle's clock
-    p.reverse_walk = op.reverse_walk;
 
     // 1. the union's inputs, on the device
     const double *bcm = nullptr, *blm = nullptr, *bmeas = nullptr;
     const int *bcam = nullptr, *blmk = nullptr;
-    CHK(stage(n, e->cam_means, (size_t)dC * 6, dev_in, scratch, &bcm)); CHK(stage(n, e->lmk_means, (size_t)dL * 3, dev_in, scratch, &blm));
-    CHK(stage(n, e->meas, (size_t)dF * 2, dev_in, scratch, &bmeas));
-    CHK(stage(n, e->cam_idx, (size_t)dF, dev_in, scratch, &bcam)); CHK(stage(n, e->lmk_idx, (size_t)dF, dev_in, scratch, &blmk));
+    CHK(graft_stage(n, e->cam_means, (size_t)dC * 6, dev_in, scratch, &bcm)); CHK(graft_stage(n, e->lmk_means, (size_t)dL * 3, dev_in, scratch, &blm));
+    CHK(graft_stage(n, e->meas, (size_t)dF * 2, dev_in, scratch, &bmeas));
+    CHK(graft_stage(n, e->cam_idx, (size_t)dF, dev_in, scratch, &bcam)); CHK(graft_stage(n, e->lmk_idx, (size_t)dF, dev_in, scratch, &blmk));
     double *u_meas = nullptr, *u_cm = nullptr, *u_lm = nullptr;
     int *u_cam = nullptr, *u_lmk = nullptr;
-    CHK(scratch_buf(n, scratch, &u_meas, (size_t)F * 2)); CHK(scratch_buf(n, scratch, &u_cam, (size_t)F)); CHK(scratch_buf(n, scratch, &u_lmk, (size_t)F));
-    CHK(scratch_buf(n, scratch, &u_cm, (size_t)C * 6)); CHK(scratch_buf(n, scratch, &u_lm, (size_t)L * 3));
+    CHK(graft_scratch(n, scratch, &u_meas, (size_t)F * 2)); CHK(graft_scratch(n, scratch, &u_cam, (size_t)F)); CHK(graft_scratch(n, scratch, &u_lmk, (size_t)F));
+    CHK(graft_scratch(n, scratch, &u_cm, (size_t)C * 6)); CHK(graft_scratch(n, scratch, &u_lm, (size_t)L * 3));
     if (F) hipLaunchKernelGGL(k_union_factors, dim3(grid_for((size_t)F)), dim3(BLOCK), 0, n->stream, op, o->d_ref_cam, o->d_ref_lmk, bmeas, bcam, blmk, dF,
                               u_meas, u_cam, u_lmk);
     const size_t nv = (size_t)C * 6 + (size_t)L * 3;
@@ -183,14 +112,12 @@ int extend_into(gbp_ba *o, gbp_ba *n, const gbp_ba_ext_t *e, std::vector<void *>
 
     // 4. the state transplant
     int *d_o2n = nullptr;
-    CHK(scratch_buf(n, scratch, &d_o2n, (size_t)op.F));
+    CHK(graft_scratch(n, scratch, &d_o2n, (size_t)op.F));
     const size_t S = n_slots(n);
     if (p.T && op.F) hipLaunchKernelGGL(k_transplant_slots, dim3(grid_for(S)), dim3(BLOCK), 0, n->stream, p, op, ref_file, d_o2n);
     if (op.C + op.L) hipLaunchKernelGGL(k_transplant_vars, dim3(grid_for((size_t)op.C + op.L)), dim3(BLOCK), 0, n->stream, p, op);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(n->d_relin_ring, o->d_relin_ring, sizeof(int) * (size_t)RELIN_RING * RELIN_LANES, hipMemcpyDeviceToDevice, n->stream));
-    n->sweep_count = o->sweep_count; n->walk_parity = o->walk_parity; n->gen_parity = o->gen_parity;
-    n->pending_possible = o->pending_possible; n->lazy_since = o->lazy_since;
+    CHK(graft_counters(o, n));
 
     // 5. priors of the new variables: the rule over their factors (all of them new), or the given scalars
     const double wf = e->prior_weaker_factor;
@@ -251,28 +178,8 @@ int gbp_ba_extend(gbp_ba_t *h, const gbp_ba_ext_t *e, int32_t *old_to_new)
     }
     for (void *q : scratch) (void)hipFreeAsync(q, h->stream);
     (void)hipStreamSynchronize(h->stream);
-    if (rc != GBP_OK) {
-        n->stream = nullptr;                                  // (the stream is the old handle's)
-        const std::string keep = gbp_last_error();            // (as gbp_ba_create does: the message outlives the clean-up)
-        gbp_ba_destroy(n);
-        return fail(rc, "%s", keep.c_str());
-    }
-    // what the handle keeps: its streams, timing settings and instrumentation buffers (the rest of it is the union's now)
-    std::swap(n->own_stream, h->own_stream);
-    std::swap(n->timing, h->timing); std::swap(n->timing_every, h->timing_every); std::swap(n->timing_tick, h->timing_tick);
-    std::swap(n->ev, h->ev); std::swap(n->ev_used, h->ev_used);
-    std::swap(n->clk_used, h->clk_used); std::swap(n->clk_rate_khz, h->clk_rate_khz);
-    std::swap(n->clk_calibrated, h->clk_calibrated); std::swap(n->clk_rate_khz_measured, h->clk_rate_khz_measured);
-    std::swap(n->side_stream, h->side_stream); std::swap(n->ev_fork, h->ev_fork); std::swap(n->ev_join, h->ev_join);
-    if (h->d_clk) {
-        h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), static_cast<void *>(h->d_clk)), h->allocs.end());
-        n->allocs.push_back(h->d_clk);
-        n->d_clk = h->d_clk; h->d_clk = nullptr;
-    }
-    std::swap(*h, *n);                                        // h: the union; n: what is left of the old handle
-    h->fused.alloc_ctx = h;
-    n->stream = h->stream;                                    // (synchronised by destroy, not destroyed: own_stream went over)
-    gbp_ba_destroy(n);
+    if (rc != GBP_OK) return graft_abandon(n, rc);
+    graft_swap(h, n);
     if (old_to_new && !o2n.empty()) std::memcpy(old_to_new, o2n.data(), o2n.size() * sizeof(int32_t));
     return GBP_OK;
 }

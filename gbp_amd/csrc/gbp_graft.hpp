@@ -1,0 +1,146 @@
+// gbp_graft.hpp -- what the two calls that rebuild a live handle share (gbp_ba_extend: gbp_capi_extend.hip, gbp_ba_retire:
+// gbp_capi_retire.hip).  Both build the new graph BESIDE the handle by the create path (gbp::build_graph), move the state of the factors
+// and variables that live on into the new layout, and swap the new graph in only when everything has succeeded.  Here: the per-slot and
+// per-variable moves (device), and on the host the settings the new graph inherits, the counters it carries and the swap itself.
+#pragma once
+#include "gbp_handle.hpp"
+
+#include <new>
+
+namespace gbp {
+
+// A factor's whole state from its old slot `os` (gathered) to its new slot (written as the tile-contiguous row pairs of gbp_kernels.hpp:
+// 16 contiguous bytes per lane and pair, 1 KB per wave and pair).  The meta word and the rank field of the state word are the new
+// layout's (k_build_tiles wrote them); everything else is the old factor's: linearisation point, measurement, clock stamp, pending /
+// robust / damped bits, messages, adaptive variance, dense remainder.
+GBP_DEV void transplant_slot(const Params &n, const Params &o, int slot, int os)
+{
+    double2 *nl = reinterpret_cast<double2 *>(n.lin);
+    const double2 *ol = reinterpret_cast<const double2 *>(o.lin);
+#pragma unroll
+    for (int k = 0; k < LIN_ROWS / 2 - 1; ++k) nl[lin_at(slot, 2 * k) / 2] = ol[lin_at(os, 2 * k) / 2];
+    {
+        const size_t nix = lin_at(slot, ROW_Z + 1) / 2;     // z[1] | meta, state
+        double2 v = ol[lin_at(os, ROW_Z + 1) / 2];
+        const double2 mine = nl[nix];
+        const unsigned *mw = reinterpret_cast<const unsigned *>(&mine.y);
+        unsigned *w = reinterpret_cast<unsigned *>(&v.y);
+        w[0] = mw[0];
+        w[1] = (w[1] & ~(STATE_RANK_MASK << 2)) | (mw[1] & (STATE_RANK_MASK << 2));
+        nl[nix] = v;
+    }
+    double2 *nm = reinterpret_cast<double2 *>(n.msg);
+    const double2 *om = reinterpret_cast<const double2 *>(o.msg);
+#pragma unroll
+    for (int k = 0; k < MSG_ROWS / 2; ++k) nm[msg_at(slot, 2 * k) / 2] = om[msg_at(os, 2 * k) / 2];
+    if (o.avar && n.avar) n.avar[slot] = o.avar[os];
+    if (o.xtra && n.xtra) {
+#pragma unroll
+        for (int k = 0; k < XTRA_ROW; ++k) n.xtra[(size_t)slot * XTRA_ROW + k] = o.xtra[(size_t)os * XTRA_ROW + k];
+    }
+}
+
+// camera oc of the old graph becomes camera nc of the new one: record, belief view and prior
+GBP_DEV void transplant_cam(const Params &n, const Params &o, int nc, int oc)
+{
+#pragma unroll
+    for (int k = 0; k < CAMREC; ++k) n.cbel[(size_t)nc * CAMREC + k] = o.cbel[(size_t)oc * CAMREC + k];
+#pragma unroll
+    for (int k = 0; k < CBEL; ++k) n.cbelief[(size_t)nc * CBEL + k] = o.cbelief[(size_t)oc * CBEL + k];
+#pragma unroll
+    for (int k = 0; k < 27; ++k) n.cprior[(size_t)nc * 27 + k] = o.cprior[(size_t)oc * 27 + k];
+}
+
+// landmark ol of the old graph becomes landmark nl of the new one: mean | covariance and prior (the slot range of the record is the new layout's)
+GBP_DEV void transplant_lmk(const Params &n, const Params &o, int nl, int ol)
+{
+    double *nr = n.lrec + (size_t)nl * LREC;
+    const double *orr = o.lrec + (size_t)ol * LREC;
+#pragma unroll
+    for (int k = 0; k < LR_ROWS; ++k) nr[k] = orr[k];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) nr[LR_PRIOR + k] = orr[LR_PRIOR + k];
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------------
+template <typename T>
+inline int graft_stage(gbp_ba *h, const T *src, size_t n, bool on_device, std::vector<void *> &scratch, const T **out)
+{
+    if (on_device || !n) { *out = src; return GBP_OK; }
+    void *q = nullptr;
+    HIPCHK(hipMallocAsync(&q, n * sizeof(T), h->stream));
+    scratch.push_back(q);
+    HIPCHK(hipMemcpyAsync(q, src, n * sizeof(T), hipMemcpyHostToDevice, h->stream));
+    *out = static_cast<const T *>(q);
+    return GBP_OK;
+}
+
+template <typename T>
+inline int graft_scratch(gbp_ba *h, std::vector<void *> &scratch, T **out, size_t n)
+{
+    void *q = nullptr;
+    HIPCHK(hipMallocAsync(&q, std::max<size_t>(n, 1) * sizeof(T), h->stream));
+    scratch.push_back(q);
+    *out = static_cast<T *>(q);
+    return GBP_OK;
+}
+
+// what create sets from the descriptor, taken from the old handle `o` as it is (no double -> descriptor -> double round trip), for a
+// graph of C cameras, L landmarks and F factors on the fresh handle `n` (which owns nothing of o's)
+inline void graft_settings(const gbp_ba *o, gbp_ba *n, int C, int L, int F)
+{
+    const Params &op = o->p;
+    n->device = o->device; n->ovr = o->ovr; n->n_cus = o->n_cus;
+    n->stream = o->stream;                                    // (not owned: the handle keeps its streams)
+    n->flags = o->staged_auto ? (o->flags & ~GBP_FLAG_NO_FUSED) : o->flags;     // the flags of create, before the sparseness rule added NO_FUSED
+    Params &p = n->p;
+    p = Params{};
+    p.F = F; p.L = L; p.C = C; p.T = 0;
+    p.K = op.K; p.sigma2 = op.sigma2; p.nstds = op.nstds; p.beta = op.beta; p.eta_damping = op.eta_damping;
+    p.num_undamped = op.num_undamped; p.min_linear = op.min_linear; p.loss = op.loss;
+    p.robustify = 0; p.local_relin = 1;
+    p.crow = op.num_undamped == 0 ? CSTAGE_ROW : CSTAGE_PLAIN;
+    p.clk = op.clk; p.clk_inc = 0;                             // factors the build makes are stamped iters_since_relin = 1 against the handle's clock
+    p.reverse_walk = op.reverse_walk;
+}
+
+// the counters of the old handle that are part of its state: relinearisation-count ring, sweep count, walk parities, the remainder's watch
+inline int graft_counters(const gbp_ba *o, gbp_ba *n)
+{
+    HIPCHK(hipMemcpyAsync(n->d_relin_ring, o->d_relin_ring, sizeof(int) * (size_t)RELIN_RING * RELIN_LANES, hipMemcpyDeviceToDevice, n->stream));
+    n->sweep_count = o->sweep_count; n->walk_parity = o->walk_parity; n->gen_parity = o->gen_parity;
+    n->pending_possible = o->pending_possible; n->lazy_since = o->lazy_since;
+    return GBP_OK;
+}
+
+// a failed build: the half-built graph goes, the message stays (as gbp_ba_create does)
+inline int graft_abandon(gbp_ba *n, int rc)
+{
+    n->stream = nullptr;                                      // (the stream is the old handle's)
+    const std::string keep = gbp_last_error();
+    gbp_ba_destroy(n);
+    return fail(rc, "%s", keep.c_str());
+}
+
+// The new graph `n` becomes the handle `h`.  What the handle keeps: its streams, timing settings and instrumentation buffers (the rest
+// of it is the new graph's now); the old graph is destroyed.
+inline void graft_swap(gbp_ba *h, gbp_ba *n)
+{
+    std::swap(n->own_stream, h->own_stream);
+    std::swap(n->timing, h->timing); std::swap(n->timing_every, h->timing_every); std::swap(n->timing_tick, h->timing_tick);
+    std::swap(n->ev, h->ev); std::swap(n->ev_used, h->ev_used);
+    std::swap(n->clk_used, h->clk_used); std::swap(n->clk_rate_khz, h->clk_rate_khz);
+    std::swap(n->clk_calibrated, h->clk_calibrated); std::swap(n->clk_rate_khz_measured, h->clk_rate_khz_measured);
+    std::swap(n->side_stream, h->side_stream); std::swap(n->ev_fork, h->ev_fork); std::swap(n->ev_join, h->ev_join);
+    if (h->d_clk) {
+        h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), static_cast<void *>(h->d_clk)), h->allocs.end());
+        n->allocs.push_back(h->d_clk);
+        n->d_clk = h->d_clk; h->d_clk = nullptr;
+    }
+    std::swap(*h, *n);                                        // h: the new graph; n: what is left of the old handle
+    h->fused.alloc_ctx = h;
+    n->stream = h->stream;                                    // (synchronised by destroy, not destroyed: own_stream went over)
+    gbp_ba_destroy(n);
+}
+
+}  // namespace gbp

@@ -139,6 +139,18 @@ class BAEngine:
         self.C, self.L, self.F = self.C + dC, self.L + dL, self.F + dF
         return o2n
 
+    # ---- shrinking (include/gbp_ba.h: gbp_ba_retire) ----------------------------------------------
+    def retire(self, cam_ids):
+        """Retire cameras (the old keyframes of a fixed-lag window): their factors' messages to the landmarks are folded into the landmarks'
+        priors, the cameras, their factors and every landmark left without a factor are removed and the survivors are renumbered compactly
+        with all their solver state.  Returns (cam_map, lmk_map, factor_map): int32, one entry per OLD camera / landmark / factor, its new
+        id or -1 when it is gone."""
+        ids = i32(np.asarray(cam_ids, dtype=np.int64).reshape(-1))
+        cm, lm, fm = np.empty(self.C, np.int32), np.empty(self.L, np.int32), np.empty(self.F, np.int32)
+        check(self._lib.gbp_ba_retire(self._h, ids.size, iptr(ids) if ids.size else None, iptr(cm), iptr(lm), iptr(fm)))
+        self.C, self.L, self.F = int((cm >= 0).sum()), int((lm >= 0).sum()), int((fm >= 0).sum())
+        return cm, lm, fm
+
     @classmethod
     def from_problem(cls, p, **kw):
         return cls(p.K, p.cam_means, p.lmk_means, p.meas, p.cam_idx, p.lmk_idx, **kw)

@@ -116,6 +116,35 @@ typedef struct gbp_ba_ext {
 } gbp_ba_ext_t;
 int gbp_ba_extend(gbp_ba_t *h, const gbp_ba_ext_t *ext, int32_t *old_to_new);
 
+/* shrinking: retire cameras (old keyframes of a fixed-lag window) from a live handle without losing the solver state of what stays.
+ * GBP's own marginalisation, not an exact Schur complement: a factor belongs to exactly one camera, so retiring camera c removes all of
+ * c's factors, the only surviving neighbours of those factors are landmarks, and camera priors never change.  After gbp_ba_retire the
+ * handle is exactly what the reference's object graph is after
+ *   1. fold: for every factor f of a retired camera, with l its landmark, l.prior.eta += f.messages[1].eta and l.prior.lam +=
+ *      f.messages[1].lam -- the full message as gbp_ba_get_messages reports it now (the dense remainder's landmark part included when
+ *      the handle carries one), added in the landmark's adj_factors order; f leaves l.adj_factors and graph.factors;
+ *   2. drop: the retired cameras go, and with them every landmark left without a factor (an orphan);
+ *   3. renumber: survivors keep their relative order; cameras, landmarks and factors are renumbered compactly, new id = old id - number
+ *      of removed ids below it.  The factor order is still the reference's camera-major order, inside a landmark the old order.  The
+ *      three output maps (cam_old_to_new[C], lmk_old_to_new[L], factor_old_to_new[F], sizes BEFORE the call, NULL to skip) carry -1 for
+ *      what is gone;
+ *   4. every surviving factor keeps its linearisation point, measurement, both messages, adaptive variance, robust, damped and pending
+ *      bits, relinearisation age (against the same clock) and dense remainder;
+ *   5. every surviving camera keeps its prior, every surviving landmark its prior plus what step 1 folded in;
+ *   6. update_all_beliefs runs: surviving beliefs are unchanged up to summation order;
+ *   7. as gbp_ba_extend step 7: the handle keeps its stream, overrides, create flags, timing settings, clock, walk parity, sweep count
+ *      and relinearisation-count ring; the sweep's plan is chosen for the survivors exactly as gbp_ba_create would choose it (a graph
+ *      that has shrunk enough moves from the general sweep to camera windows or the fused sweep);
+ *   8. dropped, as gbp_ba_extend step 8: the device snapshot slot and the streaming-means mirrors.
+ * Errors leave the handle untouched (the survivors' graph is built beside it and swapped in last): GBP_ESTATE for a handle with a
+ * communicator, an exchange callback or a peer mailbox, or without beliefs yet; GBP_EINVAL for ids out of range or repeated, a negative
+ * count, a NULL list with a non-zero count, or a set that leaves no factor; GBP_ENOMEM when the survivors' graph does not fit -- peak
+ * device memory is the old handle's plus the survivors'.  An empty list succeeds and changes nothing.
+ * Out of scope: sharded handles; retiring landmarks by name (the symmetric fold into camera priors); exact (Schur) marginalisation with
+ * camera-camera fill-in; keeping orphan landmarks. */
+int gbp_ba_retire(gbp_ba_t *h, int32_t n_cams, const int32_t *cam_ids, int32_t *cam_old_to_new, int32_t *lmk_old_to_new,
+                  int32_t *factor_old_to_new);
+
 /* priors */
 int gbp_ba_generate_priors(gbp_ba_t *h, double weaker_factor);          /* BAFactorGraph.generate_priors_var gbp_ba.py:20-34 */
 int gbp_ba_factor_lambda_max(gbp_ba_t *h, double *cam_max, double *lmk_max);  /* the max_f max(Lambda_f) half of it (sharded set-up) */
