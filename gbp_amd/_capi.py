@@ -18,6 +18,7 @@ ABI_VERSION = 3
 FLAG_NO_FUSED = 1
 FLAG_DEVICE_INPUT = 2
 FLAG_FORCE_FUSED = 4
+FLAG_REORDER_LMKS = 8
 PLAN_INFO_FIELDS = 11
 CAM_PARTIAL_DOUBLES = 27
 COMM_ID_BYTES = 128
@@ -137,6 +138,7 @@ SIGNATURES = {
     'gbp_lin_get_beliefs': (ct.c_int, [ct.c_void_p, _dp, _dp]),
     'gbp_lin_get_means': (ct.c_int, [ct.c_void_p, _dp]),
     'gbp_lin_get_messages': (ct.c_int, [ct.c_void_p, _dp, _dp, _dp, _dp]),
+    'gbp_ba_get_lmk_order': (ct.c_int, [ct.c_void_p, _ip]),
     'gbp_ba_fused_max_cams': (ct.c_int, []),
     'gbp_ba_plan_info': (ct.c_int, [ct.c_void_p, _ip, ct.c_int32]),
     'gbp_ba_phase_profile': (ct.c_int, [ct.c_void_p, ct.c_void_p, ct.c_int32, ct.POINTER(ct.c_int32), ct.POINTER(ct.c_int32)]),

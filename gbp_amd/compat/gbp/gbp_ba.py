@@ -249,7 +249,8 @@ class BAFactorGraph:
             problem, gauss_noise_std=float(configs['gauss_noise_std']), loss=configs.get('loss'),
             Nstds=float(configs.get('Nstds', 3.0)), beta=float(configs['beta']),
             num_undamped_iters=int(configs['num_undamped_iters']), min_linear_iters=int(configs['min_linear_iters']),
-            eta_damping=float(configs['eta_damping']), device=device)
+            eta_damping=float(configs['eta_damping']), device=device,
+            reorder_landmarks=bool(configs.get('reorder_landmarks', False)))
         self._C, self._L, self._F = problem.n_cams, problem.n_lmks, problem.n_factors
         self._K = np.array([[problem.K[0], 0.0, problem.K[2]], [0.0, problem.K[1], problem.K[3]], [0.0, 0.0, 1.0]])
         order = reference_factor_order(problem.cam_idx)

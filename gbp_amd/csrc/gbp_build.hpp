@@ -6,6 +6,8 @@
 //   1. k_check_ids            ids inside [0,C) x [0,L)?  camera ids already non-decreasing (every shipped file is)?
 //   2. sort_pairs             stable by camera      -> reference factor r = file row ref_file[r]       (skipped when sorted)
 //      k_lower_bounds         camera CSR offsets cptr
+//   2b. (GBP_FLAG_REORDER_LMKS) k_lmk_stats, k_lmk_class_keys, sort_pairs, k_lmk_spread_keys, sort_pairs, k_lmk_relabel_vars: internal
+//                             landmark numbers by camera locality (the rule: gbp_policy.hpp); from here on the relabelled problem
 //   3. sort_pairs             stable by landmark    -> landmark-major list lm2ref (adj_factors order), offsets lptr
 //   4. tile packing           next-fit over the landmark degrees (64 slots / 24 landmarks per tile, landmarks above 64 factors
 //                             cut into chunk tiles).  Next-fit is a chain -- where a tile starts depends on where the previous one
@@ -25,6 +27,7 @@
 // after the observations themselves went up.
 #pragma once
 #include "gbp_kernels.hpp"
+#include "gbp_policy.hpp"
 
 namespace gbp {
 
@@ -66,6 +69,59 @@ __global__ __launch_bounds__(BLOCK) void k_lower_bounds(const int *__restrict__ 
         if (keys[mid] < v) lo = mid + 1; else hi = mid;
     }
     ptr[v] = lo;
+}
+
+// ---- landmark order (GBP_FLAG_REORDER_LMKS; the rule: gbp_policy.hpp) --------------------------------------------------------
+// Between the reference order and the landmark-major sort: the landmarks get internal numbers by camera locality and the rest of the
+// build runs on the relabelled problem.  Integer atomics only (degree, lowest and highest camera), two stable sorts: deterministic.
+struct LmkStats { int *deg, *lo, *hi; };          // per landmark; lo starts at INT_MAX, deg and hi at 0 / -1
+
+__global__ __launch_bounds__(BLOCK) void k_lmk_stats(const int *__restrict__ ref_cam, const int *__restrict__ ref_lmk, int F, LmkStats s)
+{
+    const int r = blockIdx.x * BLOCK + threadIdx.x;
+    if (r >= F) return;
+    const int c = ref_cam[r], l = ref_lmk[r];
+    atomicAdd(&s.deg[l], 1);
+    atomicMin(&s.lo[l], c);
+    atomicMax(&s.hi[l], c);
+}
+
+// key[l] = reorder_class_key; counts = {local landmarks, wide landmarks}
+__global__ __launch_bounds__(BLOCK) void k_lmk_class_keys(LmkStats s, int L, int C, int *__restrict__ key, int *__restrict__ counts)
+{
+    const int l = blockIdx.x * BLOCK + threadIdx.x;
+    const int k = l < L ? reorder_class_key(s.deg[l], s.lo[l], s.hi[l], C) : C + 1;
+    if (l < L) key[l] = k;
+    const unsigned long long local = __ballot(k < C), wide = __ballot(k == C);
+    if ((threadIdx.x & 63) == 0) {
+        if (local) atomicAdd(&counts[0], __popcll(local));
+        if (wide) atomicAdd(&counts[1], __popcll(wide));
+    }
+}
+
+// key[pos] = reorder_spread_key of position pos in the order of the first sort
+__global__ __launch_bounds__(BLOCK) void k_lmk_spread_keys(const int *__restrict__ counts, int L, int *__restrict__ key)
+{
+    const int pos = blockIdx.x * BLOCK + threadIdx.x;
+    if (pos < L) key[pos] = reorder_spread_key(pos, counts[0], counts[1]);
+}
+
+// user_of_internal -> internal_of_user, and the landmark means in internal numbering
+__global__ __launch_bounds__(BLOCK) void k_lmk_relabel_vars(const int *__restrict__ i2u, int L, int *__restrict__ u2i, const double *__restrict__ means_user,
+                                                            double *__restrict__ means_internal)
+{
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= L) return;
+    const int u = i2u[i];
+    u2i[u] = i;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) means_internal[(size_t)i * 3 + k] = means_user[(size_t)u * 3 + k];
+}
+
+__global__ __launch_bounds__(BLOCK) void k_map_int_inplace(int *__restrict__ a, const int *__restrict__ map, int n)
+{
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i < n) a[i] = map[a[i]];
 }
 
 // ---- tile packing as list ranking ------------------------------------------------------------------------------------------
@@ -400,9 +456,11 @@ __global__ __launch_bounds__(BLOCK) void k_cam_max(Params p, const double *__res
 }
 
 // prior Lambda = (lambda / w2) I, eta = Lambda mu   (gbp_ba.py:32-34; w2 = weaker_factor^2, 1 when the caller gives Lambda), on cameras
-// [c0, c1) and landmarks [l0, l1) (all of them but after gbp_ba_extend, which sets the new variables' priors alone)
+// [c0, c1) and landmarks [l0, l1) (all of them but after gbp_ba_extend, which sets the new variables' priors alone).  Landmarks are
+// walked, and the range is meant, in the CALLER's numbering: lmk_map (NULL: identity) turns it into the internal one, and lmk_lambda is
+// indexed by the caller's id (lambda_by_user: scalars that came in from outside) or by the internal one (the maxima of k_lmk_max).
 __global__ __launch_bounds__(BLOCK) void k_prior_scalars(Params p, const double *__restrict__ cam_lambda, const double *__restrict__ lmk_lambda,
-                                                         double w2, int c0, int c1, int l0, int l1)
+                                                         double w2, int c0, int c1, int l0, int l1, const int *__restrict__ lmk_map, int lambda_by_user)
 {
     const int v = blockIdx.x * BLOCK + threadIdx.x;
     if (v < p.C ? (v < c0 || v >= c1) : (v - p.C < l0 || v - p.C >= l1)) return;
@@ -414,8 +472,8 @@ __global__ __launch_bounds__(BLOCK) void k_prior_scalars(Params p, const double 
 #pragma unroll
         for (int k = 0; k < 6; ++k) { pr[k] = lam * p.cbel[(size_t)v * CAMREC + CAM_MU + k]; pr[6 + Sym<6>::at(k, k)] = lam; }
     } else if (v < p.C + p.L) {
-        const int l = v - p.C;
-        const double lam = lmk_lambda[l] / w2;
+        const int u = v - p.C, l = lmk_map ? lmk_map[u] : u;
+        const double lam = lmk_lambda[lambda_by_user ? u : l] / w2;
         double *lr = p.lrec + (size_t)l * LREC;
 #pragma unroll
         for (int k = 0; k < 9; ++k) lr[LR_PRIOR + k] = 0.0;
@@ -424,11 +482,13 @@ __global__ __launch_bounds__(BLOCK) void k_prior_scalars(Params p, const double 
     }
 }
 
-// packed landmark priors (eta 3 | Lambda 6) into the landmark records
-__global__ __launch_bounds__(BLOCK) void k_scatter_lmk_priors(Params p, const double *__restrict__ pri)
+// packed landmark priors (eta 3 | Lambda 6), in the caller's numbering, into the landmark records (lmk_map: caller's id -> internal, NULL: identity)
+__global__ __launch_bounds__(BLOCK) void k_scatter_lmk_priors(Params p, const double *__restrict__ pri, const int *__restrict__ lmk_map)
 {
     const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i < (size_t)p.L * 9) p.lrec[(i / 9) * LREC + LR_PRIOR + (i % 9)] = pri[i];
+    if (i >= (size_t)p.L * 9) return;
+    const size_t u = i / 9, l = lmk_map ? (size_t)lmk_map[u] : u;
+    p.lrec[l * LREC + LR_PRIOR + (i % 9)] = pri[i];
 }
 
 // order-independent 64-bit digest of the factor layout (reference id -> slot, camera, landmark): pins a state blob to its graph

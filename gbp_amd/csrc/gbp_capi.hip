@@ -157,6 +157,45 @@ int gbp::build_graph(gbp_ba *h, const gbp_ba_desc_t *d, std::vector<void *> &scr
     }
     if (ref_file_out) *ref_file_out = ref_file;
     hipLaunchKernelGGL(k_lower_bounds, dim3(grid_for((size_t)C + 1)), dim3(BLOCK), 0, h->stream, h->d_ref_cam, F, cptr, C);
+    // 2b. GBP_FLAG_REORDER_LMKS: internal landmark numbers by camera locality (the rule: gbp_policy.hpp; kernels: gbp_build.hpp).  From here
+    //     on d_ref_lmk and lmk_means are in internal numbering and the build is that of the relabelled problem; the two maps stay with
+    //     the handle for its landmark-indexed boundaries.
+    h->d_lmk_u2i = h->d_lmk_i2u = nullptr; h->lmk_u2i.clear();
+    if ((h->flags & GBP_FLAG_REORDER_LMKS) && L > 0) {
+        if (L >= (1 << 30)) return fail(GBP_EINVAL, "GBP_FLAG_REORDER_LMKS supports fewer than 2^30 landmarks");
+        const size_t Lz = (size_t)L;
+        LmkStats st{};
+        int *key = nullptr, *key_sorted = nullptr, *l_iota = nullptr, *first = nullptr, *counts = nullptr;
+        double *means_int = nullptr;
+        CHK(scratch_alloc(h, scratch, &st.deg, Lz)); CHK(scratch_alloc(h, scratch, &st.lo, Lz)); CHK(scratch_alloc(h, scratch, &st.hi, Lz));
+        CHK(scratch_alloc(h, scratch, &key, Lz)); CHK(scratch_alloc(h, scratch, &key_sorted, Lz)); CHK(scratch_alloc(h, scratch, &l_iota, Lz));
+        CHK(scratch_alloc(h, scratch, &first, Lz)); CHK(scratch_alloc(h, scratch, &counts, 2)); CHK(scratch_alloc(h, scratch, &means_int, Lz * 3));
+        CHK(dev_alloc(h, &h->d_lmk_u2i, Lz, false)); CHK(dev_alloc(h, &h->d_lmk_i2u, Lz, false));
+        HIPCHK(hipMemsetAsync(st.deg, 0, Lz * sizeof(int), h->stream));
+        HIPCHK(hipMemsetAsync(st.lo, 0x7f, Lz * sizeof(int), h->stream));      // 0x7f7f7f7f: above every camera id
+        HIPCHK(hipMemsetAsync(st.hi, 0xff, Lz * sizeof(int), h->stream));      // -1
+        HIPCHK(hipMemsetAsync(counts, 0, 2 * sizeof(int), h->stream));
+        int bits_k1 = 1, bits_k2 = 1;
+        while ((1ll << bits_k1) < (long long)C + 2) ++bits_k1;
+        while ((1ll << bits_k2) < 2ll * L + 3) ++bits_k2;
+        const size_t lsort_bytes = std::max(sort_pairs_tmp_bytes(Lz, bits_k1), sort_pairs_tmp_bytes(Lz, bits_k2));
+        void *lsort_tmp = nullptr;
+        HIPCHK(hipMallocAsync(&lsort_tmp, std::max<size_t>(lsort_bytes, 1), h->stream)); scratch.push_back(lsort_tmp);
+        if (F) hipLaunchKernelGGL(k_lmk_stats, dim3(grid_for(Fz)), dim3(BLOCK), 0, h->stream, h->d_ref_cam, h->d_ref_lmk, F, st);
+        hipLaunchKernelGGL(k_lmk_class_keys, dim3(grid_for(Lz)), dim3(BLOCK), 0, h->stream, st, L, C, key, counts);
+        hipLaunchKernelGGL(k_iota, dim3(grid_for(Lz)), dim3(BLOCK), 0, h->stream, l_iota, L);
+        HIPCHK(hipGetLastError());
+        HIPCHK((hipError_t)sort_pairs(lsort_tmp, lsort_bytes, key, key_sorted, l_iota, first, Lz, bits_k1, h->stream));
+        hipLaunchKernelGGL(k_lmk_spread_keys, dim3(grid_for(Lz)), dim3(BLOCK), 0, h->stream, counts, L, key);
+        HIPCHK(hipGetLastError());
+        HIPCHK((hipError_t)sort_pairs(lsort_tmp, lsort_bytes, key, key_sorted, first, h->d_lmk_i2u, Lz, bits_k2, h->stream));
+        hipLaunchKernelGGL(k_lmk_relabel_vars, dim3(grid_for(Lz)), dim3(BLOCK), 0, h->stream, h->d_lmk_i2u, L, h->d_lmk_u2i, lmk_means, means_int);
+        if (F) hipLaunchKernelGGL(k_map_int_inplace, dim3(grid_for(Fz)), dim3(BLOCK), 0, h->stream, h->d_ref_lmk, h->d_lmk_u2i, F);
+        HIPCHK(hipGetLastError());
+        lmk_means = means_int;
+        CHK(download(h, h->lmk_u2i, h->d_lmk_u2i, Lz));
+        clk.mark("landmark order");
+    }
     // 3. landmark-major, stable in reference id (= VariableNode.adj_factors order, gbp_ba.py:139)
     if (F) HIPCHK((hipError_t)sort_pairs(sort_tmp, sort_bytes, h->d_ref_lmk, lm_key, iota, lm2ref, Fz, bits_l, h->stream));
     hipLaunchKernelGGL(k_lower_bounds, dim3(grid_for((size_t)L + 1)), dim3(BLOCK), 0, h->stream, lm_key, F, lptr, L);
@@ -445,8 +484,13 @@ int gbp_ba_factor_lambda_max(gbp_ba_t *h, double *cam_max, double *lmk_max)
     const Params &p = h->p;
     CHK(variable_lambda_max(h));
     if (cam_max && p.C) HIPCHK(hipMemcpyAsync(cam_max, h->d_varmax, sizeof(double) * (size_t)p.C, hipMemcpyDeviceToHost, h->stream));
-    if (lmk_max && p.L) HIPCHK(hipMemcpyAsync(lmk_max, h->d_varmax + p.C, sizeof(double) * (size_t)p.L, hipMemcpyDeviceToHost, h->stream));
+    if (lmk_max && p.L && h->lmk_u2i.empty()) HIPCHK(hipMemcpyAsync(lmk_max, h->d_varmax + p.C, sizeof(double) * (size_t)p.L, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
+    if (lmk_max && p.L && !h->lmk_u2i.empty()) {           // d_varmax is in internal numbering
+        std::vector<double> m;
+        CHK(download(h, m, h->d_varmax + p.C, (size_t)p.L));
+        for (int l = 0; l < p.L; ++l) lmk_max[l] = m[(size_t)h->lmk_u2i[(size_t)l]];
+    }
     return GBP_OK;
 }
 
@@ -459,7 +503,7 @@ int gbp_ba_set_prior_scalars(gbp_ba_t *h, const double *cam_lambda, const double
     if (p.C) HIPCHK(hipMemcpyAsync(h->d_varmax, cam_lambda, sizeof(double) * (size_t)p.C, hipMemcpyHostToDevice, h->stream));
     if (p.L) HIPCHK(hipMemcpyAsync(h->d_varmax + p.C, lmk_lambda, sizeof(double) * (size_t)p.L, hipMemcpyHostToDevice, h->stream));
     if (p.C + p.L) hipLaunchKernelGGL(k_prior_scalars, dim3(grid_for((size_t)p.C + p.L)), dim3(BLOCK), 0, h->stream, p, h->d_varmax, h->d_varmax + p.C, 1.0,
-                                      0, p.C, 0, p.L);
+                                      0, p.C, 0, p.L, h->d_lmk_u2i, 1);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));               // the arrays are the caller's
     return GBP_OK;
@@ -473,7 +517,7 @@ int gbp_ba_generate_priors(gbp_ba_t *h, double weaker_factor)
     const Params &p = h->p;
     CHK(variable_lambda_max(h));                           // nothing F-sized leaves the device
     if (p.C + p.L) hipLaunchKernelGGL(k_prior_scalars, dim3(grid_for((size_t)p.C + p.L)), dim3(BLOCK), 0, h->stream, p, h->d_varmax,
-                                      h->d_varmax + p.C, weaker_factor * weaker_factor, 0, p.C, 0, p.L);
+                                      h->d_varmax + p.C, weaker_factor * weaker_factor, 0, p.C, 0, p.L, h->d_lmk_u2i, 0);
     HIPCHK(hipGetLastError());
     return GBP_OK;
 }
@@ -500,7 +544,7 @@ int gbp_ba_set_priors(gbp_ba_t *h, const double *cam_eta, const double *cam_lam,
     CHK(upload(h, p.cprior, cp));
     CHK(ensure_tmp(h, sizeof(double) * lp.size()));
     CHK(upload(h, h->d_tmp, lp));
-    if (p.L) hipLaunchKernelGGL(k_scatter_lmk_priors, dim3(grid_for((size_t)p.L * 9)), dim3(BLOCK), 0, h->stream, p, h->d_tmp);
+    if (p.L) hipLaunchKernelGGL(k_scatter_lmk_priors, dim3(grid_for((size_t)p.L * 9)), dim3(BLOCK), 0, h->stream, p, h->d_tmp, h->d_lmk_u2i);
     HIPCHK(hipGetLastError());
     return GBP_OK;
 }
@@ -560,6 +604,13 @@ int gbp_ba_check_layout(gbp_ba_t *h, int32_t *bad_slots)
     return GBP_OK;
 }
 
+int gbp_ba_get_lmk_order(gbp_ba_t *h, int32_t *internal_of_user)
+{
+    if (!h || (h->p.L > 0 && !internal_of_user)) return fail(GBP_EINVAL, "null argument");
+    for (int l = 0; l < h->p.L; ++l) internal_of_user[l] = h->lmk_u2i.empty() ? l : h->lmk_u2i[(size_t)l];
+    return (h->flags & GBP_FLAG_REORDER_LMKS) ? 1 : 0;
+}
+
 int gbp_ba_fused_max_cams(void)
 {
     return fused_max_cams();
@@ -604,15 +655,16 @@ int gbp::variable_lambda_max(gbp_ba *h)
     return GBP_OK;
 }
 
-// prior Lambda = (lambda / w2) I, eta = Lambda mu on cameras [c0, C) and landmarks [l0, L) only, lambda from d_varmax (gbp_ba_extend: the NEW
-// variables; w2 = weaker_factor^2 for the rule, 1 for given scalars)
-int gbp::prior_scalars_range(gbp_ba *h, int c0, int l0, double w2_cam, double w2_lmk)
+// prior Lambda = (lambda / w2) I, eta = Lambda mu on cameras [c0, C) and landmarks [l0, L) (the caller's ids) only, lambda from d_varmax
+// (gbp_ba_extend: the NEW variables; w2 = weaker_factor^2 for the rule, 1 for given scalars).  The landmark half of d_varmax is indexed
+// by the caller's id when it came from outside (lmk_lambda_by_user), by the internal one when variable_lambda_max wrote it.
+int gbp::prior_scalars_range(gbp_ba *h, int c0, int l0, double w2_cam, double w2_lmk, bool lmk_lambda_by_user)
 {
     const Params &p = h->p;
     if (p.C > c0) hipLaunchKernelGGL(k_prior_scalars, dim3(grid_for((size_t)p.C)), dim3(BLOCK), 0, h->stream, p, h->d_varmax, h->d_varmax + p.C, w2_cam,
-                                     c0, p.C, p.L, p.L);
+                                     c0, p.C, p.L, p.L, nullptr, 0);
     if (p.L > l0) hipLaunchKernelGGL(k_prior_scalars, dim3(grid_for((size_t)p.C + p.L)), dim3(BLOCK), 0, h->stream, p, h->d_varmax, h->d_varmax + p.C,
-                                     w2_lmk, p.C, p.C, l0, p.L);
+                                     w2_lmk, p.C, p.C, l0, p.L, h->d_lmk_u2i, lmk_lambda_by_user ? 1 : 0);
     HIPCHK(hipGetLastError());
     return GBP_OK;
 }
@@ -629,6 +681,7 @@ int gbp::graph_hash(gbp_ba *h, uint64_t *out)
         unsigned long long v = 0;
         HIPCHK(hipMemcpyAsync(&v, d, sizeof v, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
+        if (h->flags & GBP_FLAG_REORDER_LMKS) v ^= 0x4c4d4b4f52444552ull;      // a reordered handle's blob holds its records in its own order
         h->hash = v; h->hash_ok = true;
     }
     *out = h->hash;

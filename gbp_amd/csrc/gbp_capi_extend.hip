@@ -11,8 +11,9 @@
 
 namespace {
 
-// the union's factor arrays in file order: the old factors in reference order (measurement = the z rows of their slot), then the batch
-__global__ __launch_bounds__(BLOCK) void k_union_factors(Params o, const int *__restrict__ ref_cam, const int *__restrict__ ref_lmk,
+// the union's factor arrays in file order: the old factors in reference order (measurement = the z rows of their slot), then the batch.
+// Landmark ids go out in the caller's numbering: o_i2u (NULL: identity) turns a reordered handle's internal ids back.
+__global__ __launch_bounds__(BLOCK) void k_union_factors(Params o, const int *__restrict__ ref_cam, const int *__restrict__ ref_lmk, const int *__restrict__ o_i2u,
                                                          const double *__restrict__ bmeas, const int *__restrict__ bcam, const int *__restrict__ blmk,
                                                          int n_new, double *__restrict__ meas, int *__restrict__ cam, int *__restrict__ lmk)
 {
@@ -22,7 +23,7 @@ __global__ __launch_bounds__(BLOCK) void k_union_factors(Params o, const int *__
         meas[(size_t)i * 2] = o.lin[lin_at(s, ROW_Z)];
         meas[(size_t)i * 2 + 1] = o.lin[lin_at(s, ROW_Z + 1)];
         cam[i] = ref_cam[i];
-        lmk[i] = ref_lmk[i];
+        lmk[i] = o_i2u ? o_i2u[ref_lmk[i]] : ref_lmk[i];
     } else if (i < o.F + n_new) {
         const int j = i - o.F;
         meas[(size_t)i * 2] = bmeas[(size_t)j * 2];
@@ -32,8 +33,9 @@ __global__ __launch_bounds__(BLOCK) void k_union_factors(Params o, const int *__
     }
 }
 
-// the union's initial means: the old variables' current belief means (node.mu), then the batch's
-__global__ __launch_bounds__(BLOCK) void k_union_means(Params o, const double *__restrict__ bcam, const double *__restrict__ blmk, int dC, int dL,
+// the union's initial means: the old variables' current belief means (node.mu), then the batch's (o_u2i: caller's landmark id -> the old
+// handle's record, NULL: identity)
+__global__ __launch_bounds__(BLOCK) void k_union_means(Params o, const int *__restrict__ o_u2i, const double *__restrict__ bcam, const double *__restrict__ blmk, int dC, int dL,
                                                        double *__restrict__ cam_means, double *__restrict__ lmk_means)
 {
     const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
@@ -43,7 +45,7 @@ __global__ __launch_bounds__(BLOCK) void k_union_means(Params o, const double *_
         cam_means[i] = c < (size_t)o.C ? o.cbel[c * CAMREC + CAM_MU + k] : bcam[i - (size_t)o.C * 6];
     } else if (i < nc + nl) {
         const size_t j = i - nc, l = j / 3, k = j % 3;
-        lmk_means[j] = l < (size_t)o.L ? o.lrec[l * LREC + LR_MU + k] : blmk[j - (size_t)o.L * 3];
+        lmk_means[j] = l < (size_t)o.L ? o.lrec[(o_u2i ? (size_t)o_u2i[l] : l) * LREC + LR_MU + k] : blmk[j - (size_t)o.L * 3];
     }
 }
 
@@ -65,12 +67,13 @@ __global__ __launch_bounds__(BLOCK) void k_transplant_slots(Params n, Params o, 
 }
 
 // per-variable state of the old variables: camera records, belief views and priors; landmark mean | covariance and prior (the slot range
-// of a landmark record is the new layout's)
-__global__ __launch_bounds__(BLOCK) void k_transplant_vars(Params n, Params o)
+// of a landmark record is the new layout's).  A landmark keeps its id in the caller's numbering; on a reordered handle its record moves
+// old internal -> caller's -> new internal (o_u2i, n_u2i; NULL: identity).
+__global__ __launch_bounds__(BLOCK) void k_transplant_vars(Params n, Params o, const int *__restrict__ n_u2i, const int *__restrict__ o_u2i)
 {
     const int v = blockIdx.x * BLOCK + threadIdx.x;
     if (v < o.C) transplant_cam(n, o, v, v);
-    else if (v < o.C + o.L) transplant_lmk(n, o, v - o.C, v - o.C);
+    else if (v < o.C + o.L) { const int u = v - o.C; transplant_lmk(n, o, n_u2i ? n_u2i[u] : u, o_u2i ? o_u2i[u] : u); }
 }
 
 // the union built beside the old handle `o` into the fresh handle `n` (which owns nothing of o's)
@@ -93,10 +96,10 @@ int extend_into(gbp_ba *o, gbp_ba *n, const gbp_ba_ext_t *e, std::vector<void *>
     int *u_cam = nullptr, *u_lmk = nullptr;
     CHK(graft_scratch(n, scratch, &u_meas, (size_t)F * 2)); CHK(graft_scratch(n, scratch, &u_cam, (size_t)F)); CHK(graft_scratch(n, scratch, &u_lmk, (size_t)F));
     CHK(graft_scratch(n, scratch, &u_cm, (size_t)C * 6)); CHK(graft_scratch(n, scratch, &u_lm, (size_t)L * 3));
-    if (F) hipLaunchKernelGGL(k_union_factors, dim3(grid_for((size_t)F)), dim3(BLOCK), 0, n->stream, op, o->d_ref_cam, o->d_ref_lmk, bmeas, bcam, blmk, dF,
+    if (F) hipLaunchKernelGGL(k_union_factors, dim3(grid_for((size_t)F)), dim3(BLOCK), 0, n->stream, op, o->d_ref_cam, o->d_ref_lmk, o->d_lmk_i2u, bmeas, bcam, blmk, dF,
                               u_meas, u_cam, u_lmk);
     const size_t nv = (size_t)C * 6 + (size_t)L * 3;
-    if (nv) hipLaunchKernelGGL(k_union_means, dim3(grid_for(nv)), dim3(BLOCK), 0, n->stream, op, bcm, blm, dC, dL, u_cm, u_lm);
+    if (nv) hipLaunchKernelGGL(k_union_means, dim3(grid_for(nv)), dim3(BLOCK), 0, n->stream, op, o->d_lmk_u2i, bcm, blm, dC, dL, u_cm, u_lm);
     HIPCHK(hipGetLastError());
 
     // 2. the union's graph by the create path (ids are checked there: out of range -> GBP_EINVAL)
@@ -115,7 +118,7 @@ int extend_into(gbp_ba *o, gbp_ba *n, const gbp_ba_ext_t *e, std::vector<void *>
     CHK(graft_scratch(n, scratch, &d_o2n, (size_t)op.F));
     const size_t S = n_slots(n);
     if (p.T && op.F) hipLaunchKernelGGL(k_transplant_slots, dim3(grid_for(S)), dim3(BLOCK), 0, n->stream, p, op, ref_file, d_o2n);
-    if (op.C + op.L) hipLaunchKernelGGL(k_transplant_vars, dim3(grid_for((size_t)op.C + op.L)), dim3(BLOCK), 0, n->stream, p, op);
+    if (op.C + op.L) hipLaunchKernelGGL(k_transplant_vars, dim3(grid_for((size_t)op.C + op.L)), dim3(BLOCK), 0, n->stream, p, op, n->d_lmk_u2i, o->d_lmk_u2i);
     HIPCHK(hipGetLastError());
     CHK(graft_counters(o, n));
 
@@ -131,7 +134,8 @@ int extend_into(gbp_ba *o, gbp_ba *n, const gbp_ba_ext_t *e, std::vector<void *>
         HIPCHK(hipMemcpyAsync(n->d_varmax + op.C, e->cam_prior_lambda, sizeof(double) * (size_t)dC, hipMemcpyHostToDevice, n->stream));
     if (dL && e->lmk_prior_lambda)
         HIPCHK(hipMemcpyAsync(n->d_varmax + C + op.L, e->lmk_prior_lambda, sizeof(double) * (size_t)dL, hipMemcpyHostToDevice, n->stream));
-    CHK(prior_scalars_range(n, op.C, op.L, e->cam_prior_lambda || !rule ? 1.0 : wf * wf, e->lmk_prior_lambda || !rule ? 1.0 : wf * wf));
+    CHK(prior_scalars_range(n, op.C, op.L, e->cam_prior_lambda || !rule ? 1.0 : wf * wf, e->lmk_prior_lambda || !rule ? 1.0 : wf * wf,
+                            e->lmk_prior_lambda || !rule));
 
     // 6. update_all_beliefs over the union
     CHK(gbp_ba_update_beliefs(n));

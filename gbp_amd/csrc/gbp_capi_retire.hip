@@ -15,15 +15,17 @@ namespace {
 
 // keep[0 .. C): the camera stays; keep[C .. C+L): the landmark has a surviving factor; keep[C+L .. C+L+F): the factor (old reference
 // order) stays; keep[C+L+F] = 0, so that the exclusive scan behind it ends with the total.  One scan over all of it gives the three
-// renumbering maps: new id = number of survivors below = scan[i] - scan[start of the kind].
-__global__ __launch_bounds__(BLOCK) void k_retire_flags(Params o, const int *__restrict__ ref_cam, const int *__restrict__ retired, int *__restrict__ keep)
+// renumbering maps: new id = number of survivors below = scan[i] - scan[start of the kind].  Landmarks are walked in the CALLER's numbering
+// (the maps are the caller's): o_u2i / o_i2u (NULL: identity) lead to and from a reordered handle's records, here and below.
+__global__ __launch_bounds__(BLOCK) void k_retire_flags(Params o, const int *__restrict__ ref_cam, const int *__restrict__ retired, const int *__restrict__ o_u2i,
+                                                        int *__restrict__ keep)
 {
     const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
     const size_t C = (size_t)o.C, L = (size_t)o.L, F = (size_t)o.F;
     if (i < C) {
         keep[i] = retired[i] ? 0 : 1;
     } else if (i < C + L) {
-        const int2 rows = *reinterpret_cast<const int2 *>(o.lrec + (i - C) * LREC + LR_ROWS);
+        const int2 rows = *reinterpret_cast<const int2 *>(o.lrec + (o_u2i ? (size_t)o_u2i[i - C] : i - C) * LREC + LR_ROWS);
         int any = 0;
         for (int s = rows.x; s < rows.y && !any; ++s) any = retired[slot_meta(o, s) >> META_LMK_BITS] ? 0 : 1;
         keep[i] = any;
@@ -43,6 +45,7 @@ struct Survivors {
 
 // The maps and the survivors' inputs for the create path.  A surviving factor's measurement is the z rows of its slot.
 __global__ __launch_bounds__(BLOCK) void k_retire_compact(Params o, const int *__restrict__ ref_cam, const int *__restrict__ ref_lmk,
+                                                          const int *__restrict__ o_u2i, const int *__restrict__ o_i2u,
                                                           const int *__restrict__ keep, const int *__restrict__ pos, Survivors s)
 {
     const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
@@ -58,7 +61,7 @@ __global__ __launch_bounds__(BLOCK) void k_retire_compact(Params o, const int *_
         const int nl = pos[i] - pos[C];
         s.o2n[i] = nl;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) s.lmk_means[(size_t)nl * 3 + k] = o.lrec[(i - C) * LREC + LR_MU + k];
+        for (int k = 0; k < 3; ++k) s.lmk_means[(size_t)nl * 3 + k] = o.lrec[(o_u2i ? (size_t)o_u2i[i - C] : i - C) * LREC + LR_MU + k];
     } else {
         const size_t f = i - C - L;
         const int nf = pos[i] - pos[C + L], os = o.cadj[f];
@@ -67,7 +70,7 @@ __global__ __launch_bounds__(BLOCK) void k_retire_compact(Params o, const int *_
         s.meas[(size_t)nf * 2] = o.lin[lin_at(os, ROW_Z)];
         s.meas[(size_t)nf * 2 + 1] = o.lin[lin_at(os, ROW_Z + 1)];
         s.cam[nf] = pos[ref_cam[f]];                            // (a surviving factor's camera and landmark survive)
-        s.lmk[nf] = pos[C + (size_t)ref_lmk[f]] - pos[C];
+        s.lmk[nf] = pos[C + (size_t)(o_i2u ? o_i2u[ref_lmk[f]] : ref_lmk[f])] - pos[C];
     }
 }
 
@@ -85,27 +88,29 @@ __global__ __launch_bounds__(BLOCK) void k_retire_slots(Params n, Params o, cons
 
 // One lane per OLD variable: a surviving camera keeps its record, belief view and prior; a surviving landmark its mean | covariance
 // (its prior is k_fold_retired's)
-__global__ __launch_bounds__(BLOCK) void k_retire_vars(Params n, Params o, const int *__restrict__ o2n)
+__global__ __launch_bounds__(BLOCK) void k_retire_vars(Params n, Params o, const int *__restrict__ o2n, const int *__restrict__ n_u2i, const int *__restrict__ o_u2i)
 {
     const int v = blockIdx.x * BLOCK + threadIdx.x;
     if (v >= o.C + o.L) return;
     const int nv = o2n[v];
     if (nv < 0) return;
     if (v < o.C) transplant_cam(n, o, nv, v);
-    else transplant_lmk(n, o, nv, v - o.C);
+    else transplant_lmk(n, o, n_u2i ? n_u2i[nv] : nv, o_u2i ? o_u2i[v - o.C] : v - o.C);
 }
 
 // One lane per OLD landmark that survives walks its old slot range in adj_factors order; every factor of a retired camera is folded into
 // the prior: l.prior += f.messages[1], the full message as the message view reports it (dense_messages: Lambda = J_l^T V J_l and
 // eta = J_l^T q_L with J at the factor's stored linearisation point, plus the landmark part of the dense remainder).  Prior first, then
 // the folds one by one in fp64: a fixed order, the same result every run.  A landmark none of whose factors goes keeps its prior bit for bit.
-__global__ __launch_bounds__(BLOCK) void k_fold_retired(Params n, Params o, const int *__restrict__ lmk_o2n, const int *__restrict__ retired)
+__global__ __launch_bounds__(BLOCK) void k_fold_retired(Params n, Params o, const int *__restrict__ lmk_o2n, const int *__restrict__ retired,
+                                                        const int *__restrict__ n_u2i, const int *__restrict__ o_u2i)
 {
-    const int l = blockIdx.x * BLOCK + threadIdx.x;
+    const int l = blockIdx.x * BLOCK + threadIdx.x;              // the caller's id of an old landmark
     if (l >= o.L) return;
-    const int nl = lmk_o2n[l];
+    int nl = lmk_o2n[l];
     if (nl < 0) return;
-    const double *lr = o.lrec + (size_t)l * LREC;
+    if (n_u2i) nl = n_u2i[nl];
+    const double *lr = o.lrec + (size_t)(o_u2i ? o_u2i[l] : l) * LREC;
     double acc[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) acc[k] = lr[LR_PRIOR + k];
@@ -136,7 +141,7 @@ int retire_into(gbp_ba *o, gbp_ba *n, const std::vector<int> &retired, std::vect
     int *d_ret = nullptr, *d_keep = nullptr, *d_pos = nullptr;
     CHK(graft_scratch(n, scratch, &d_ret, (size_t)op.C)); CHK(graft_scratch(n, scratch, &d_keep, N + 1)); CHK(graft_scratch(n, scratch, &d_pos, N + 1));
     HIPCHK(hipMemcpyAsync(d_ret, retired.data(), sizeof(int) * (size_t)op.C, hipMemcpyHostToDevice, n->stream));
-    hipLaunchKernelGGL(k_retire_flags, dim3(grid_for(N + 1)), dim3(BLOCK), 0, n->stream, op, o->d_ref_cam, d_ret, d_keep);
+    hipLaunchKernelGGL(k_retire_flags, dim3(grid_for(N + 1)), dim3(BLOCK), 0, n->stream, op, o->d_ref_cam, d_ret, o->d_lmk_u2i, d_keep);
     HIPCHK(hipGetLastError());
     size_t scan_bytes = 0;
     HIPCHK(rocprim::exclusive_scan(nullptr, scan_bytes, d_keep, d_pos, 0, N + 1, rocprim::plus<int>(), n->stream));
@@ -159,7 +164,7 @@ int retire_into(gbp_ba *o, gbp_ba *n, const std::vector<int> &retired, std::vect
     CHK(graft_scratch(n, scratch, &s.o2n, N)); CHK(graft_scratch(n, scratch, &s.f_n2o, (size_t)F));
     CHK(graft_scratch(n, scratch, &s.meas, (size_t)F * 2)); CHK(graft_scratch(n, scratch, &s.cam, (size_t)F)); CHK(graft_scratch(n, scratch, &s.lmk, (size_t)F));
     CHK(graft_scratch(n, scratch, &s.cam_means, (size_t)C * 6)); CHK(graft_scratch(n, scratch, &s.lmk_means, (size_t)L * 3));
-    hipLaunchKernelGGL(k_retire_compact, dim3(grid_for(N)), dim3(BLOCK), 0, n->stream, op, o->d_ref_cam, o->d_ref_lmk, d_keep, d_pos, s);
+    hipLaunchKernelGGL(k_retire_compact, dim3(grid_for(N)), dim3(BLOCK), 0, n->stream, op, o->d_ref_cam, o->d_ref_lmk, o->d_lmk_u2i, o->d_lmk_i2u, d_keep, d_pos, s);
     HIPCHK(hipGetLastError());
 
     // 3. the survivors' graph by the create path
@@ -176,8 +181,8 @@ int retire_into(gbp_ba *o, gbp_ba *n, const std::vector<int> &retired, std::vect
 
     // 5. the state transplant, and the fold of the retired factors' messages into their landmarks' priors
     hipLaunchKernelGGL(k_retire_slots, dim3(grid_for(n_slots(n))), dim3(BLOCK), 0, n->stream, p, op, s.f_n2o);
-    hipLaunchKernelGGL(k_retire_vars, dim3(grid_for((size_t)op.C + op.L)), dim3(BLOCK), 0, n->stream, p, op, s.o2n);
-    hipLaunchKernelGGL(k_fold_retired, dim3(grid_for((size_t)op.L)), dim3(BLOCK), 0, n->stream, p, op, s.o2n + op.C, d_ret);
+    hipLaunchKernelGGL(k_retire_vars, dim3(grid_for((size_t)op.C + op.L)), dim3(BLOCK), 0, n->stream, p, op, s.o2n, n->d_lmk_u2i, o->d_lmk_u2i);
+    hipLaunchKernelGGL(k_fold_retired, dim3(grid_for((size_t)op.L)), dim3(BLOCK), 0, n->stream, p, op, s.o2n + op.C, d_ret, n->d_lmk_u2i, o->d_lmk_u2i);
     HIPCHK(hipGetLastError());
     CHK(graft_counters(o, n));
 

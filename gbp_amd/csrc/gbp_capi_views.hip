@@ -11,8 +11,9 @@ extern "C" {
 static void unpack6(const double *pk, double *dense) { for (int i = 0; i < 6; ++i) for (int j = 0; j < 6; ++j) dense[i * 6 + j] = pk[Sym<6>::at(std::min(i, j), std::max(i, j))]; }
 static void unpack3(const double *pk, double *dense) { for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) dense[i * 3 + j] = pk[Sym<3>::at(std::min(i, j), std::max(i, j))]; }
 
-// cameras: rows of `cam_stride` doubles with (eta 6 | Lambda 21) in front; landmarks: rows of `lmk_stride` doubles with (eta 3 | Lambda 6) at lmk_off
-static int get_var_info(gbp_ba *h, const double *d_cam, int cam_stride, const double *d_lmk, int lmk_stride, int lmk_off,
+// cameras: rows of `cam_stride` doubles with (eta 6 | Lambda 21) in front; landmarks: rows of `lmk_stride` doubles with (eta 3 | Lambda 6) at lmk_off.
+// lmk_internal: the landmark rows are in the handle's internal numbering (a reordered handle's records); out they go in the caller's.
+static int get_var_info(gbp_ba *h, const double *d_cam, int cam_stride, const double *d_lmk, int lmk_stride, int lmk_off, bool lmk_internal,
                         double *cam_eta, double *cam_lam, double *lmk_eta, double *lmk_lam)
 {
     const Params &p = h->p;
@@ -27,9 +28,11 @@ static int get_var_info(gbp_ba *h, const double *d_cam, int cam_stride, const do
     if (lmk_eta || lmk_lam) {
         std::vector<double> lr;
         CHK(download(h, lr, d_lmk, (size_t)std::max(p.L, 1) * lmk_stride));
+        const int *u2i = lmk_internal && !h->lmk_u2i.empty() ? h->lmk_u2i.data() : nullptr;
         for (int l = 0; l < p.L; ++l) {
-            if (lmk_eta) for (int k = 0; k < 3; ++k) lmk_eta[(size_t)l * 3 + k] = lr[(size_t)l * lmk_stride + lmk_off + k];
-            if (lmk_lam) unpack3(&lr[(size_t)l * lmk_stride + lmk_off + 3], lmk_lam + (size_t)l * 9);
+            const size_t row = (size_t)(u2i ? u2i[l] : l) * lmk_stride + lmk_off;
+            if (lmk_eta) for (int k = 0; k < 3; ++k) lmk_eta[(size_t)l * 3 + k] = lr[row + k];
+            if (lmk_lam) unpack3(&lr[row + 3], lmk_lam + (size_t)l * 9);
         }
     }
     return GBP_OK;
@@ -46,17 +49,17 @@ int gbp_ba_get_beliefs(gbp_ba_t *h, double *cam_eta, double *cam_lam, double *lm
         // update_all_beliefs, like the reference's freshly constructed nodes (gbp.py:164)
         CHK(ensure_tmp(h, sizeof(double) * 9 * (size_t)std::max(p.L, 1)));
         if (!h->has_beliefs) HIPCHK(hipMemsetAsync(h->d_tmp, 0, sizeof(double) * 9 * (size_t)std::max(p.L, 1), h->stream));
-        else if (p.L) hipLaunchKernelGGL(k_lmk_belief_view, dim3(grid_for((size_t)p.L)), dim3(BLOCK), 0, h->stream, p, h->d_tmp);
+        else if (p.L) hipLaunchKernelGGL(k_lmk_belief_view, dim3(grid_for((size_t)p.L)), dim3(BLOCK), 0, h->stream, p, h->d_tmp, h->d_lmk_u2i);
         HIPCHK(hipGetLastError());
         d_lmk = h->d_tmp;
     }
-    return get_var_info(h, p.cbelief, CBEL, d_lmk, 9, 0, cam_eta, cam_lam, lmk_eta, lmk_lam);
+    return get_var_info(h, p.cbelief, CBEL, d_lmk, 9, 0, false, cam_eta, cam_lam, lmk_eta, lmk_lam);
 }
 
 int gbp_ba_get_priors(gbp_ba_t *h, double *cam_eta, double *cam_lam, double *lmk_eta, double *lmk_lam)
 {
     ENTER(h);
-    return get_var_info(h, h->p.cprior, 27, h->p.lrec, LREC, LR_PRIOR, cam_eta, cam_lam, lmk_eta, lmk_lam);
+    return get_var_info(h, h->p.cprior, 27, h->p.lrec, LREC, LR_PRIOR, true, cam_eta, cam_lam, lmk_eta, lmk_lam);
 }
 
 int gbp_ba_get_means(gbp_ba_t *h, double *cam_mu, double *lmk_mu)
@@ -72,7 +75,8 @@ int gbp_ba_get_means(gbp_ba_t *h, double *cam_mu, double *lmk_mu)
     if (lmk_mu) {
         std::vector<double> lr;
         CHK(download(h, lr, p.lrec, (size_t)std::max(p.L, 1) * LREC));
-        for (int l = 0; l < p.L; ++l) for (int k = 0; k < 3; ++k) lmk_mu[(size_t)l * 3 + k] = lr[(size_t)l * LREC + LR_MU + k];
+        const int *u2i = h->lmk_u2i.empty() ? nullptr : h->lmk_u2i.data();
+        for (int l = 0; l < p.L; ++l) for (int k = 0; k < 3; ++k) lmk_mu[(size_t)l * 3 + k] = lr[(size_t)(u2i ? u2i[l] : l) * LREC + LR_MU + k];
     }
     return GBP_OK;
 }
@@ -85,7 +89,7 @@ int gbp_ba_get_covariances(gbp_ba_t *h, double *cam_sigma, double *lmk_sigma)
     if (!h->has_beliefs) return fail(GBP_ESTATE, "beliefs have not been computed yet (Sigma is zeros in the reference, gbp.py:166)");
     const size_t nc = (size_t)p.C * 21, nl = (size_t)p.L * 6;
     CHK(ensure_tmp(h, sizeof(double) * (nc + nl + 1)));
-    if (p.C + p.L) hipLaunchKernelGGL(k_covariances, dim3(grid_for((size_t)p.C + p.L)), dim3(BLOCK), 0, h->stream, p, h->d_tmp, h->d_tmp + nc);
+    if (p.C + p.L) hipLaunchKernelGGL(k_covariances, dim3(grid_for((size_t)p.C + p.L)), dim3(BLOCK), 0, h->stream, p, h->d_tmp, h->d_tmp + nc, h->d_lmk_u2i);
     HIPCHK(hipGetLastError());
     std::vector<double> s;
     CHK(download(h, s, h->d_tmp, nc + nl));
@@ -129,6 +133,11 @@ int gbp_ba_get_factors(gbp_ba_t *h, int32_t f0, int32_t n, double *eta, double *
     if (cam && n) HIPCHK(hipMemcpyAsync(cam, h->d_ref_cam + f0, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
     if (lmk && n) HIPCHK(hipMemcpyAsync(lmk, h->d_ref_lmk + f0, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
     if ((cam || lmk) && n) HIPCHK(hipStreamSynchronize(h->stream));
+    if (lmk && n && !h->lmk_u2i.empty()) {                           // d_ref_lmk holds internal ids: out go the caller's
+        std::vector<int> i2u;
+        CHK(download(h, i2u, h->d_lmk_i2u, (size_t)p.L));
+        for (int q = 0; q < n; ++q) lmk[q] = i2u[(size_t)lmk[q]];
+    }
     if ((linpoint || meas) && n) {                                  // gathered on the device: only the requested range moves
         CHK(ensure_tmp(h, sizeof(double) * 11 * (size_t)n));
         double *d_x0 = h->d_tmp, *d_z = h->d_tmp + 9 * (size_t)n;
@@ -271,7 +280,7 @@ int gbp_ba_means_snapshot(gbp_ba_t *h)
     }
     const int b = (int)(h->snap_count & 1);
     if (h->snap_count >= 1) HIPCHK(hipStreamWaitEvent(h->stream, h->ev_landed[(h->snap_count - 1) & 1], 0));   // d_mu is free again
-    if (n) hipLaunchKernelGGL(k_pack_means, dim3(grid_for(n)), dim3(BLOCK), 0, h->stream, p, h->d_mu);
+    if (n) hipLaunchKernelGGL(k_pack_means, dim3(grid_for(n)), dim3(BLOCK), 0, h->stream, p, h->d_mu, h->d_lmk_u2i);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->ev_packed, h->stream));
     HIPCHK(hipStreamWaitEvent(h->copy_stream, h->ev_packed, 0));

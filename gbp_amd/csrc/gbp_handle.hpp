@@ -89,6 +89,10 @@ struct gbp_ba {
     hipStream_t own_stream = nullptr, stream = nullptr;
     // order maps: on the device (built there, gbp_build.hpp); the host keeps only what is L- or C-sized
     int *d_ref_cam = nullptr, *d_ref_lmk = nullptr;   // per reference factor (p.cadj = reference id -> slot, p.cpos = slot -> reference id)
+    // landmark order (GBP_FLAG_REORDER_LMKS): inside, landmarks are numbered by camera locality; every landmark-indexed boundary goes
+    // through these maps.  All three NULL / empty on a handle without the flag (identity).
+    int *d_lmk_u2i = nullptr, *d_lmk_i2u = nullptr;   // caller's id -> internal id and back, L entries each
+    std::vector<int> lmk_u2i;                    // host copy of d_lmk_u2i (views that unpack on the host, gbp_ba_get_lmk_order)
     int pack_mode = 0, n_big = 0;                // tile packing (build_graph): 0 whole landmarks, 1 + chunk tiles of the n_big landmarks above 64 factors, 2 dense
     bool hash_ok = false; uint64_t hash = 0;     // digest of the layout (state blobs)
     void *arena = nullptr; size_t arena_bytes = 0, arena_used = 0;
@@ -270,7 +274,7 @@ int graph_hash(gbp_ba *h, uint64_t *out);            // digest of the factor -> 
 int build_graph(gbp_ba *h, const gbp_ba_desc_t *d, std::vector<void *> &scratch, int n_cus, const int **ref_file_out = nullptr);
                                                      // the graph of a descriptor onto a handle (gbp_ba_create, gbp_ba_extend)
 int variable_lambda_max(gbp_ba *h);                  // d_varmax = max over each variable's factors of max(Lambda_f) (gbp_ba.py:27-31)
-int prior_scalars_range(gbp_ba *h, int c0, int l0, double w2_cam, double w2_lmk);   // priors from d_varmax for cameras >= c0, landmarks >= l0
+int prior_scalars_range(gbp_ba *h, int c0, int l0, double w2_cam, double w2_lmk, bool lmk_lambda_by_user);   // priors from d_varmax for cameras >= c0, landmarks >= l0
 // gbp_capi_sweep.hip
 int plan_fused_sweep(gbp_ba *h, int n_cus);          // fused_plan on the handle (the kernels whose attributes it sets live in that unit)
 int fused_max_cams_of_this_build();

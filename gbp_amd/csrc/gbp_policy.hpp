@@ -74,6 +74,29 @@ inline bool camera_windows(int C, int max_cams, long long set_rows, long long wh
 inline bool staged_for_sparseness(long long F, long long table_rows, const Overrides &o) { return (double)F < o.staged_below.value_or(0.75) * (double)table_rows; }
 inline bool general_sweep(bool no_fused, bool dense_remainder, int C, int max_cams, bool windowed) { return no_fused || dense_remainder || (C > max_cams && !windowed); }
 
+// Landmark ORDER (GBP_FLAG_REORDER_LMKS, build_graph): camera windows need landmarks numbered along the trajectory, and a file need not
+// number them so.  The rule, two integer keys and two stable sorts (ties keep the caller's order, so the order is a pure function of the
+// graph and an input already in key order is left alone):
+//   1. reorder_class_key: a LOCAL landmark -- its cameras span at most reorder_wide_span(C) ids -- is keyed by its lowest camera; a WIDE
+//      one (a place seen again: its cameras have no locality) by C; one without factors by C + 1.  Sorted: the locals along the
+//      trajectory, then the wide ones, then the empty ones.
+//   2. reorder_spread_key of that position: the wide landmarks are dealt evenly, by rank, through the locals (wide j of n_wide goes in
+//      front of local floor((2 j + 1) n_local / (2 n_wide))), the empty ones stay last.
+// One per-camera key for all (mean, lowest, median camera) piles the wide landmarks up -- in the middle, at the start or at both ends of
+// the order -- and a few workgroups then meet several hundred cameras; dealt evenly every workgroup carries its share (DESIGN 7d has the
+// modelled camera sets).  Wide means a span above a quarter of the cameras, and never below 128: a sequence's landmarks span a few dozen
+// keyframes (the reference's files: 2 .. 46), ten cameras drawn from anywhere span less than a quarter with probability 4e-5, and a
+// graph of up to 128 cameras fits every table whole.
+constexpr int REORDER_WIDE_MIN = 128;
+constexpr int reorder_wide_span(int C) { return C / 4 > REORDER_WIDE_MIN ? C / 4 : REORDER_WIDE_MIN; }
+constexpr int reorder_class_key(int deg, int lo, int hi, int C) { return deg <= 0 ? C + 1 : (hi - lo + 1 > reorder_wide_span(C) ? C : lo); }
+constexpr int reorder_spread_key(int pos, int n_local, int n_wide)
+{
+    return pos < n_local ? 2 * pos + 1
+           : pos < n_local + n_wide ? 2 * (int)(((2LL * (pos - n_local) + 1) * n_local) / (2LL * n_wide))
+                                    : 2 * n_local + 2;
+}
+
 // Few rows per camera ON AVERAGE behind camera windows: one wave adds them (k_cam_reduce_rows).  A wave takes 32 rows per round trip, so
 // a camera with many rows costs that launch microseconds where the tree form costs every camera a 1024-thread workgroup (fr1desk_small
 // with windows forced: 41 rows per camera, 5.1 us against 3.6) -- which is also why MANY cameras take the wave form whatever their rows

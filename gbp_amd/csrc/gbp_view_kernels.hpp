@@ -9,11 +9,12 @@ namespace gbp {
 // mean | covariance; its information form is Lambda = Sigma^-1, eta = Lambda mu -- the belief as of the last update_belief, whatever has
 // happened to messages or priors since (the stage-wise calls of gbp.py:46-84 change those without touching the beliefs).  The 3x3
 // round trip costs ~cond(Lambda) * 1e-16 relative (1e-10 on the shipped data) against 72 bytes per landmark and sweep that no kernel reads.
-__global__ __launch_bounds__(BLOCK) void k_lmk_belief_view(Params p, double *__restrict__ out)
+// Row u of `out` is the caller's landmark u: lmk_map (caller's id -> internal id; NULL: identity) finds its record.
+__global__ __launch_bounds__(BLOCK) void k_lmk_belief_view(Params p, double *__restrict__ out, const int *__restrict__ lmk_map)
 {
     const int l = blockIdx.x * BLOCK + threadIdx.x;
     if (l >= p.L) return;
-    const double *lr = p.lrec + (size_t)l * LREC;
+    const double *lr = p.lrec + (size_t)(lmk_map ? lmk_map[l] : l) * LREC;
     double sig[6], lam[6], mu[3];
 #pragma unroll
     for (int k = 0; k < 6; ++k) sig[k] = lr[LR_COV + k];
@@ -165,23 +166,28 @@ __global__ __launch_bounds__(BLOCK) void k_export_messages(Params p, const int *
 
 // Sigma = Lambda^-1 for the covariance view (VariableNode.Sigma gbp.py:192)
 // mu of every variable, cameras then landmarks, dense: the viewer's per-frame read (vis/ba_vis.py:39-43, 111-114)
-__global__ __launch_bounds__(BLOCK) void k_pack_means(Params p, double *__restrict__ out)
+// (landmarks in the caller's numbering: lmk_map = caller's id -> internal id, NULL: identity)
+__global__ __launch_bounds__(BLOCK) void k_pack_means(Params p, double *__restrict__ out, const int *__restrict__ lmk_map)
 {
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     if (i < p.C * 6) out[i] = p.cbel[(size_t)(i / 6) * CAMREC + CAM_MU + i % 6];
-    else if (i < p.C * 6 + p.L * 3) { const int j = i - p.C * 6; out[i] = p.lrec[(size_t)(j / 3) * LREC + LR_MU + j % 3]; }
+    else if (i < p.C * 6 + p.L * 3) {
+        const int j = i - p.C * 6, u = j / 3;
+        out[i] = p.lrec[(size_t)(lmk_map ? lmk_map[u] : u) * LREC + LR_MU + j % 3];
+    }
 }
 
-__global__ __launch_bounds__(BLOCK) void k_covariances(Params p, double *__restrict__ cam_sig, double *__restrict__ lmk_sig)
+
+__global__ __launch_bounds__(BLOCK) void k_covariances(Params p, double *__restrict__ cam_sig, double *__restrict__ lmk_sig, const int *__restrict__ lmk_map)
 {
     const int v = blockIdx.x * BLOCK + threadIdx.x;          // (the beliefs carry their covariances: gbp_math.hpp, covariance form)
     if (v < p.C) {
 #pragma unroll
         for (int k = 0; k < 21; ++k) cam_sig[(size_t)v * 21 + k] = p.cbel[(size_t)v * CAMREC + CAM_COV + k];
     } else if (v < p.C + p.L) {
-        const int l = v - p.C;
+        const int u = v - p.C, l = lmk_map ? lmk_map[u] : u;       // row u: the caller's landmark u
 #pragma unroll
-        for (int k = 0; k < 6; ++k) lmk_sig[(size_t)l * 6 + k] = p.lrec[(size_t)l * LREC + LR_COV + k];
+        for (int k = 0; k < 6; ++k) lmk_sig[(size_t)u * 6 + k] = p.lrec[(size_t)l * LREC + LR_COV + k];
     }
 }
 

@@ -25,24 +25,28 @@ def eval_fn(K4, x9, device=0):
     return h, J, hp
 
 
-def _sweep_flags(fused):
-    return 0 if fused is None else (_capi.FLAG_FORCE_FUSED if fused else _capi.FLAG_NO_FUSED)
+def _sweep_flags(fused, reorder_landmarks=False):
+    return (0 if fused is None else (_capi.FLAG_FORCE_FUSED if fused else _capi.FLAG_NO_FUSED)) | \
+        (_capi.FLAG_REORDER_LMKS if reorder_landmarks else 0)
 
 
 class BAEngine:
     def __init__(self, K, cam_means, lmk_means, meas, cam_idx, lmk_idx, *, gauss_noise_std=2.0, loss=None,
                  Nstds=3.0, beta=0.01, num_undamped_iters=6, min_linear_iters=8, eta_damping=0.4,
-                 device=0, fused=None, device_pointers=None):
+                 device=0, fused=None, device_pointers=None, reorder_landmarks=False):
         """fused: None = the library picks the sweep (the fused one -- with per-workgroup camera windows where each workgroup's tiles meet
         few of the cameras -- unless neither all cameras nor the workgroups' camera sets fit one LDS table; plan_info() says what it chose);
         True = the fused sweep whatever the sparseness rule says (GBP_FLAG_FORCE_FUSED); False = the general sweep (GBP_FLAG_NO_FUSED).
         device_pointers = (C, L, F): the five arrays are then integer DEVICE addresses on `device` (float64 cam_means[C,6],
-        lmk_means[L,3], meas[F,2]; int32 cam_idx[F], lmk_idx[F]) and nothing is uploaded (GBP_FLAG_DEVICE_INPUT)."""
+        lmk_means[L,3], meas[F,2]; int32 cam_idx[F], lmk_idx[F]) and nothing is uploaded (GBP_FLAG_DEVICE_INPUT).
+        reorder_landmarks = True: the library numbers the landmarks inside by camera locality (GBP_FLAG_REORDER_LMKS), so that a file whose
+        points come in no particular order still gets camera windows; everything this class takes or returns stays in the caller's
+        numbering (landmark_order() tells where each landmark went), and extend / retire keep the option."""
         self._lib = _capi.load()
         if device_pointers is not None:
             return self._init_from_device(K, cam_means, lmk_means, meas, cam_idx, lmk_idx, device_pointers,
                                           gauss_noise_std, loss, Nstds, beta, num_undamped_iters, min_linear_iters,
-                                          eta_damping, device, fused)
+                                          eta_damping, device, fused, reorder_landmarks)
         K = np.asarray(K, dtype=np.float64)
         if K.shape == (3, 3):
             K = np.array([K[0, 0], K[1, 1], K[0, 2], K[1, 2]])
@@ -67,13 +71,13 @@ class BAEngine:
         d.gauss_noise_std = float(gauss_noise_std)
         d.loss = _capi.LOSS[loss]
         d.num_undamped_iters, d.min_linear_iters = int(num_undamped_iters), int(min_linear_iters)
-        d.flags = _sweep_flags(fused)
+        d.flags = _sweep_flags(fused, reorder_landmarks)
         d.nstds, d.beta, d.eta_damping = float(Nstds), float(beta), float(eta_damping)
         self._h = ct.c_void_p()
         check(self._lib.gbp_ba_create(ct.byref(self._h), ct.byref(d)))
 
     def _init_from_device(self, K, cam_means, lmk_means, meas, cam_idx, lmk_idx, sizes, gauss_noise_std, loss, Nstds, beta,
-                          num_undamped_iters, min_linear_iters, eta_damping, device, fused):
+                          num_undamped_iters, min_linear_iters, eta_damping, device, fused, reorder_landmarks=False):
         K = np.asarray(K, dtype=np.float64)
         if K.shape == (3, 3):                                # the host constructor takes either form too
             K = np.array([K[0, 0], K[1, 1], K[0, 2], K[1, 2]])
@@ -94,7 +98,7 @@ class BAEngine:
         d.gauss_noise_std = float(gauss_noise_std)
         d.loss = _capi.LOSS[loss]
         d.num_undamped_iters, d.min_linear_iters = int(num_undamped_iters), int(min_linear_iters)
-        d.flags = _sweep_flags(fused) | _capi.FLAG_DEVICE_INPUT
+        d.flags = _sweep_flags(fused, reorder_landmarks) | _capi.FLAG_DEVICE_INPUT
         d.nstds, d.beta, d.eta_damping = float(Nstds), float(beta), float(eta_damping)
         self._h = ct.c_void_p()
         check(self._lib.gbp_ba_create(ct.byref(self._h), ct.byref(d)))
@@ -458,6 +462,15 @@ class BAEngine:
         v = ct.c_int32()
         check(self._lib.gbp_ba_check_layout(self._h, ct.byref(v)))
         return v.value
+
+    def landmark_order(self):
+        """internal_of_user (L,) int32: the internal number of every landmark (gbp_ba_get_lmk_order); the identity unless the engine was
+        made with reorder_landmarks=True."""
+        out = np.empty(self.L, np.int32)
+        rc = self._lib.gbp_ba_get_lmk_order(self._h, iptr(out))
+        if rc < 0:
+            check(rc)
+        return out
 
     def info(self):
         a, b, c = ct.c_int32(), ct.c_int32(), ct.c_int32()

@@ -71,6 +71,24 @@ typedef struct gbp_ba_desc {
 #define GBP_FLAG_DEVICE_INPUT 2   /* cam_means / lmk_means / meas / cam_idx / lmk_idx are DEVICE pointers (on desc.device): nothing is
                                      uploaded; the graph is ordered, tiled and linearised where the observations already are */
 
+#define GBP_FLAG_REORDER_LMKS 8    /* number the landmarks INSIDE by camera locality, so that a file whose points come in no particular order
+                                     (any BAL-style file of a reconstruction tool, a live graph whose front end recycles ids) still gets the
+                                     fused sweep's per-workgroup camera windows.  The caller never sees an internal id:
+                                       1. gbp_ba_create orders the landmarks: those whose cameras lie close together go along the trajectory by
+                                          their lowest camera, those seen from all over (places visited again) are dealt evenly through that
+                                          order, landmarks without factors go last; ties keep the caller's order, so the order is a pure function
+                                          of the graph and landmarks that are in that order already stay where they are;
+                                       2. everything indexed by landmark at this boundary -- beliefs, means, covariances, priors in and out, the
+                                          streaming means, the landmark ids of gbp_ba_get_factors, gbp_ba_factor_lambda_max, the ids and maps of
+                                          gbp_ba_extend and gbp_ba_retire -- stays in the caller's numbering;
+                                       3. factor order does not change (inside a landmark it is the reference's adj_factors order), and the results
+                                          are those of a handle without the flag created from the relabelled problem, bit for bit;
+                                       4. gbp_ba_extend and gbp_ba_retire inherit the flag (step 7 of each) and order the union / the survivors
+                                          afresh: a loop closure that arrives with a keyframe finds its landmarks a proper place;
+                                       5. a state blob of a reordered handle restores only into a reordered handle of the same graph, and a blob
+                                          of a handle without the flag only into one without (GBP_EINVAL otherwise, the handle untouched).
+                                     Without the flag nothing changes.  Out of scope: handles with a communicator, renumbering cameras. */
+
 int gbp_abi_version(void);
 const char *gbp_last_error(void);
 
@@ -316,6 +334,10 @@ int gbp_ba_info(gbp_ba_t *h, int32_t *fused_path, int32_t *n_tiles, int32_t *n_b
 int gbp_ba_plan_info(gbp_ba_t *h, int32_t *out, int32_t n);
 int gbp_ba_phase_profile(gbp_ba_t *h, uint64_t *out, int32_t cap_rows, int32_t *n_rows, int32_t *n_cols);   /* debug builds with -DGBP_PHASE_TIMING only (tools/phase_profile.py): per-wave time per phase of the last fused sweep */
 int gbp_ba_check_layout(gbp_ba_t *h, int32_t *bad_slots);   /* debug: slots whose (camera, landmark) do not match the reference factor they hold (0 = sound) */
+/* internal_of_user[L]: where the handle keeps the caller's landmark l (the identity without GBP_FLAG_REORDER_LMKS).  Returns 1 when the handle
+ * was created with the flag, 0 when not, a negative GBP_E* code on error.  For visualisers and for tests that compare against a handle of
+ * the relabelled problem. */
+int gbp_ba_get_lmk_order(gbp_ba_t *h, int32_t *internal_of_user);
 int gbp_ba_fused_max_cams(void);    /* most cameras of ONE workgroup's table in the fused sweep (camera table + wave scratch in 160 KB of LDS); graphs above it run the general sweep unless their camera windows fit (gbp_ba_plan_info [8]) */
 
 #ifdef __cplusplus
