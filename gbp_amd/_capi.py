@@ -77,6 +77,7 @@ SIGNATURES = {
     'gbp_ba_sync': (ct.c_int, [ct.c_void_p]),
     'gbp_ba_extend': (ct.c_int, [ct.c_void_p, ct.POINTER(Ext), _ip]),
     'gbp_ba_retire': (ct.c_int, [ct.c_void_p, ct.c_int32, _ip, _ip, _ip, _ip]),
+    'gbp_ba_cull': (ct.c_int, [ct.c_void_p, ct.c_int32, _ip, _ip, _ip, _ip]),
     'gbp_ba_generate_priors': (ct.c_int, [ct.c_void_p, ct.c_double]),
     'gbp_ba_factor_lambda_max': (ct.c_int, [ct.c_void_p, _dp, _dp]),
     'gbp_ba_set_prior_scalars': (ct.c_int, [ct.c_void_p, _dp, _dp]),
@@ -99,6 +100,7 @@ SIGNATURES = {
     'gbp_ba_get_factors': (ct.c_int, [ct.c_void_p, ct.c_int32, ct.c_int32, _dp, _dp, _dp, _ip, _ip, _dp]),
     'gbp_ba_get_relin_state': (ct.c_int, [ct.c_void_p, _ip, _dp, _dp, _bp]),
     'gbp_ba_get_relin_state_range': (ct.c_int, [ct.c_void_p, ct.c_int32, ct.c_int32, _ip, _dp, _dp, _bp]),
+    'gbp_ba_get_residuals': (ct.c_int, [ct.c_void_p, ct.c_int32, ct.c_int32, _dp, _dp, _dp]),
     'gbp_ba_count_relinearising': (ct.c_int, [ct.c_void_p, ct.POINTER(ct.c_int64)]),
     'gbp_ba_get_relin_counts': (ct.c_int, [ct.c_void_p, _ip, ct.c_int32]),
     'gbp_ba_eval_fn': (ct.c_int, [_dp, ct.c_int32, _dp, _dp, _dp, _dp, ct.c_int32]),

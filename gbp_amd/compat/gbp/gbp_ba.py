@@ -391,7 +391,18 @@ class BAFactorGraph:
         its state; every node and factor view is rebuilt over the survivors.  Returns (cam_map, lmk_map, factor_map): new id of every old
         camera / landmark / factor, -1 for what is gone.  Views taken BEFORE the call are stale afterwards, as after extend."""
         self._flush()
-        cm, lm, fm = self._engine.retire(cam_ids)
+        return self._shrunk(*self._engine.retire(cam_ids))
+
+    def cull_observations(self, factor_ids):
+        """Remove single observations (factor ids as in graph.factors) the way a front end drops matches it has found to be wrong: the
+        factors' messages are discarded -- nothing is folded into any prior -- the cameras and landmarks left without a factor leave the
+        graph, the rest is renumbered compactly and keeps its state; every node and factor view is rebuilt over the survivors.  Returns
+        (cam_map, lmk_map, factor_map) as retire_keyframes does; views taken BEFORE the call are stale afterwards."""
+        self._flush()
+        return self._shrunk(*self._engine.cull(factor_ids))
+
+    def _shrunk(self, cm, lm, fm):
+        """The node and factor view lists over the survivors of a retirement or a cull."""
         keep = fm >= 0
         self._cam_of, self._lmk_of = cm[self._cam_of[keep]].astype(np.int32), lm[self._lmk_of[keep]].astype(np.int32)
         self._C, self._L, self._F = self._engine.C, self._engine.L, self._engine.F
@@ -504,10 +515,9 @@ class BAFactorGraph:
         return self._engine.count_relinearising()
 
     def compute_residuals(self):
-        out = []
-        for f in self.factors:
-            out += list(f.compute_residual())
-        return out
+        """gbp_ba.py:54-59: the residuals of all factors one after the other, as one range view instead of F per-factor calls."""
+        self._flush()
+        return list(self._engine.residuals()[0].reshape(-1))
 
     def get_means(self):
         cm, lm = self._means()

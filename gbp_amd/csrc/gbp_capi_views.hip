@@ -1,5 +1,5 @@
 // gbp_capi_views.hip -- libgbp_hip.so, the state views of include/gbp_ba.h (reference order, dense): beliefs, means, covariances, priors,
-// messages, factors, relinearisation state and its setters, the streaming means export for a viewer, and gbp_ba_eval_fn.  Each view
+// messages, factors, relinearisation state and its setters, per-factor residuals, the streaming means export for a viewer, and gbp_ba_eval_fn.  Each view
 // gathers on the device and moves only the requested range (gbp_view_kernels.hpp).
 #include "gbp_handle.hpp"
 #include "gbp_view_kernels.hpp"
@@ -196,6 +196,29 @@ int gbp_ba_get_relin_state_range(gbp_ba_t *h, int32_t f0, int32_t n, int32_t *it
     ENTER(h);
     CHK(check_range(h, f0, n));
     return relin_range(h, f0, n, iters, eta_damping, adaptive_var, robust_flag);
+}
+
+// Factor.compute_residual of factors [f0, f0+n) of the reference's order (gbp.py:251-259), gathered on the device: what a front end
+// looks at to find the observations it wants to cull (gbp_ba_cull)
+int gbp_ba_get_residuals(gbp_ba_t *h, int32_t f0, int32_t n, double *r2, double *mahalanobis, double *adaptive_var)
+{
+    ENTER(h);
+    CHK(peer_check(h, false));
+    if (!h->has_beliefs) return fail(GBP_ESTATE, "beliefs have not been computed yet (gbp_ba_update_beliefs first)");
+    CHK(check_range(h, f0, n));
+    const Params &p = h->p;
+    if (!n || !(r2 || mahalanobis || adaptive_var)) return GBP_OK;
+    const size_t N = (size_t)n;
+    CHK(ensure_tmp(h, sizeof(double) * 4 * N));
+    double *d_r = h->d_tmp, *d_m = h->d_tmp + 2 * N, *d_av = h->d_tmp + 3 * N;
+    hipLaunchKernelGGL(k_export_residuals, dim3(grid_for(N)), dim3(BLOCK), 0, h->stream, p, p.cadj + f0, n, r2 ? d_r : nullptr,
+                       mahalanobis ? d_m : nullptr, adaptive_var ? d_av : nullptr);
+    HIPCHK(hipGetLastError());
+    if (r2) HIPCHK(hipMemcpyAsync(r2, d_r, sizeof(double) * 2 * N, hipMemcpyDeviceToHost, h->stream));
+    if (mahalanobis) HIPCHK(hipMemcpyAsync(mahalanobis, d_m, sizeof(double) * N, hipMemcpyDeviceToHost, h->stream));
+    if (adaptive_var) HIPCHK(hipMemcpyAsync(adaptive_var, d_av, sizeof(double) * N, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return GBP_OK;
 }
 
 int gbp_ba_set_iters_since_relin(gbp_ba_t *h, const int32_t *iters)

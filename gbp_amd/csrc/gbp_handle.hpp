@@ -8,7 +8,8 @@
 //   gbp_capi_state.hip  checkpoints (host blob, device slot)
 //   gbp_capi_extend.hip growth of a live handle (gbp_ba_extend): the union's inputs, the state transplant
 //   gbp_capi_retire.hip shrinking of a live handle (gbp_ba_retire): renumbering maps, the survivors' inputs, transplant through maps, the fold
-//                       (gbp_graft.hpp: what the two share)
+//   gbp_capi_cull.hip   removal of single observations from a live handle (gbp_ba_cull): survival flags from a factor list, no fold
+//                       (gbp_graft.hpp: what the three share; from the survival flags on, retire and cull go the same way)
 //
 // Kernels live with the unit that launches them (a __global__ defined in a header may be instantiated by one unit only: the
 // dynamic-LDS attributes of the fused sweep are set on the very function objects that are launched).

@@ -1,5 +1,5 @@
-// gbp_view_kernels.hpp -- kernels behind the state views of include/gbp_ba.h (beliefs, messages, factors, relinearisation state, means export,
-// eval_fn): launched by gbp_capi_views.hip only; each moves only the requested range
+// gbp_view_kernels.hpp -- kernels behind the state views of include/gbp_ba.h (beliefs, messages, factors, relinearisation state, per-factor residuals,
+// means export, eval_fn): launched by gbp_capi_views.hip only; each moves only the requested range
 #pragma once
 #include "gbp_kernels.hpp"
 
@@ -89,6 +89,29 @@ __global__ __launch_bounds__(BLOCK) void k_export_relin(Params p, const int *__r
     const int slot = slots[i], st = slot_state(p, slot);
     if (iters) iters[i] = state_age(st, p.clk);
     if (flags) flags[i] = (unsigned char)(st & 3);
+    if (avar) avar[i] = slot_avar(p, slot);
+}
+
+// Factor.compute_residual of a list of slots at the current belief means (gbp.py:251-259): r = h(mu) - z, ||r|| / gauss_noise_std and the
+// adaptive variance.  The same project() and the same mean sources as k_residual (gbp_sweep_kernels.hpp), so the view's sums are those of
+// gbp_ba_residual_sums up to summation order.  The meta word holds the landmark's INTERNAL number: a reordered handle needs no map here.
+__global__ __launch_bounds__(BLOCK) void k_export_residuals(Params p, const int *__restrict__ slots, int n, double *__restrict__ r2,
+                                                            double *__restrict__ maha, double *__restrict__ avar)
+{
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int slot = slots[i];
+    int cam, lmk;
+    if (slot < 0 || slot >= p.T * WTILE || !slot_info(p, slot, cam, lmk)) return;
+    double x[9], h[2];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) x[k] = p.cbel[(size_t)cam * CAMREC + CAM_MU + k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) x[6 + k] = p.lrec[(size_t)lmk * LREC + LR_MU + k];
+    project(x, p.K, h);
+    const double r0 = h[0] - p.lin[lin_at(slot, ROW_Z)], r1 = h[1] - p.lin[lin_at(slot, ROW_Z + 1)];
+    if (r2) { r2[(size_t)i * 2] = r0; r2[(size_t)i * 2 + 1] = r1; }
+    if (maha) maha[i] = sqrt(r0 * r0 + r1 * r1) / sqrt(p.sigma2);
     if (avar) avar[i] = slot_avar(p, slot);
 }
 

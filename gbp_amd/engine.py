@@ -155,6 +155,23 @@ class BAEngine:
         self.C, self.L, self.F = int((cm >= 0).sum()), int((lm >= 0).sum()), int((fm >= 0).sum())
         return cm, lm, fm
 
+    # ---- culling (include/gbp_ba.h: gbp_ba_cull) --------------------------------------------------
+    def cull(self, factor_ids):
+        """Remove single observations (factor ids in reference order): both messages of every listed factor are discarded -- nothing is
+        folded into any prior, an outlier's information vanishes -- cameras and landmarks left without a factor are removed and the
+        survivors are renumbered compactly with all their solver state.  Returns (cam_map, lmk_map, factor_map) as retire does."""
+        ids = i32(np.asarray(factor_ids, dtype=np.int64).reshape(-1))
+        cm, lm, fm = np.empty(self.C, np.int32), np.empty(self.L, np.int32), np.empty(self.F, np.int32)
+        check(self._lib.gbp_ba_cull(self._h, ids.size, iptr(ids) if ids.size else None, iptr(cm), iptr(lm), iptr(fm)))
+        self.C, self.L, self.F = int((cm >= 0).sum()), int((lm >= 0).sum()), int((fm >= 0).sum())
+        return cm, lm, fm
+
+    def cull_outliers(self, nstds):
+        """Cull every factor whose residual at the current belief means exceeds nstds standard deviations (||r|| / gauss_noise_std >
+        nstds).  Returns (culled ids, cam_map, lmk_map, factor_map); identity maps and no device work beyond the view when none does."""
+        ids = np.nonzero(self.residuals()[1] > float(nstds))[0].astype(np.int32)
+        return (ids,) + self.cull(ids)
+
     @classmethod
     def from_problem(cls, p, **kw):
         return cls(p.K, p.cam_means, p.lmk_means, p.meas, p.cam_idx, p.lmk_idx, **kw)
@@ -313,6 +330,14 @@ class BAEngine:
         out = np.empty(2)
         check(self._lib.gbp_ba_residual_sums(self._h, dptr(out)))
         return out
+
+    def residuals(self, f0=0, n=None):
+        """Per-factor residuals of factors [f0, f0+n) at the current belief means (gbp_ba_get_residuals):
+        (r2 (n, 2) = h(mu) - z, mahalanobis (n,) = ||r|| / gauss_noise_std, adaptive_var (n,))."""
+        n = self.F - f0 if n is None else n
+        r2, m, av = np.empty((n, 2)), np.empty(n), np.empty(n)
+        check(self._lib.gbp_ba_get_residuals(self._h, int(f0), int(n), dptr(r2), dptr(m), dptr(av)))
+        return r2, m, av
 
     # ---- views -----------------------------------------------------------------------------
     def _four(self, fn):

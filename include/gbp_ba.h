@@ -163,6 +163,36 @@ int gbp_ba_extend(gbp_ba_t *h, const gbp_ba_ext_t *ext, int32_t *old_to_new);
 int gbp_ba_retire(gbp_ba_t *h, int32_t n_cams, const int32_t *cam_ids, int32_t *cam_old_to_new, int32_t *lmk_old_to_new,
                   int32_t *factor_old_to_new);
 
+/* culling: remove single observations (factors) from a live handle without losing the solver state of what stays.  The counterpart of
+ * gbp_ba_retire for observations that were WRONG: retirement folds the departing factors' messages into priors because their
+ * information was good; culling DROPS it -- an outlier's information must vanish, not be down-weighted (Huber) or kept as a prior.
+ * factor_ids are in the reference's factor order, as everywhere at this boundary (gbp_ba_get_residuals finds the candidates).  After
+ * gbp_ba_cull the handle is exactly what the reference's object graph is after
+ *   1. remove: every listed factor f leaves graph.factors, its camera's adj_factors and its landmark's adj_factors; both of its
+ *      messages are discarded and nothing is added to any prior;
+ *   2. drop: every camera and every landmark that has no surviving factor goes -- the rule gbp_ba_retire applies to landmarks, here
+ *      applied to both kinds.  A variable that had no factor BEFORE the call goes too;
+ *   3. renumber: exactly as gbp_ba_retire step 3 -- survivors keep their relative order, new id = old id - number of removed ids below
+ *      it, the factor order stays the reference's camera-major order, inside a landmark the old order; the three output maps
+ *      (cam_old_to_new[C], lmk_old_to_new[L], factor_old_to_new[F], sizes BEFORE the call, NULL to skip) carry -1 for what is gone;
+ *   4. every surviving factor keeps its linearisation point, measurement, both messages, adaptive variance, robust, damped and pending
+ *      bits, relinearisation age (against the same clock) and its dense remainder when the handle carries one;
+ *   5. every surviving variable keeps its prior, bit for bit;
+ *   6. update_all_beliefs runs: the neighbours of a culled factor lose that factor's messages, every other belief is unchanged up to
+ *      summation order;
+ *   7. / 8. as gbp_ba_retire steps 7 and 8: the handle keeps its stream, overrides, create flags (GBP_FLAG_REORDER_LMKS included: the
+ *      survivors are ordered afresh, maps and ids stay in the caller's numbering), timing settings, clock, walk parity, sweep count and
+ *      relinearisation-count ring; the sweep's plan is chosen for the survivors exactly as gbp_ba_create would choose it; the device
+ *      snapshot slot and the streaming-means mirrors are dropped.
+ * Errors leave the handle untouched (the survivors' graph is built beside it and swapped in last): GBP_ESTATE for a handle with a
+ * communicator, an exchange callback or a peer mailbox, or without beliefs yet; GBP_EINVAL for an id out of range or repeated (the
+ * message names the entry), a negative count, a NULL list with a non-zero count, or a list that leaves no factor; GBP_ENOMEM as for
+ * gbp_ba_retire.  An empty list succeeds, writes identity maps and changes nothing.
+ * Out of scope: sharded handles; keeping variables that are left without factors; removing a landmark by name; a threshold
+ * selection on the device (the caller thresholds gbp_ba_get_residuals and passes the list). */
+int gbp_ba_cull(gbp_ba_t *h, int32_t n_factors, const int32_t *factor_ids, int32_t *cam_old_to_new, int32_t *lmk_old_to_new,
+                int32_t *factor_old_to_new);
+
 /* priors */
 int gbp_ba_generate_priors(gbp_ba_t *h, double weaker_factor);          /* BAFactorGraph.generate_priors_var gbp_ba.py:20-34 */
 int gbp_ba_factor_lambda_max(gbp_ba_t *h, double *cam_max, double *lmk_max);  /* the max_f max(Lambda_f) half of it (sharded set-up) */
@@ -207,6 +237,11 @@ int gbp_ba_get_relin_state(gbp_ba_t *h, int32_t *iters_since_relin, double *eta_
                            double *adaptive_var, uint8_t *robust_flag);                                   /* gbp.py:242-249 */
 int gbp_ba_get_relin_state_range(gbp_ba_t *h, int32_t f0, int32_t n, int32_t *iters_since_relin, double *eta_damping,
                                  double *adaptive_var, uint8_t *robust_flag);                             /* the same for factors [f0, f0+n) only */
+/* per-factor residuals of factors [f0, f0+n) at the current belief means: r2[n*2] = h(mu) - z (Factor.compute_residual gbp.py:251-259),
+ * mahalanobis[n] = ||r|| / gauss_noise_std, adaptive_var[n] = the factor's adaptive variance.  The same projection and the same means as
+ * gbp_ba_are / gbp_ba_energy: sum ||r|| and sum 0.5 ||r||^2 / adaptive_var reproduce gbp_ba_residual_sums.  One device gather over the
+ * requested range.  GBP_ESTATE before beliefs exist and after a peer time-out, like the other belief views. */
+int gbp_ba_get_residuals(gbp_ba_t *h, int32_t f0, int32_t n, double *r2, double *mahalanobis, double *adaptive_var);
 int gbp_ba_set_iters_since_relin(gbp_ba_t *h, const int32_t *iters);                                      /* ba.py:91-93 (per factor) */
 int gbp_ba_fill_iters_since_relin(gbp_ba_t *h, int32_t value);                                            /* ba.py:91-93 (all factors) */
 
