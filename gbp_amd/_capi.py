@@ -19,6 +19,8 @@ FLAG_NO_FUSED = 1
 FLAG_DEVICE_INPUT = 2
 FLAG_FORCE_FUSED = 4
 FLAG_REORDER_LMKS = 8
+RETIRE_FOLD = 0
+RETIRE_DROP = 1
 PLAN_INFO_FIELDS = 11
 CAM_PARTIAL_DOUBLES = 27
 COMM_ID_BYTES = 128
@@ -78,6 +80,7 @@ SIGNATURES = {
     'gbp_ba_extend': (ct.c_int, [ct.c_void_p, ct.POINTER(Ext), _ip]),
     'gbp_ba_retire': (ct.c_int, [ct.c_void_p, ct.c_int32, _ip, _ip, _ip, _ip]),
     'gbp_ba_cull': (ct.c_int, [ct.c_void_p, ct.c_int32, _ip, _ip, _ip, _ip]),
+    'gbp_ba_retire_landmarks': (ct.c_int, [ct.c_void_p, ct.c_int32, _ip, ct.c_int32, _ip, _ip, _ip]),
     'gbp_ba_generate_priors': (ct.c_int, [ct.c_void_p, ct.c_double]),
     'gbp_ba_factor_lambda_max': (ct.c_int, [ct.c_void_p, _dp, _dp]),
     'gbp_ba_set_prior_scalars': (ct.c_int, [ct.c_void_p, _dp, _dp]),

@@ -393,6 +393,15 @@ class BAFactorGraph:
         self._flush()
         return self._shrunk(*self._engine.retire(cam_ids))
 
+    def retire_landmarks(self, lmk_ids, fold=True):
+        """Let go of landmarks (ids as in graph.lmk_nodes) the way a front end drops map points: with fold=True what their factors told
+        the cameras is folded into the cameras' priors (points no keyframe tracks any more), with fold=False it is discarded (points found
+        to be bad).  The landmarks, their factors and the cameras and landmarks left without a factor leave the graph, the rest is
+        renumbered compactly and keeps its state; every node and factor view is rebuilt over the survivors.  Returns (cam_map, lmk_map,
+        factor_map) as retire_keyframes does; views taken BEFORE the call are stale afterwards."""
+        self._flush()
+        return self._shrunk(*self._engine.retire_landmarks(lmk_ids, fold=fold))
+
     def cull_observations(self, factor_ids):
         """Remove single observations (factor ids as in graph.factors) the way a front end drops matches it has found to be wrong: the
         factors' messages are discarded -- nothing is folded into any prior -- the cameras and landmarks left without a factor leave the
@@ -402,7 +411,7 @@ class BAFactorGraph:
         return self._shrunk(*self._engine.cull(factor_ids))
 
     def _shrunk(self, cm, lm, fm):
-        """The node and factor view lists over the survivors of a retirement or a cull."""
+        """The node and factor view lists over the survivors of a retirement (of keyframes or landmarks) or a cull."""
         keep = fm >= 0
         self._cam_of, self._lmk_of = cm[self._cam_of[keep]].astype(np.int32), lm[self._lmk_of[keep]].astype(np.int32)
         self._C, self._L, self._F = self._engine.C, self._engine.L, self._engine.F

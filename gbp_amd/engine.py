@@ -166,6 +166,19 @@ class BAEngine:
         self.C, self.L, self.F = int((cm >= 0).sum()), int((lm >= 0).sum()), int((fm >= 0).sum())
         return cm, lm, fm
 
+    # ---- letting go of landmarks (include/gbp_ba.h: gbp_ba_retire_landmarks) -----------------------
+    def retire_landmarks(self, lmk_ids, fold=True):
+        """Retire landmarks by name (ids in the caller's numbering).  fold=True (the landmarks were good): their factors' messages to the
+        cameras are folded into the cameras' priors; fold=False (the landmarks were bad): the messages are discarded, as cull of exactly
+        those factors does.  The landmarks, their factors and every camera and landmark left without a factor are removed and the survivors
+        are renumbered compactly with all their solver state.  Returns (cam_map, lmk_map, factor_map) as retire does."""
+        ids = i32(np.asarray(lmk_ids, dtype=np.int64).reshape(-1))
+        cm, lm, fm = np.empty(self.C, np.int32), np.empty(self.L, np.int32), np.empty(self.F, np.int32)
+        mode = _capi.RETIRE_FOLD if fold else _capi.RETIRE_DROP
+        check(self._lib.gbp_ba_retire_landmarks(self._h, ids.size, iptr(ids) if ids.size else None, mode, iptr(cm), iptr(lm), iptr(fm)))
+        self.C, self.L, self.F = int((cm >= 0).sum()), int((lm >= 0).sum()), int((fm >= 0).sum())
+        return cm, lm, fm
+
     def cull_outliers(self, nstds):
         """Cull every factor whose residual at the current belief means exceeds nstds standard deviations (||r|| / gauss_noise_std >
         nstds).  Returns (culled ids, cam_map, lmk_map, factor_map); identity maps and no device work beyond the view when none does."""

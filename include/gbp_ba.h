@@ -158,8 +158,8 @@ int gbp_ba_extend(gbp_ba_t *h, const gbp_ba_ext_t *ext, int32_t *old_to_new);
  * communicator, an exchange callback or a peer mailbox, or without beliefs yet; GBP_EINVAL for ids out of range or repeated, a negative
  * count, a NULL list with a non-zero count, or a set that leaves no factor; GBP_ENOMEM when the survivors' graph does not fit -- peak
  * device memory is the old handle's plus the survivors'.  An empty list succeeds and changes nothing.
- * Out of scope: sharded handles; retiring landmarks by name (the symmetric fold into camera priors); exact (Schur) marginalisation with
- * camera-camera fill-in; keeping orphan landmarks. */
+ * Out of scope: sharded handles; exact (Schur) marginalisation with camera-camera fill-in; keeping orphan landmarks.  (Landmarks are
+ * retired by name, with the symmetric fold into camera priors, by gbp_ba_retire_landmarks below.) */
 int gbp_ba_retire(gbp_ba_t *h, int32_t n_cams, const int32_t *cam_ids, int32_t *cam_old_to_new, int32_t *lmk_old_to_new,
                   int32_t *factor_old_to_new);
 
@@ -188,10 +188,50 @@ int gbp_ba_retire(gbp_ba_t *h, int32_t n_cams, const int32_t *cam_ids, int32_t *
  * communicator, an exchange callback or a peer mailbox, or without beliefs yet; GBP_EINVAL for an id out of range or repeated (the
  * message names the entry), a negative count, a NULL list with a non-zero count, or a list that leaves no factor; GBP_ENOMEM as for
  * gbp_ba_retire.  An empty list succeeds, writes identity maps and changes nothing.
- * Out of scope: sharded handles; keeping variables that are left without factors; removing a landmark by name; a threshold
- * selection on the device (the caller thresholds gbp_ba_get_residuals and passes the list). */
+ * Out of scope: sharded handles; keeping variables that are left without factors; a threshold selection on the device (the caller
+ * thresholds gbp_ba_get_residuals and passes the list).  (A landmark is removed by name by gbp_ba_retire_landmarks below.) */
 int gbp_ba_cull(gbp_ba_t *h, int32_t n_factors, const int32_t *factor_ids, int32_t *cam_old_to_new, int32_t *lmk_old_to_new,
                 int32_t *factor_old_to_new);
+
+/* letting go of landmarks: retire landmarks by name (a map point no recent keyframe tracks any more, or one the front end has decided
+ * is bad) from a live handle without losing the solver state of what stays.  The mirror image of gbp_ba_retire: a factor belongs to
+ * exactly one landmark, so retiring landmark l removes all of l's factors, the only surviving neighbours of those factors are cameras,
+ * and landmark priors never change.  lmk_ids are in the caller's numbering.  mode says what becomes of what the factors told their
+ * cameras: GBP_RETIRE_FOLD keeps it (GBP's own marginalisation, as gbp_ba_retire), GBP_RETIRE_DROP discards it (as gbp_ba_cull of
+ * exactly those factors).  After gbp_ba_retire_landmarks the handle is exactly what the reference's object graph is after
+ *   1. fold (mode FOLD only): for every factor f of a listed landmark, with c its camera, c.prior.eta += f.messages[0].eta and
+ *      c.prior.lam += f.messages[0].lam -- the full message as gbp_ba_get_messages reports it now (the dense remainder's camera part
+ *      included when the handle carries one), added in the camera's adj_factors order, which is the reference factor order inside the
+ *      camera's range; f leaves c.adj_factors and graph.factors.  (The library adds a camera's departing messages as a fixed tree, 64
+ *      at a time, and the chunk sums in ascending order on top of the prior: the same bits in every run, equal to the left-to-right sum
+ *      up to fp64 rounding.)  In mode DROP nothing is added to any prior;
+ *   2. drop: the listed landmarks go, and with them every camera and every landmark left without a factor -- the orphan rule of
+ *      gbp_ba_cull, applied to both kinds.  An orphaned camera's prior, with what step 1 has just folded into it, goes with the camera:
+ *      the information of a camera ALL of whose landmarks are retired is lost.  A listed landmark that has no factor is not an error
+ *      (it would go anyway);
+ *   3. renumber: exactly as gbp_ba_retire step 3 -- survivors keep their relative order, new id = old id - number of removed ids below
+ *      it, the factor order stays the reference's camera-major order, inside a landmark the old order; the three output maps
+ *      (cam_old_to_new[C], lmk_old_to_new[L], factor_old_to_new[F], sizes BEFORE the call, NULL to skip) carry -1 for what is gone;
+ *   4. every surviving factor keeps its linearisation point, measurement, both messages, adaptive variance, robust, damped and pending
+ *      bits, relinearisation age (against the same clock) and its dense remainder when the handle carries one;
+ *   5. every surviving landmark keeps its prior, bit for bit; every surviving camera keeps its prior plus what step 1 folded in -- a
+ *      camera none of whose factors goes keeps its prior bit for bit;
+ *   6. update_all_beliefs runs: in mode FOLD surviving beliefs are unchanged up to summation order, in mode DROP the cameras of the
+ *      departed factors lose those factors' messages;
+ *   7. / 8. as gbp_ba_retire steps 7 and 8: the handle keeps its stream, overrides, create flags (GBP_FLAG_REORDER_LMKS included: the
+ *      survivors are ordered afresh, lmk_ids and all maps stay in the caller's numbering), timing settings, clock, walk parity, sweep
+ *      count and relinearisation-count ring; the sweep's plan is chosen for the survivors exactly as gbp_ba_create would choose it;
+ *      the device snapshot slot and the streaming-means mirrors are dropped.
+ * Errors leave the handle untouched (the survivors' graph is built beside it and swapped in last): GBP_ESTATE for a handle with a
+ * communicator, an exchange callback or a peer mailbox, or without beliefs yet; GBP_EINVAL for an id out of range or repeated (the
+ * message names the entry), a negative count, a NULL list with a non-zero count, a mode other than the two, or a list that leaves no
+ * factor; GBP_ENOMEM as for gbp_ba_retire.  An empty list succeeds, writes identity maps and changes nothing.
+ * Out of scope: sharded handles; keeping cameras or landmarks that are left without factors; exact (Schur) marginalisation with
+ * camera-camera fill-in; one combined window step (cull + retire + extend in a single rebuild); a threshold selection on the device. */
+#define GBP_RETIRE_FOLD 0   /* the landmarks were good: keep what their factors told the cameras */
+#define GBP_RETIRE_DROP 1   /* the landmarks were bad: discard it */
+int gbp_ba_retire_landmarks(gbp_ba_t *h, int32_t n_lmks, const int32_t *lmk_ids, int32_t mode, int32_t *cam_old_to_new,
+                            int32_t *lmk_old_to_new, int32_t *factor_old_to_new);
 
 /* priors */
 int gbp_ba_generate_priors(gbp_ba_t *h, double weaker_factor);          /* BAFactorGraph.generate_priors_var gbp_ba.py:20-34 */
