@@ -63,6 +63,18 @@ class Ext(ct.Structure):
                 ('prior_weaker_factor', ct.c_double), ('cam_prior_lambda', _dp), ('lmk_prior_lambda', _dp)]
 
 
+class Window(ct.Structure):
+    """gbp_ba_window_t (include/gbp_ba.h): the lists and the batch of one gbp_ba_window_step."""
+    _fields_ = [('n_cull', ct.c_int32), ('n_retire_cams', ct.c_int32), ('n_retire_lmks', ct.c_int32), ('lmk_mode', ct.c_int32),
+                ('cull_ids', _ip), ('retire_cam_ids', _ip), ('retire_lmk_ids', _ip), ('batch', ct.POINTER(Ext))]
+
+
+class WindowMaps(ct.Structure):
+    """gbp_ba_window_maps_t (include/gbp_ba.h): where gbp_ba_window_step writes its six maps (NULL to skip)."""
+    _fields_ = [('cam_old_to_new', _ip), ('lmk_old_to_new', _ip), ('factor_old_to_new', _ip),
+                ('new_cam_ids', _ip), ('new_lmk_ids', _ip), ('new_factor_ids', _ip)]
+
+
 class GbpError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libgbp_hip error {code}: {msg}")
@@ -81,6 +93,8 @@ SIGNATURES = {
     'gbp_ba_retire': (ct.c_int, [ct.c_void_p, ct.c_int32, _ip, _ip, _ip, _ip]),
     'gbp_ba_cull': (ct.c_int, [ct.c_void_p, ct.c_int32, _ip, _ip, _ip, _ip]),
     'gbp_ba_retire_landmarks': (ct.c_int, [ct.c_void_p, ct.c_int32, _ip, ct.c_int32, _ip, _ip, _ip]),
+    'gbp_ba_window_step': (ct.c_int, [ct.c_void_p, ct.POINTER(Window), ct.POINTER(WindowMaps)]),
+    'gbp_ba_rebuild_count': (ct.c_int, [ct.c_void_p, ct.POINTER(ct.c_int64)]),
     'gbp_ba_generate_priors': (ct.c_int, [ct.c_void_p, ct.c_double]),
     'gbp_ba_factor_lambda_max': (ct.c_int, [ct.c_void_p, _dp, _dp]),
     'gbp_ba_set_prior_scalars': (ct.c_int, [ct.c_void_p, _dp, _dp]),

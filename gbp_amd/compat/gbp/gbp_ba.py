@@ -410,6 +410,29 @@ class BAFactorGraph:
         self._flush()
         return self._shrunk(*self._engine.cull(factor_ids))
 
+    def window_step(self, *, cull=None, retire=None, retire_landmarks=None, fold_landmarks=True, batch=None, prior_weaker_factor=50.0,
+                    cam_prior_lambda=None, lmk_prior_lambda=None):
+        """One step of a sliding window in a single rebuild: extend(*batch), cull_observations(cull), retire_keyframes(retire) and
+        retire_landmarks(retire_landmarks, fold=fold_landmarks), with every id as in cam_nodes / lmk_nodes / factors BEFORE the call (the
+        batch in the union numbering, host arrays).  A landmark whose old observers all retire but which the batch observes stays.  Every
+        node and factor view is rebuilt over the result.  Returns the engine's WindowResult (six maps, -1 for what is gone); views taken
+        BEFORE the call are stale afterwards."""
+        self._flush()
+        if batch is not None:
+            batch = tuple(batch[:3]) + (np.asarray(batch[3], np.int32).reshape(-1), np.asarray(batch[4], np.int32).reshape(-1))
+        r = self._engine.window_step(cull=cull, retire=retire, retire_landmarks=retire_landmarks, fold_landmarks=fold_landmarks, batch=batch,
+                                     prior_weaker_factor=prior_weaker_factor, cam_prior_lambda=cam_prior_lambda, lmk_prior_lambda=lmk_prior_lambda)
+        cam_u = np.concatenate([r.cam_map, r.new_cam_ids])             # union id -> id after the step
+        lmk_u = np.concatenate([r.lmk_map, r.new_lmk_ids])
+        cam_of, lmk_of = np.empty(self._engine.F, np.int32), np.empty(self._engine.F, np.int32)
+        keep = r.factor_map >= 0
+        cam_of[r.factor_map[keep]], lmk_of[r.factor_map[keep]] = cam_u[self._cam_of[keep]], lmk_u[self._lmk_of[keep]]
+        if batch is not None and r.new_factor_ids.size:
+            cam_of[r.new_factor_ids], lmk_of[r.new_factor_ids] = cam_u[batch[3]], lmk_u[batch[4]]
+        self._cam_of, self._lmk_of = cam_of, lmk_of
+        self._shrunk(np.arange(self._engine.C, dtype=np.int32), np.arange(self._engine.L, dtype=np.int32), np.arange(self._engine.F, dtype=np.int32))
+        return r
+
     def _shrunk(self, cm, lm, fm):
         """The node and factor view lists over the survivors of a retirement (of keyframes or landmarks) or a cull."""
         keep = fm >= 0

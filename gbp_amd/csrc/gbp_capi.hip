@@ -109,6 +109,7 @@ struct BuildClock {
 int gbp::build_graph(gbp_ba *h, const gbp_ba_desc_t *d, std::vector<void *> &scratch, int n_cus, const int **ref_file_out)
 {
     BuildClock clk(h->ovr.build_timing, h->stream);
+    ++h->rebuilds;                                            // (gbp_ba_rebuild_count)
     const int C = d->n_cams, L = d->n_lmks, F = d->n_factors;
     Params &p = h->p;
     const bool dev_in = (d->flags & GBP_FLAG_DEVICE_INPUT) != 0;
@@ -609,6 +610,13 @@ int gbp_ba_get_lmk_order(gbp_ba_t *h, int32_t *internal_of_user)
     if (!h || (h->p.L > 0 && !internal_of_user)) return fail(GBP_EINVAL, "null argument");
     for (int l = 0; l < h->p.L; ++l) internal_of_user[l] = h->lmk_u2i.empty() ? l : h->lmk_u2i[(size_t)l];
     return (h->flags & GBP_FLAG_REORDER_LMKS) ? 1 : 0;
+}
+
+int gbp_ba_rebuild_count(gbp_ba_t *h, int64_t *count)
+{
+    if (!h || !count) return fail(GBP_EINVAL, "null argument");
+    *count = (int64_t)h->rebuilds;
+    return GBP_OK;
 }
 
 int gbp_ba_fused_max_cams(void)

@@ -141,6 +141,7 @@ inline void graft_swap(gbp_ba *h, gbp_ba *n)
         n->allocs.push_back(h->d_clk);
         n->d_clk = h->d_clk; h->d_clk = nullptr;
     }
+    n->rebuilds += h->rebuilds;                               // (gbp_ba_rebuild_count: the new graph's own build on top of the handle's)
     std::swap(*h, *n);                                        // h: the new graph; n: what is left of the old handle
     h->fused.alloc_ctx = h;
     n->stream = h->stream;                                    // (synchronised by destroy, not destroyed: own_stream went over)

@@ -11,6 +11,7 @@
 //   gbp_capi_cull.hip   removal of single observations from a live handle (gbp_ba_cull): survival flags from a factor list, no fold
 //   gbp_capi_retire_lmk.hip  letting go of landmarks by name (gbp_ba_retire_landmarks): survival flags from a landmark list, the fold
 //                       into the cameras' priors
+//   gbp_capi_window.hip one window step (gbp_ba_window_step): extend + cull + retire + retire_landmarks in a single rebuild
 //                       (gbp_graft.hpp: what these share; from the survival flags on, the three shrinking calls go the same way)
 //
 // Kernels live with the unit that launches them (a __global__ defined in a header may be instantiated by one unit only: the
@@ -106,6 +107,7 @@ struct gbp_ba {
     double *d_tmp = nullptr; size_t tmp_bytes = 0;
     std::vector<void *> allocs;
     bool has_beliefs = false;
+    long rebuilds = 0;                           // graphs built for this handle so far (gbp_ba_rebuild_count): build_graph counts, graft_swap carries
     int n_cus = 0;
     std::vector<int4> wg_win;                    // camera windows, per workgroup of the fused sweep: {lowest camera, cameras in its set, offset into wg_cams, width of
                                                  // the interval lowest .. highest}; empty: no windows (build_graph decides, fused_plan consumes)

@@ -6,6 +6,7 @@ in libgbp_hip.so on the GPU; constructing an engine without a gfx950 device rais
 """
 from __future__ import annotations
 
+import collections
 import ctypes as ct
 
 import numpy as np
@@ -28,6 +29,11 @@ def eval_fn(K4, x9, device=0):
 def _sweep_flags(fused, reorder_landmarks=False):
     return (0 if fused is None else (_capi.FLAG_FORCE_FUSED if fused else _capi.FLAG_NO_FUSED)) | \
         (_capi.FLAG_REORDER_LMKS if reorder_landmarks else 0)
+
+
+WindowResult = collections.namedtuple('WindowResult', 'cam_map lmk_map factor_map new_cam_ids new_lmk_ids new_factor_ids')
+WindowResult.__doc__ = """What BAEngine.window_step returns: int32 maps of every OLD camera / landmark / factor and of every camera / landmark / factor
+of the batch to its id after the step, -1 for what is gone."""
 
 
 class BAEngine:
@@ -110,6 +116,16 @@ class BAEngine:
         graph is after the same appends, generate_priors_var over the new variables only (or Lambda = lambda I from the scalars) and
         update_all_beliefs.  Returns old_to_new (int32, one entry per old factor: its id in the union's reference order).
         device_pointers = (dC, dL, dF): the five arrays are integer DEVICE addresses (GBP_FLAG_DEVICE_INPUT)."""
+        e, keep, (dC, dL, dF) = self._ext((cam_means, lmk_means, meas, cam_idx, lmk_idx), prior_weaker_factor, cam_prior_lambda,
+                                          lmk_prior_lambda, device_pointers)
+        o2n = np.empty(self.F, np.int32)
+        check(self._lib.gbp_ba_extend(self._h, ct.byref(e), iptr(o2n)))
+        self.C, self.L, self.F = self.C + dC, self.L + dL, self.F + dF
+        return o2n
+
+    def _ext(self, batch, prior_weaker_factor, cam_prior_lambda, lmk_prior_lambda, device_pointers):
+        """gbp_ba_ext_t of a batch (cam_means, lmk_means, meas, cam_idx, lmk_idx) and the arrays that must outlive the call."""
+        cam_means, lmk_means, meas, cam_idx, lmk_idx = batch
         e = _capi.Ext()
         keep = []
         if device_pointers is not None:
@@ -138,10 +154,40 @@ class BAEngine:
             a = f64(lmk_prior_lambda, (dL,))
             keep.append(a)
             e.lmk_prior_lambda = dptr(a)
-        o2n = np.empty(self.F, np.int32)
-        check(self._lib.gbp_ba_extend(self._h, ct.byref(e), iptr(o2n)))
-        self.C, self.L, self.F = self.C + dC, self.L + dL, self.F + dF
-        return o2n
+        return e, keep, (dC, dL, dF)
+
+    # ---- one window step (include/gbp_ba.h: gbp_ba_window_step) -----------------------------------
+    def window_step(self, *, cull=None, retire=None, retire_landmarks=None, fold_landmarks=True, batch=None, prior_weaker_factor=50.0,
+                    cam_prior_lambda=None, lmk_prior_lambda=None, device_pointers=None):
+        """extend(*batch), cull(cull), retire(retire) and retire_landmarks(retire_landmarks, fold=fold_landmarks) in ONE rebuild, with every
+        id in the numbering from BEFORE the call: cull = old factor ids, retire = old cameras, retire_landmarks = old landmarks, batch = the
+        five arrays of extend (ids in the union numbering; device_pointers = (dC, dL, dF) as there).  A landmark whose old observers all
+        retire but which the batch observes is kept.  Returns a WindowResult of six int32 maps (-1: gone)."""
+        w, m = _capi.Window(), _capi.WindowMaps()
+        lists = [i32(np.asarray([] if v is None else v, dtype=np.int64).reshape(-1)) for v in (cull, retire, retire_landmarks)]
+        w.n_cull, w.n_retire_cams, w.n_retire_lmks = (a.size for a in lists)
+        w.cull_ids, w.retire_cam_ids, w.retire_lmk_ids = (iptr(a) if a.size else None for a in lists)
+        w.lmk_mode = _capi.RETIRE_FOLD if fold_landmarks else _capi.RETIRE_DROP
+        dC = dL = dF = 0
+        if batch is not None:
+            e, keep, (dC, dL, dF) = self._ext(batch, prior_weaker_factor, cam_prior_lambda, lmk_prior_lambda, device_pointers)
+            w.batch = ct.pointer(e)
+        out = WindowResult(*(np.empty(n, np.int32) for n in (self.C, self.L, self.F, dC, dL, dF)))
+        (m.cam_old_to_new, m.lmk_old_to_new, m.factor_old_to_new, m.new_cam_ids, m.new_lmk_ids, m.new_factor_ids) = (iptr(a) for a in out)
+        empty = not (w.n_cull or w.n_retire_cams or w.n_retire_lmks or dC or dL or dF)
+        check(self._lib.gbp_ba_window_step(self._h, ct.byref(w), ct.byref(m)))
+        if not empty:
+            self.C = int((out.cam_map >= 0).sum() + (out.new_cam_ids >= 0).sum())
+            self.L = int((out.lmk_map >= 0).sum() + (out.new_lmk_ids >= 0).sum())
+            self.F = int((out.factor_map >= 0).sum() + (out.new_factor_ids >= 0).sum())
+        return out
+
+    def rebuild_count(self):
+        """How many times the graph of this engine has been built (gbp_ba_rebuild_count): 1 after the constructor, + 1 for every extend,
+        retire, cull, retire_landmarks or window_step that changed something."""
+        v = ct.c_int64()
+        check(self._lib.gbp_ba_rebuild_count(self._h, ct.byref(v)))
+        return v.value
 
     # ---- shrinking (include/gbp_ba.h: gbp_ba_retire) ----------------------------------------------
     def retire(self, cam_ids):

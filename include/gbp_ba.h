@@ -227,11 +227,62 @@ int gbp_ba_cull(gbp_ba_t *h, int32_t n_factors, const int32_t *factor_ids, int32
  * message names the entry), a negative count, a NULL list with a non-zero count, a mode other than the two, or a list that leaves no
  * factor; GBP_ENOMEM as for gbp_ba_retire.  An empty list succeeds, writes identity maps and changes nothing.
  * Out of scope: sharded handles; keeping cameras or landmarks that are left without factors; exact (Schur) marginalisation with
- * camera-camera fill-in; one combined window step (cull + retire + extend in a single rebuild); a threshold selection on the device. */
+ * camera-camera fill-in; a threshold selection on the device.  (All four moves of a window in ONE rebuild: gbp_ba_window_step below.) */
 #define GBP_RETIRE_FOLD 0   /* the landmarks were good: keep what their factors told the cameras */
 #define GBP_RETIRE_DROP 1   /* the landmarks were bad: discard it */
 int gbp_ba_retire_landmarks(gbp_ba_t *h, int32_t n_lmks, const int32_t *lmk_ids, int32_t mode, int32_t *cam_old_to_new,
                             int32_t *lmk_old_to_new, int32_t *factor_old_to_new);
+
+/* one window step: what a fixed-lag front end does for every keyframe -- append the keyframe, drop the observations found wrong, let the
+ * oldest keyframes go, let go of the map points nobody tracks any more -- in ONE rebuild of the handle instead of four.  After
+ * gbp_ba_window_step the handle is exactly what this sequence of the calls above leaves:
+ *   1. gbp_ba_extend(step->batch);  2. gbp_ba_cull(cull list);  3. gbp_ba_retire(camera list);  4. gbp_ba_retire_landmarks(landmark
+ *   list, step->lmk_mode),
+ * but every id the caller passes is in the numbering from BEFORE the call (no translation through intermediate maps): cull_ids are old
+ * reference factor ids, retire_cam_ids old cameras, retire_lmk_ids old landmarks in the caller's numbering, and the batch is a
+ * gbp_ba_ext_t as it is (union numbering 0..C+dC-1 and 0..L+dL-1; NULL: no batch).  What follows from the sequence:
+ *   a. new factors are linearised at the belief means the variables have when the call is made (the given means for new variables), with
+ *      zero messages, iters_since_relin = 1, and priors for new variables by gbp_ba_extend step 5;
+ *   b. a variable survives if it is not listed and has at least one surviving factor, old or new.  A landmark all of whose old observers
+ *      are retired but which the new keyframe observes is therefore KEPT, with the folds in its prior (retire-then-extend would have
+ *      orphaned it and refused the batch).  A variable with no factor at all goes (gbp_ba_cull step 2), a new variable the batch gives no
+ *      factor too -- in every step that is not empty, whichever of its parts are.  Removing orphans never removes factors: no cascade;
+ *   c. why a factor leaves, by precedence: it is culled -- both messages are dropped, nothing is folded; otherwise its camera is retired
+ *      -- messages[1] is folded into the landmark's prior if the landmark survives, prior first, then adj_factors order, exactly as
+ *      gbp_ba_retire step 1; otherwise its landmark is listed -- with GBP_RETIRE_FOLD messages[0] is folded into the camera's prior if the
+ *      camera survives, by the fixed 64-wide tree of gbp_ba_retire_landmarks step 1 over the camera's range of the OLD reference order
+ *      (the sequence's chunks fall differently once culled and retired factors are gone: equal up to fp64 rounding), with
+ *      GBP_RETIRE_DROP nothing is folded.  No message is folded twice.  A batch factor never leaves;
+ *   d. the result's factor order is the reference's: camera-major, inside a camera the surviving old factors in their old order, then the
+ *      new ones in batch order.  Survivors keep everything steps 4 - 5 of the four calls promise, update_all_beliefs runs, the handle
+ *      keeps what step 7 promises (GBP_FLAG_REORDER_LMKS included: all ids and maps stay in the caller's numbering) and step 8's drops apply.
+ * Maps out, each optional (NULL to skip), -1 for what is gone: cam_old_to_new[C], lmk_old_to_new[L], factor_old_to_new[F] (sizes from
+ * BEFORE the call) and new_cam_ids[dC], new_lmk_ids[dL], new_factor_ids[dF] for the batch.
+ * Errors leave the handle untouched, bit for bit: GBP_ESTATE for a handle with a communicator, an exchange callback or a peer mailbox, or
+ * without beliefs yet; GBP_EINVAL (the message names the entry) for an id out of range or repeated in any list, a batch factor that names
+ * a retired camera, a listed landmark or an id beyond the union (batch ids are checked on the device with GBP_FLAG_DEVICE_INPUT), a
+ * negative count, a NULL list with a non-zero count, a bad mode, or a step that leaves no factor; GBP_ENOMEM when the result does not
+ * fit -- peak device memory is the old handle's plus the RESULT's, no intermediate union.  An empty step (no list entry, no batch entry)
+ * succeeds, writes identity maps and changes nothing.
+ * Out of scope: sharded handles; exact (Schur) marginalisation; keeping variables that have no factor; a threshold selection on the device. */
+typedef struct gbp_ba_window {
+    int32_t n_cull, n_retire_cams, n_retire_lmks;    /* list lengths (any may be 0) */
+    int32_t lmk_mode;                                /* GBP_RETIRE_FOLD / GBP_RETIRE_DROP: what becomes of messages[0] of the listed landmarks' factors */
+    const int32_t *cull_ids;                         /* old reference factor ids */
+    const int32_t *retire_cam_ids;                   /* old cameras */
+    const int32_t *retire_lmk_ids;                   /* old landmarks, the caller's numbering */
+    const gbp_ba_ext_t *batch;                       /* the keyframe to append, or NULL */
+} gbp_ba_window_t;
+typedef struct gbp_ba_window_maps {
+    int32_t *cam_old_to_new, *lmk_old_to_new, *factor_old_to_new;   /* [C], [L], [F] from before the call */
+    int32_t *new_cam_ids, *new_lmk_ids, *new_factor_ids;            /* [dC], [dL], [dF] of the batch */
+} gbp_ba_window_maps_t;
+int gbp_ba_window_step(gbp_ba_t *h, const gbp_ba_window_t *step, const gbp_ba_window_maps_t *maps);   /* maps: NULL to skip all */
+
+/* how many times the graph of this handle has been built (gbp::build_graph): 1 after gbp_ba_create, + 1 for every gbp_ba_extend /
+ * gbp_ba_retire / gbp_ba_cull / gbp_ba_retire_landmarks / gbp_ba_window_step that succeeds and changes something (empty lists do not
+ * count).  Carried from graph to graph; not part of the state blob. */
+int gbp_ba_rebuild_count(gbp_ba_t *h, int64_t *count);
 
 /* priors */
 int gbp_ba_generate_priors(gbp_ba_t *h, double weaker_factor);          /* BAFactorGraph.generate_priors_var gbp_ba.py:20-34 */
