@@ -157,6 +157,11 @@ SIGNATURES = {
     'gbp_lin_get_beliefs': (ct.c_int, [ct.c_void_p, _dp, _dp]),
     'gbp_lin_get_means': (ct.c_int, [ct.c_void_p, _dp]),
     'gbp_lin_get_messages': (ct.c_int, [ct.c_void_p, _dp, _dp, _dp, _dp]),
+    'gbp_lin_joint_matvec': (ct.c_int, [ct.c_void_p, _dp, _dp]),
+    'gbp_lin_joint_eta': (ct.c_int, [ct.c_void_p, _dp]),
+    'gbp_lin_solve_map': (ct.c_int, [ct.c_void_p, ct.c_void_p, ct.c_void_p]),
+    'gbp_lin_get_map': (ct.c_int, [ct.c_void_p, _dp]),
+    'gbp_lin_map_distance': (ct.c_int, [ct.c_void_p, _dp]),
     'gbp_ba_get_lmk_order': (ct.c_int, [ct.c_void_p, _ip]),
     'gbp_ba_fused_max_cams': (ct.c_int, []),
     'gbp_ba_plan_info': (ct.c_int, [ct.c_void_p, _ip, ct.c_int32]),
@@ -172,6 +177,16 @@ class LinDesc(ct.Structure):
     _fields_ = [('n_vars', ct.c_int32), ('dofs', ct.c_int32), ('n_factors', ct.c_int32), ('device', ct.c_int32),
                 ('var_a', _ip), ('var_b', _ip), ('factor_eta', _dp), ('factor_lam', _dp), ('factor_const', _dp),
                 ('prior_eta', _dp), ('prior_lam', _dp), ('eta_damping', ct.c_double)]
+
+
+class LinMapOpts(ct.Structure):
+    """gbp_lin_map_opts_t (include/gbp_lin.h)."""
+    _fields_ = [('rel_tol', ct.c_double), ('max_iters', ct.c_int32), ('check_every', ct.c_int32), ('warm_start', ct.c_int32)]
+
+
+class LinMapInfo(ct.Structure):
+    """gbp_lin_map_info_t (include/gbp_lin.h)."""
+    _fields_ = [('iters', ct.c_int32), ('converged', ct.c_int32), ('rel_residual', ct.c_double), ('eta_norm', ct.c_double)]
 
 
 _lib = None

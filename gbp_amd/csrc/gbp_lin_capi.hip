@@ -12,8 +12,7 @@
 // edge order (vmsg, through an LDS transpose) for the belief stage; beliefs are records [N][d + d(d+1)/2 + d]
 // (eta | packed Lambda | mu) gathered per factor.  Lambda_f is constant: packed upper 2d x 2d, read every sweep.
 // HBM-bound like the BA sweep; d <= 6 keeps a factor's working set in registers (one wave per SIMD for d = 6).
-#include "../../include/gbp_ba.h"
-#include "../../include/gbp_lin.h"
+#include "gbp_lin_handle.hpp"
 #include "gbp_math.hpp"
 
 #include <hip/hip_runtime.h>
@@ -25,27 +24,6 @@
 #include <vector>
 
 namespace gbp {
-int set_error(int code, const char *fmt, ...);      // gbp_capi.hip: thread-local message behind gbp_last_error()
-
-struct LinParams {
-    int N, F;
-    double damping;
-    const int *va, *vb;          // [F]
-    const double *feta, *flam;   // [2D][F], [D(2D+1)][F] packed upper
-    const double *fconst;        // [F]
-    double *msg_a, *msg_b;       // [D + D(D+1)/2][F] each: eta rows then packed Lambda rows
-    double *bel;                 // [N][D + P + D]
-    const double *prior;         // [N][D + P]
-    const int *vptr, *vadj;      // CSR: variable -> (factor << 1 | side), ascending factor id
-    double *vmsg;                // [2F][D + P]: the same messages in VARIABLE-major (CSR edge) order, for the belief stage
-    const int *epos_a, *epos_b;  // [F]: CSR edge index of (factor, side)
-};
-
-template <int D> struct LinDims {
-    static constexpr int P = D * (D + 1) / 2;       // packed d x d
-    static constexpr int P2 = D * (2 * D + 1);      // packed 2d x 2d
-    static constexpr int REC = D + P + D;           // belief record
-};
 
 // Message to the KEPT variable from  [ A_kk  A_kn ; A_nk  A_nn ] , with the eliminated block S = A_nn + cavity already
 // formed (consumed):  Lambda = A_kk - A_kn S^-1 A_nk,  eta = e_k - A_kn S^-1 e_n   (gbp.py:353-367).
@@ -280,57 +258,6 @@ __global__ __launch_bounds__(256) void k_lin_energy(LinParams p, double *out)
 }
 
 }  // namespace gbp
-
-using namespace gbp;
-
-struct gbp_lin {
-    LinParams p{};
-    int D = 0, device = 0;
-    hipStream_t stream = nullptr;
-    std::vector<void *> allocs;
-    double *d_red = nullptr;
-    int red_blocks = 0;
-    bool has_beliefs = false;
-};
-
-#define LHIPCHK(expr)                                                                                       \
-    do {                                                                                                    \
-        hipError_t e__ = (expr);                                                                            \
-        if (e__ != hipSuccess)                                                                              \
-            return set_error(e__ == hipErrorOutOfMemory ? GBP_ENOMEM : GBP_EHIP, "%s failed: %s (%s:%d)",   \
-                             #expr, hipGetErrorString(e__), __FILE__, __LINE__);                            \
-    } while (0)
-#define LCHK(expr) do { int rc__ = (expr); if (rc__ != GBP_OK) return rc__; } while (0)
-#define LENTER(h)                                                                        \
-    do {                                                                                 \
-        if (!(h)) return set_error(GBP_EINVAL, "NULL handle");                           \
-        LHIPCHK(hipSetDevice((h)->device));                                              \
-    } while (0)
-
-template <typename T>
-static int lin_upload(gbp_lin *h, T **out, const std::vector<T> &v)
-{
-    void *q = nullptr;
-    LHIPCHK(hipMalloc(&q, std::max<size_t>(v.size(), 1) * sizeof(T)));
-    h->allocs.push_back(q);
-    if (!v.empty()) LHIPCHK(hipMemcpyAsync(q, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, h->stream));
-    LHIPCHK(hipStreamSynchronize(h->stream));            // `v` may be a temporary of the caller
-    *out = static_cast<T *>(q);
-    return GBP_OK;
-}
-
-template <typename K>
-static void lin_dispatch(int D, K &&k)
-{
-    switch (D) {
-    case 1: k(std::integral_constant<int, 1>{}); break;
-    case 2: k(std::integral_constant<int, 2>{}); break;
-    case 3: k(std::integral_constant<int, 3>{}); break;
-    case 4: k(std::integral_constant<int, 4>{}); break;
-    case 5: k(std::integral_constant<int, 5>{}); break;
-    default: k(std::integral_constant<int, 6>{}); break;
-    }
-}
 
 static int lin_beliefs(gbp_lin *h)
 {

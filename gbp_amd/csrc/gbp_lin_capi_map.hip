@@ -1,0 +1,224 @@
+// gbp_lin_capi_map.hip -- the batch MAP entry points of include/gbp_lin.h: FactorGraph.joint_distribution_inf / _cov (gbp.py:94-144) on
+// the device, by block-Jacobi conjugate gradients over the handle's own arrays (kernels and method: gbp_lin_map.hpp).
+//
+// The engine has no setters, so the joint system of a handle never changes: the diagonal-block factors and the joint eta are made once,
+// by the first call that needs them, together with the workspace (all of it freed with the handle through `allocs`).  A solve queues
+// four kernels per iteration on the handle's stream and reads |r|^2 back only every `check_every` iterations; when the recurrence claims
+// convergence (or max_iters runs out) the TRUE residual eta - Lambda x is formed with one more product, and the recurrence restarts from
+// it if the claim was wrong.  Nothing here touches the sweep's state (messages, beliefs, has_beliefs).
+#include "gbp_lin_map.hpp"
+
+#include <cmath>
+#include <cstring>
+
+using namespace gbp;
+
+namespace {
+
+int map_alloc(gbp_lin *h, double **out, size_t n)
+{
+    void *q = nullptr;
+    LHIPCHK(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(double)));
+    h->allocs.push_back(q);
+    *out = static_cast<double *>(q);
+    return GBP_OK;
+}
+
+// sum of the first nb doubles of a partials array, in index order
+int map_read_sum(gbp_lin *h, const double *part, double *out)
+{
+    std::vector<double> v((size_t)h->map.nb);
+    LHIPCHK(hipMemcpyAsync(v.data(), part, v.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    LHIPCHK(hipStreamSynchronize(h->stream));
+    double s = 0.0;
+    for (double x : v) s += x;
+    *out = s;
+    return GBP_OK;
+}
+
+// workspace, LDL^T of the diagonal blocks, joint eta and its norm: once per handle
+int map_prepare(gbp_lin *h)
+{
+    if (h->map_ready) return GBP_OK;
+    LinMap &m = h->map;
+    const int D = h->D, P = D * (D + 1) / 2;
+    const size_t nd = (size_t)h->p.N * D;
+    m.nb = std::min(MAP_MAX_BLOCKS, std::max(1, (h->p.N + MAP_BLOCK - 1) / MAP_BLOCK));
+    LCHK(map_alloc(h, &m.ldl, (size_t)h->p.N * (P + D))); LCHK(map_alloc(h, &m.jeta, nd));
+    LCHK(map_alloc(h, &m.x, nd)); LCHK(map_alloc(h, &m.r, nd)); LCHK(map_alloc(h, &m.z, nd)); LCHK(map_alloc(h, &m.p, nd)); LCHK(map_alloc(h, &m.q, nd));
+    LCHK(map_alloc(h, &m.ebuf, (size_t)2 * h->p.F * D));
+    LCHK(map_alloc(h, &m.pq_part, (size_t)m.nb)); LCHK(map_alloc(h, &m.rz_part, (size_t)2 * m.nb)); LCHK(map_alloc(h, &m.rr_part, (size_t)m.nb));
+    LHIPCHK(hipMemsetAsync(m.pq_part, 0, (size_t)m.nb * sizeof(double), h->stream));
+    LHIPCHK(hipMemsetAsync(m.rz_part, 0, (size_t)2 * m.nb * sizeof(double), h->stream));
+    LHIPCHK(hipMemsetAsync(m.rr_part, 0, (size_t)m.nb * sizeof(double), h->stream));
+    double ee = 0.0;
+    if (h->p.N) {
+        lin_dispatch(D, [&](auto d) {
+            hipLaunchKernelGGL((k_map_setup<decltype(d)::value>), dim3(m.nb), dim3(MAP_BLOCK), 0, h->stream, h->p, m);
+        });
+        LHIPCHK(hipGetLastError());
+        LCHK(map_read_sum(h, m.rr_part, &ee));
+    }
+    h->map_eta_norm = std::sqrt(ee);
+    h->map_ready = true;
+    return GBP_OK;
+}
+
+// dst = Lambda_joint src (both device [N][d]); leaves the partials of src . dst in pq_part
+int map_matvec(gbp_lin *h, const double *src, double *dst)
+{
+    const LinMap &m = h->map;
+    if (!h->p.N) return GBP_OK;
+    lin_dispatch(h->D, [&](auto d) {
+        constexpr int DD = decltype(d)::value;
+        if (h->p.F) hipLaunchKernelGGL((k_map_factor<DD>), dim3((h->p.F + 63) / 64), dim3(64), 0, h->stream, h->p, src, m.ebuf);
+        hipLaunchKernelGGL((k_map_var<DD>), dim3(m.nb), dim3(MAP_BLOCK), 0, h->stream, h->p, src, (const double *)m.ebuf, dst, m.pq_part);
+    });
+    LHIPCHK(hipGetLastError());
+    return GBP_OK;
+}
+
+// r = eta - q (use_q) or eta, z, p = z and the partials the iteration `next_it` reads as old; *rel = |r| / |eta|
+int map_restart(gbp_lin *h, int use_q, int next_it, double *rel)
+{
+    const LinMap &m = h->map;
+    lin_dispatch(h->D, [&](auto d) {
+        hipLaunchKernelGGL((k_map_restart<decltype(d)::value>), dim3(m.nb), dim3(MAP_BLOCK), 0, h->stream, m, h->p.N, use_q, (next_it & 1) ^ 1);
+    });
+    LHIPCHK(hipGetLastError());
+    double rr = 0.0;
+    LCHK(map_read_sum(h, m.rr_part, &rr));
+    *rel = std::sqrt(rr) / h->map_eta_norm;
+    return GBP_OK;
+}
+
+int map_solve(gbp_lin *h, const gbp_lin_map_opts_t &o, gbp_lin_map_info_t *info)
+{
+    LCHK(map_prepare(h));
+    const LinMap &m = h->map;
+    const int N = h->p.N, D = h->D;
+    const size_t bytes = (size_t)N * D * sizeof(double);
+    gbp_lin_map_info_t out{0, 1, 0.0, h->map_eta_norm};
+    h->map_solved = false;
+    if (!N || !(h->map_eta_norm > 0.0)) {                 // eta = 0 (or no variables): x = 0
+        if (!N || h->map_eta_norm == 0.0) {
+            if (bytes) LHIPCHK(hipMemsetAsync(m.x, 0, bytes, h->stream));
+            LHIPCHK(hipStreamSynchronize(h->stream));
+            h->map_solved = true;
+            if (info) *info = out;
+            return GBP_OK;
+        }
+        return set_error(GBP_EINVAL, "the joint eta is not finite");
+    }
+    double rel = 0.0;
+    if (o.warm_start) {
+        lin_dispatch(D, [&](auto d) {
+            hipLaunchKernelGGL((k_map_load_means<decltype(d)::value>), dim3(m.nb), dim3(MAP_BLOCK), 0, h->stream, h->p, m);
+        });
+        LHIPCHK(hipGetLastError());
+        LCHK(map_matvec(h, m.x, m.q));
+        LCHK(map_restart(h, 1, 0, &rel));
+    } else {
+        LHIPCHK(hipMemsetAsync(m.x, 0, bytes, h->stream));
+        LCHK(map_restart(h, 0, 0, &rel));
+    }
+    // with no factors the preconditioner is the matrix: one iteration is exact, so it is tested after one
+    const int every = h->p.F ? o.check_every : 1;
+    int it = 0;
+    bool converged = rel <= o.rel_tol;                    // r was formed from eta and x0 directly: already the true residual
+    while (!converged && it < o.max_iters) {
+        const int n = std::min(every, o.max_iters - it);
+        for (int j = 0; j < n; ++j, ++it) {
+            LCHK(map_matvec(h, m.p, m.q));
+            lin_dispatch(D, [&](auto d) {
+                constexpr int DD = decltype(d)::value;
+                hipLaunchKernelGGL((k_map_step<DD>), dim3(m.nb), dim3(MAP_BLOCK), 0, h->stream, m, N, it & 1);
+                hipLaunchKernelGGL((k_map_dir<DD>), dim3(m.nb), dim3(MAP_BLOCK), 0, h->stream, m, N, it & 1);
+            });
+            LHIPCHK(hipGetLastError());
+        }
+        double rr = 0.0;
+        LCHK(map_read_sum(h, m.rr_part, &rr));
+        if (std::sqrt(rr) / h->map_eta_norm <= o.rel_tol || it >= o.max_iters) {
+            LCHK(map_matvec(h, m.x, m.q));                // the true residual; the recurrence goes on from it if the claim was wrong
+            LCHK(map_restart(h, 1, it, &rel));
+            converged = rel <= o.rel_tol;
+        }
+    }
+    LHIPCHK(hipStreamSynchronize(h->stream));
+    out.iters = it; out.converged = converged ? 1 : 0; out.rel_residual = rel;
+    h->map_solved = true;
+    if (info) *info = out;
+    return GBP_OK;
+}
+
+int map_download(gbp_lin *h, const double *src, double *dst)
+{
+    const size_t bytes = (size_t)h->p.N * h->D * sizeof(double);
+    if (bytes) LHIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
+    LHIPCHK(hipStreamSynchronize(h->stream));
+    return GBP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gbp_lin_joint_matvec(gbp_lin_t *h, const double *x, double *y)
+{
+    LENTER(h);
+    if (!x || !y) return set_error(GBP_EINVAL, "x or y is NULL");
+    LCHK(map_prepare(h));
+    const size_t bytes = (size_t)h->p.N * h->D * sizeof(double);
+    if (bytes) LHIPCHK(hipMemcpyAsync(h->map.p, x, bytes, hipMemcpyHostToDevice, h->stream));   // p / q are scratch between solves
+    LCHK(map_matvec(h, h->map.p, h->map.q));
+    return map_download(h, h->map.q, y);
+}
+
+int gbp_lin_joint_eta(gbp_lin_t *h, double *eta)
+{
+    LENTER(h);
+    if (!eta) return set_error(GBP_EINVAL, "eta is NULL");
+    LCHK(map_prepare(h));
+    return map_download(h, h->map.jeta, eta);
+}
+
+int gbp_lin_solve_map(gbp_lin_t *h, const gbp_lin_map_opts_t *opts, gbp_lin_map_info_t *info)
+{
+    LENTER(h);
+    gbp_lin_map_opts_t o{1e-12, 10000, 8, 0};
+    if (opts) o = *opts;
+    if (!(o.rel_tol > 0.0)) return set_error(GBP_EINVAL, "rel_tol must be positive");
+    if (o.max_iters < 0) return set_error(GBP_EINVAL, "negative max_iters");
+    if (o.check_every < 1) return set_error(GBP_EINVAL, "check_every must be at least 1");
+    if (o.warm_start && !h->has_beliefs) return set_error(GBP_ESTATE, "warm_start needs beliefs: call gbp_lin_update_beliefs first");
+    return map_solve(h, o, info);
+}
+
+int gbp_lin_get_map(gbp_lin_t *h, double *mu)
+{
+    LENTER(h);
+    if (!mu) return set_error(GBP_EINVAL, "mu is NULL");
+    if (!h->map_solved) return set_error(GBP_ESTATE, "call gbp_lin_solve_map first");
+    return map_download(h, h->map.x, mu);
+}
+
+int gbp_lin_map_distance(gbp_lin_t *h, double *out)
+{
+    LENTER(h);
+    if (!out) return set_error(GBP_EINVAL, "out is NULL");
+    if (!h->has_beliefs) return set_error(GBP_ESTATE, "beliefs have not been computed yet");
+    if (!h->map_solved) return set_error(GBP_ESTATE, "call gbp_lin_solve_map first");
+    double s = 0.0;
+    if (h->p.N) {
+        lin_dispatch(h->D, [&](auto d) {
+            hipLaunchKernelGGL((k_map_distance<decltype(d)::value>), dim3(h->map.nb), dim3(MAP_BLOCK), 0, h->stream, h->p, h->map);
+        });
+        LHIPCHK(hipGetLastError());
+        LCHK(map_read_sum(h, h->map.pq_part, &s));
+    }
+    *out = std::sqrt(s);
+    return GBP_OK;
+}
+
+}  // extern "C"

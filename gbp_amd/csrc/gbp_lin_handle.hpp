@@ -1,0 +1,101 @@
+// gbp_lin_handle.hpp -- what the translation units of the linear engine (include/gbp_lin.h) share: the kernel parameter block, the
+// handle behind gbp_lin_t, the error / entry macros and the two host helpers every entry point uses.
+//   gbp_lin_capi.hip       create / destroy, the sweep (k_lin_factor, k_lin_belief), energy, getters
+//   gbp_lin_capi_map.hip   the batch MAP by block-Jacobi conjugate gradients (kernels in gbp_lin_map.hpp)
+#pragma once
+#include "../../include/gbp_ba.h"
+#include "../../include/gbp_lin.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <type_traits>
+#include <vector>
+
+namespace gbp {
+int set_error(int code, const char *fmt, ...);      // gbp_capi.hip: thread-local message behind gbp_last_error()
+
+struct LinParams {
+    int N, F;
+    double damping;
+    const int *va, *vb;          // [F]
+    const double *feta, *flam;   // [2D][F], [D(2D+1)][F] packed upper
+    const double *fconst;        // [F]
+    double *msg_a, *msg_b;       // [D + D(D+1)/2][F] each: eta rows then packed Lambda rows
+    double *bel;                 // [N][D + P + D]
+    const double *prior;         // [N][D + P]
+    const int *vptr, *vadj;      // CSR: variable -> (factor << 1 | side), ascending factor id
+    double *vmsg;                // [2F][D + P]: the same messages in VARIABLE-major (CSR edge) order, for the belief stage
+    const int *epos_a, *epos_b;  // [F]: CSR edge index of (factor, side)
+};
+
+template <int D> struct LinDims {
+    static constexpr int P = D * (D + 1) / 2;       // packed d x d
+    static constexpr int P2 = D * (2 * D + 1);      // packed 2d x 2d
+    static constexpr int REC = D + P + D;           // belief record
+};
+
+// Batch-MAP solver state (gbp_lin_map.hpp): every pointer is device memory owned by gbp_lin::allocs, allocated on the first call that needs it.
+struct LinMap {
+    double *ldl, *jeta;              // [N][P + D] LDL^T of the joint's diagonal blocks (packed factor | 1/d), [N][D] joint eta
+    double *x, *r, *z, *p, *q;       // [N][D] each: iterate, residual, preconditioned residual, direction, Lambda_joint p
+    double *ebuf;                    // [2F][D]: per-(factor, side) products in CSR edge order
+    double *pq_part, *rz_part, *rr_part;   // [nb], [2][nb], [nb]: per-block partial sums (rz: one slot per iteration parity)
+    int nb;                          // blocks of every per-variable kernel = number of partials
+};
+
+}  // namespace gbp
+
+using namespace gbp;
+
+struct gbp_lin {
+    LinParams p{};
+    int D = 0, device = 0;
+    hipStream_t stream = nullptr;
+    std::vector<void *> allocs;
+    double *d_red = nullptr;
+    int red_blocks = 0;
+    bool has_beliefs = false;
+    LinMap map{};                    // gbp_lin_capi_map.hip
+    bool map_ready = false, map_solved = false;
+    double map_eta_norm = 0.0;
+};
+
+#define LHIPCHK(expr)                                                                                       \
+    do {                                                                                                    \
+        hipError_t e__ = (expr);                                                                            \
+        if (e__ != hipSuccess)                                                                              \
+            return set_error(e__ == hipErrorOutOfMemory ? GBP_ENOMEM : GBP_EHIP, "%s failed: %s (%s:%d)",   \
+                             #expr, hipGetErrorString(e__), __FILE__, __LINE__);                            \
+    } while (0)
+#define LCHK(expr) do { int rc__ = (expr); if (rc__ != GBP_OK) return rc__; } while (0)
+#define LENTER(h)                                                                        \
+    do {                                                                                 \
+        if (!(h)) return set_error(GBP_EINVAL, "NULL handle");                           \
+        LHIPCHK(hipSetDevice((h)->device));                                              \
+    } while (0)
+
+template <typename T>
+static int lin_upload(gbp_lin *h, T **out, const std::vector<T> &v)
+{
+    void *q = nullptr;
+    LHIPCHK(hipMalloc(&q, std::max<size_t>(v.size(), 1) * sizeof(T)));
+    h->allocs.push_back(q);
+    if (!v.empty()) LHIPCHK(hipMemcpyAsync(q, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, h->stream));
+    LHIPCHK(hipStreamSynchronize(h->stream));            // `v` may be a temporary of the caller
+    *out = static_cast<T *>(q);
+    return GBP_OK;
+}
+
+template <typename K>
+static void lin_dispatch(int D, K &&k)
+{
+    switch (D) {
+    case 1: k(std::integral_constant<int, 1>{}); break;
+    case 2: k(std::integral_constant<int, 2>{}); break;
+    case 3: k(std::integral_constant<int, 3>{}); break;
+    case 4: k(std::integral_constant<int, 4>{}); break;
+    case 5: k(std::integral_constant<int, 5>{}); break;
+    default: k(std::integral_constant<int, 6>{}); break;
+    }
+}

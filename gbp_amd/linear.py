@@ -108,5 +108,37 @@ class LinearEngine:
         check(self._lib.gbp_lin_get_messages(self._h, dptr(ea), dptr(la), dptr(eb), dptr(lb)))
         return ea, la, eb, lb
 
+    # the batch MAP (FactorGraph.joint_distribution_inf / _cov gbp.py:94-144), by block-Jacobi conjugate gradients on the device
+    def joint_matvec(self, x):
+        """Lambda_joint @ x for x of N x d (any shape of that size); returns (N, d)."""
+        x = f64(np.asarray(x, dtype=np.float64).reshape(self.N, self.D))
+        y = np.empty((self.N, self.D))
+        check(self._lib.gbp_lin_joint_matvec(self._h, dptr(x), dptr(y)))
+        return y
+
+    def joint_eta(self):
+        eta = np.empty((self.N, self.D))
+        check(self._lib.gbp_lin_joint_eta(self._h, dptr(eta)))
+        return eta
+
+    def solve_map(self, rel_tol=1e-12, max_iters=10000, check_every=8, warm_start=False):
+        """The batch MAP Lambda_joint^-1 eta_joint: (mu (N, d), info).  info: iters, converged, rel_residual (of the true residual),
+        eta_norm.  warm_start: from the current belief means instead of 0.  Running out of max_iters is not an error."""
+        o = _capi.LinMapOpts(float(rel_tol), int(max_iters), int(check_every), int(bool(warm_start)))
+        i = _capi.LinMapInfo()
+        check(self._lib.gbp_lin_solve_map(self._h, ct.byref(o), ct.byref(i)))
+        return self.map_mean(), {'iters': i.iters, 'converged': bool(i.converged), 'rel_residual': i.rel_residual, 'eta_norm': i.eta_norm}
+
+    def map_mean(self):
+        mu = np.empty((self.N, self.D))
+        check(self._lib.gbp_lin_get_map(self._h, dptr(mu)))
+        return mu
+
+    def map_distance(self):
+        """|get_means() - map_mean()|_2 computed on the device: the 'Av distance of means from MAP' of ndim_posegraph.py:108."""
+        out = ct.c_double()
+        check(self._lib.gbp_lin_map_distance(self._h, ct.byref(out)))
+        return out.value
+
     def sync(self):
         check(self._lib.gbp_lin_sync(self._h))

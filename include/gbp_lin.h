@@ -51,6 +51,29 @@ int  gbp_lin_get_beliefs(gbp_lin_t *h, double *eta, double *lam);               
 int  gbp_lin_get_means(gbp_lin_t *h, double *mu);                               /* N x d   FactorGraph.get_means gbp.py:146-153 */
 int  gbp_lin_get_messages(gbp_lin_t *h, double *eta_a, double *lam_a, double *eta_b, double *lam_b);   /* Factor.messages gbp.py:222 */
 
+/* ---- batch MAP: FactorGraph.joint_distribution_inf / joint_distribution_cov (gbp.py:94-144) without the dense N d x N d inverse ----
+ * The joint information form  Lambda = blockdiag(prior Lambda) + sum_f scatter(Lambda_f),  eta = prior eta + sum_f scatter(eta_f)
+ * (gbp.py:94-126) is block-sparse and SPD; its solution Lambda^-1 eta (the means of gbp.py:139-144, the "MAP" that
+ * ndim_posegraph.py:94,108 measures the GBP means against) is found on the device by conjugate gradients preconditioned with the d x d
+ * diagonal blocks.  No floating-point atomics: two solves of one handle with the same options are bit-identical.  The sweep's state
+ * (messages, beliefs) is neither read -- except by warm_start and gbp_lin_map_distance -- nor written.
+ *
+ * gbp_lin_map_opts_t: stop at |eta - Lambda x| <= rel_tol |eta|; the recurrence's residual is read every check_every iterations (every
+ * iteration on a graph without factors, where one iteration is exact), so `iters` is a multiple of it unless max_iters cuts it short;
+ * warm_start 1: x0 = the current belief means (GBP_ESTATE without beliefs), 0: x0 = 0.  NULL opts = {1e-12, 10000, 8, 0};
+ * rel_tol <= 0, max_iters < 0 or check_every < 1: GBP_EINVAL.
+ * gbp_lin_map_info_t: rel_residual is that of the TRUE residual, recomputed with one product when the recurrence claims convergence or
+ * max_iters runs out (the recurrence restarts from it when the claim was wrong); converged = 0 with GBP_OK when max_iters ran out --
+ * the iterate reached is still retrievable; eta_norm = |eta|_2.  eta = 0 gives x = 0, converged, 0 iterations.  info may be NULL. */
+typedef struct { double rel_tol; int32_t max_iters, check_every, warm_start; } gbp_lin_map_opts_t;
+typedef struct { int32_t iters, converged; double rel_residual, eta_norm; } gbp_lin_map_info_t;
+
+int  gbp_lin_joint_matvec(gbp_lin_t *h, const double *x, double *y);            /* host N x d in / out: y = Lambda_joint x (joint_distribution_inf gbp.py:94-126) */
+int  gbp_lin_joint_eta(gbp_lin_t *h, double *eta);                              /* host N x d: prior eta + scattered factor eta (gbp.py:94-126)                  */
+int  gbp_lin_solve_map(gbp_lin_t *h, const gbp_lin_map_opts_t *opts, gbp_lin_map_info_t *info);   /* joint_distribution_cov's mu gbp.py:128-144; stays on the device */
+int  gbp_lin_get_map(gbp_lin_t *h, double *mu);                                 /* N x d, the solution of the last solve (gbp.py:139-144); GBP_ESTATE before one   */
+int  gbp_lin_map_distance(gbp_lin_t *h, double *out);                           /* |means - map|_2 on the device (gbp.py:94-144, ndim_posegraph.py:108); GBP_ESTATE without beliefs or a solve */
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@ ap.add_argument('--k', type=int, default=5)
 ap.add_argument('--steps', type=int, default=100)
 ap.add_argument('--warmup', type=int, default=10)
 ap.add_argument('--no-cpu-baseline', action='store_true')
+ap.add_argument('--map', action='store_true', help='after the timed sweeps, solve the batch MAP (cold) and report the distance of the means from it')
 a = ap.parse_args()
 rs = np.random.RandomState(0)
 N, D, k = a.vars, a.dofs, a.k
@@ -35,6 +36,16 @@ e = LinearEngine(va, vb, fe, np.ascontiguousarray(fl), mu0 / 3.0, np.ascontiguou
 e.update_all_beliefs()
 e.iterate(a.warmup); e.sync()
 t0 = time.perf_counter(); e.iterate(a.steps); e.sync(); dt = time.perf_counter() - t0
+map_res = None
+if a.map:
+    # the batch MAP by block-Jacobi CG (gbp_lin_solve_map), cold; the first call also makes the workspace and the diagonal-block
+    # factors, so that is done by a product beforehand and kept out of the time per iteration
+    e.joint_eta()
+    tm = time.perf_counter(); _, info = e.solve_map(); tm = time.perf_counter() - tm
+    ms_cg = 1e3 * tm / max(info['iters'], 1)
+    map_res = {"cg_iters": info['iters'], "converged": info['converged'], "rel_residual": info['rel_residual'], "ms_per_cg_iter": ms_cg,
+               "map_distance": e.map_distance(), "sweeps_before_distance": a.warmup + a.steps,
+               "cg_iter_over_sweep": ms_cg / (1e3 * dt / a.steps)}
 P = D * (D + 1) // 2
 bytes_sweep = 8 * (F * (D * (2 * D + 1) + 2 * D + 6 * (D + P) + 2 * (D + P)) + N * (2 * (D + P) + D))
 cpu = None
@@ -55,4 +66,4 @@ print(json.dumps({"metric": "linear GBP sweeps/s", "value": a.steps / dt, "unit"
                   "config": {"workload": f"ring pose graph {N} vars x {D} dofs, {F} linear_displacement factors"},
                   "dtype": "f64", "roofline": {"bound": "hbm", "achieved": bytes_sweep * a.steps / dt / 1e9, "peak": 8000.0,
                                                "unit": "GB/s", "frac": bytes_sweep * a.steps / dt / 1e9 / 8000.0, "traffic": None},
-                  "energy_after": e.energy(), "cpu_baseline": cpu}))
+                  "energy_after": e.energy(), "map": map_res, "cpu_baseline": cpu}))
