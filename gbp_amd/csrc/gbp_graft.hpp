@@ -1,13 +1,11 @@
-// gbp_graft.hpp -- what the calls that rebuild a live handle share (gbp_ba_extend: gbp_capi_extend.hip, gbp_ba_retire:
-// gbp_capi_retire.hip, gbp_ba_cull: gbp_capi_cull.hip).  All build the new graph BESIDE the handle by the create path (gbp::build_graph),
-// move the state of the factors and variables that live on into the new layout, and swap the new graph in only when everything has
-// succeeded.  Here: the per-slot and per-variable moves (device), on the host the settings the new graph inherits, the counters it
-// carries and the swap itself, and -- for the two calls that SHRINK a handle -- the whole way from survival flags to the survivors'
-// graph (graft_survivors: one scan, the compaction, the create path, the transplant through index maps).
+// gbp_graft.hpp -- what the calls that rebuild a live handle share: gbp_ba_extend (gbp_capi_extend.hip) and the engine behind
+// gbp_ba_window_step, gbp_ba_cull, gbp_ba_retire and gbp_ba_retire_landmarks (gbp_capi_window.hip).  Both build the new graph BESIDE the
+// handle by the create path (gbp::build_graph), move the state of the factors and variables that live on into the new layout, and swap
+// the new graph in only when everything has succeeded.  Here: the per-slot and per-variable moves (device), the arrays a rebuild
+// assembles for the create path (Survivors), and on the host the staging of inputs and scratch, the settings the new graph inherits, the
+// counters it carries, the swap itself and the maps of a call that changes nothing.
 #pragma once
 #include "gbp_handle.hpp"
-
-#include <rocprim/device/device_scan.hpp>
 
 #include <new>
 
@@ -148,157 +146,14 @@ inline void graft_swap(gbp_ba *h, gbp_ba *n)
     gbp_ba_destroy(n);
 }
 
-// ---- shrinking: from survival flags to the survivors' graph (gbp_ba_retire, gbp_ba_cull) ----------------------------------------------
-// keep[0 .. C): the camera stays; keep[C .. C+L): the landmark (the CALLER's numbering) stays; keep[C+L .. C+L+F): the factor (old
-// reference order) stays; keep[C+L+F] = 0, so that the exclusive scan behind it ends with the total.  One scan over all of it gives the
-// three renumbering maps: new id = number of survivors below = scan[i] - scan[start of the kind].  A surviving factor's camera and
-// landmark survive (the caller's flag kernel sees to that).  o_u2i / o_i2u (NULL: identity) lead to and from a reordered handle's records.
+// What a rebuild that lets things go assembles on the device for the create path, and its maps (gbp_capi_window.hip fills them, over the
+// index space of the old graph followed by the batch; the ids are the CALLER's: new id = number of survivors below)
 struct Survivors {
-    int *o2n;                     // [C + L + F] the three maps one after the other: new id, or -1 for what is gone
-    int *f_n2o;                   // [F'] old reference id of every surviving factor
-    double *meas; int *cam, *lmk; // [F'] the survivors' observations in old reference order, ids in the NEW numbering
-    double *cam_means, *lmk_means;// [C' x 6], [L' x 3] current belief means (node.mu)
+    int *o2n;                     // [C | L | F] the maps one after the other: new id, or -1 for what is gone
+    int *f_n2o;                   // [F'] the old id of the factor at every file position of the result
+    double *meas; int *cam, *lmk; // [F'] the result's observations in file order, ids in the NEW numbering
+    double *cam_means, *lmk_means;// [C' x 6], [L' x 3] current belief means (node.mu) of old variables, the given means of new ones
 };
-
-// The maps and the survivors' inputs for the create path.  A surviving factor's measurement is the z rows of its slot.
-// (static: these kernels are instantiated by every unit that shrinks a handle, each for itself)
-static __global__ __launch_bounds__(BLOCK) void k_graft_compact(Params o, const int *__restrict__ ref_cam, const int *__restrict__ ref_lmk,
-                                                                const int *__restrict__ o_u2i, const int *__restrict__ o_i2u,
-                                                                const int *__restrict__ keep, const int *__restrict__ pos, Survivors s)
-{
-    const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-    const size_t C = (size_t)o.C, L = (size_t)o.L, F = (size_t)o.F;
-    if (i >= C + L + F) return;
-    if (!keep[i]) { s.o2n[i] = -1; return; }
-    if (i < C) {
-        const int nc = pos[i];
-        s.o2n[i] = nc;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) s.cam_means[(size_t)nc * 6 + k] = o.cbel[i * CAMREC + CAM_MU + k];
-    } else if (i < C + L) {
-        const int nl = pos[i] - pos[C];
-        s.o2n[i] = nl;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) s.lmk_means[(size_t)nl * 3 + k] = o.lrec[(o_u2i ? (size_t)o_u2i[i - C] : i - C) * LREC + LR_MU + k];
-    } else {
-        const size_t f = i - C - L;
-        const int nf = pos[i] - pos[C + L], os = o.cadj[f];
-        s.o2n[i] = nf;
-        s.f_n2o[nf] = (int)f;
-        s.meas[(size_t)nf * 2] = o.lin[lin_at(os, ROW_Z)];
-        s.meas[(size_t)nf * 2 + 1] = o.lin[lin_at(os, ROW_Z + 1)];
-        s.cam[nf] = pos[ref_cam[f]];                            // (a surviving factor's camera and landmark survive)
-        s.lmk[nf] = pos[C + (size_t)(o_i2u ? o_i2u[ref_lmk[f]] : ref_lmk[f])] - pos[C];
-    }
-}
-
-// One lane per slot of the survivors' graph: the factor's whole state from its old slot (transplant_slot)
-static __global__ __launch_bounds__(BLOCK) void k_graft_slots(Params n, Params o, const int *__restrict__ f_n2o)
-{
-    const int slot = blockIdx.x * BLOCK + threadIdx.x;
-    if (slot >= n.T * WTILE || (slot & 63) >= n.tiles[slot >> 6].z) return;
-    const int r = n.cpos[slot];
-    if (r < 0 || r >= n.F) return;
-    const int f = f_n2o[r];
-    if (f < 0 || f >= o.F) return;
-    transplant_slot(n, o, slot, o.cadj[f]);
-}
-
-// One lane per OLD variable: a surviving camera keeps its record, belief view and prior; a surviving landmark its mean | covariance
-// and prior (gbp_ba_retire then writes the landmarks' priors again, with the folds)
-static __global__ __launch_bounds__(BLOCK) void k_graft_vars(Params n, Params o, const int *__restrict__ o2n, const int *__restrict__ n_u2i, const int *__restrict__ o_u2i)
-{
-    const int v = blockIdx.x * BLOCK + threadIdx.x;
-    if (v >= o.C + o.L) return;
-    const int nv = o2n[v];
-    if (nv < 0) return;
-    if (v < o.C) transplant_cam(n, o, nv, v);
-    else transplant_lmk(n, o, n_u2i ? n_u2i[nv] : nv, o_u2i ? o_u2i[v - o.C] : v - o.C);
-}
-
-// The survivors' graph built beside the old handle `o` into the fresh handle `n` (which owns nothing of o's), from the survival flags
-// d_keep[C + L + F + 1] (device, made on n->stream).  `emptied`: the message when nothing survives.  `after_transplant(s)`: what the caller
-// launches on n->stream between the transplant and update_all_beliefs (gbp_ba_retire: the fold; gbp_ba_cull: nothing).  maps: the three
-// maps one after the other, on the host.
-//
-// The survivors' "file order" is the old reference order with the departed factors taken out: camera renumbering is monotone, so that
-// list is camera-major already, create keeps it as it is (no sort, no ref_file map) and new reference id = position in the list.
-template <typename After>
-inline int graft_survivors(gbp_ba *o, gbp_ba *n, const int *d_keep, std::vector<void *> &scratch, std::vector<int> &maps, const char *emptied,
-                           After &&after_transplant)
-{
-    const Params &op = o->p;
-    const size_t N = (size_t)op.C + op.L + op.F;
-
-    // 1. one prefix sum, the survivors' sizes
-    int *d_pos = nullptr;
-    CHK(graft_scratch(n, scratch, &d_pos, N + 1));
-    size_t scan_bytes = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, scan_bytes, d_keep, d_pos, 0, N + 1, rocprim::plus<int>(), n->stream));
-    void *scan_tmp = nullptr;
-    HIPCHK(hipMallocAsync(&scan_tmp, std::max<size_t>(scan_bytes, 1), n->stream));
-    scratch.push_back(scan_tmp);
-    HIPCHK(rocprim::exclusive_scan(scan_tmp, scan_bytes, d_keep, d_pos, 0, N + 1, rocprim::plus<int>(), n->stream));
-    int ends[3] = {0, 0, 0};
-    HIPCHK(hipMemcpyAsync(&ends[0], d_pos + op.C, sizeof(int), hipMemcpyDeviceToHost, n->stream));
-    HIPCHK(hipMemcpyAsync(&ends[1], d_pos + op.C + op.L, sizeof(int), hipMemcpyDeviceToHost, n->stream));
-    HIPCHK(hipMemcpyAsync(&ends[2], d_pos + N, sizeof(int), hipMemcpyDeviceToHost, n->stream));
-    HIPCHK(hipStreamSynchronize(n->stream));
-    const int C = ends[0], L = ends[1] - ends[0], F = ends[2] - ends[1];
-    if (F <= 0 || C <= 0 || L <= 0) return fail(GBP_EINVAL, "%s", emptied);
-    graft_settings(o, n, C, L, F);
-    Params &p = n->p;
-
-    // 2. the survivors' inputs, on the device
-    Survivors s{};
-    CHK(graft_scratch(n, scratch, &s.o2n, N)); CHK(graft_scratch(n, scratch, &s.f_n2o, (size_t)F));
-    CHK(graft_scratch(n, scratch, &s.meas, (size_t)F * 2)); CHK(graft_scratch(n, scratch, &s.cam, (size_t)F)); CHK(graft_scratch(n, scratch, &s.lmk, (size_t)F));
-    CHK(graft_scratch(n, scratch, &s.cam_means, (size_t)C * 6)); CHK(graft_scratch(n, scratch, &s.lmk_means, (size_t)L * 3));
-    hipLaunchKernelGGL(k_graft_compact, dim3(grid_for(N)), dim3(BLOCK), 0, n->stream, op, o->d_ref_cam, o->d_ref_lmk, o->d_lmk_u2i, o->d_lmk_i2u, d_keep, d_pos, s);
-    HIPCHK(hipGetLastError());
-
-    // 3. the survivors' graph by the create path
-    gbp_ba_desc_t d{};
-    d.n_cams = C; d.n_lmks = L; d.n_factors = F; d.device = o->device;
-    d.cam_means = s.cam_means; d.lmk_means = s.lmk_means; d.meas = s.meas; d.cam_idx = s.cam; d.lmk_idx = s.lmk;
-    d.flags = GBP_FLAG_DEVICE_INPUT;                           // (the sweep flags are n->flags)
-    const int *ref_file = nullptr;
-    CHK(build_graph(n, &d, scratch, n->n_cus, &ref_file));
-    if (ref_file) return fail(GBP_ESTATE, "internal error: the survivors' list is not camera-major");
-
-    // 4. a remainder switched on on demand stays on (the fresh handle allocates it exactly as the old one did)
-    if (o->lazy_xtra && op.xtra) CHK(enable_remainder(n));
-
-    // 5. the state transplant, and what the caller does to it
-    hipLaunchKernelGGL(k_graft_slots, dim3(grid_for(n_slots(n))), dim3(BLOCK), 0, n->stream, p, op, s.f_n2o);
-    hipLaunchKernelGGL(k_graft_vars, dim3(grid_for((size_t)op.C + op.L)), dim3(BLOCK), 0, n->stream, p, op, s.o2n, n->d_lmk_u2i, o->d_lmk_u2i);
-    after_transplant(s);
-    HIPCHK(hipGetLastError());
-    CHK(graft_counters(o, n));
-
-    // 6. update_all_beliefs over the survivors
-    CHK(gbp_ba_update_beliefs(n));
-    maps.resize(N);
-    HIPCHK(hipMemcpyAsync(maps.data(), s.o2n, sizeof(int) * N, hipMemcpyDeviceToHost, n->stream));
-    HIPCHK(hipStreamSynchronize(n->stream));
-    return GBP_OK;
-}
-
-// the end of a shrinking call: the scratch goes; on success the maps go out (sizes from BEFORE the call, NULL to skip) and the new
-// graph becomes the handle, on failure the half-built graph goes and the handle is what it was
-inline int graft_finish_shrink(gbp_ba *h, gbp_ba *n, int rc, std::vector<void *> &scratch, const std::vector<int> &maps,
-                               int32_t *cam_old_to_new, int32_t *lmk_old_to_new, int32_t *factor_old_to_new)
-{
-    for (void *q : scratch) (void)hipFreeAsync(q, h->stream);
-    (void)hipStreamSynchronize(h->stream);
-    if (rc != GBP_OK) return n ? graft_abandon(n, rc) : rc;
-    const size_t C0 = (size_t)h->p.C, L0 = (size_t)h->p.L, F0 = (size_t)h->p.F;     // (h->p is the old graph's until the swap)
-    if (cam_old_to_new) std::memcpy(cam_old_to_new, maps.data(), C0 * sizeof(int32_t));
-    if (lmk_old_to_new) std::memcpy(lmk_old_to_new, maps.data() + C0, L0 * sizeof(int32_t));
-    if (factor_old_to_new) std::memcpy(factor_old_to_new, maps.data() + C0 + L0, F0 * sizeof(int32_t));
-    graft_swap(h, n);
-    return GBP_OK;
-}
 
 // nothing goes: identity maps
 inline void graft_identity_maps(const Params &op, int32_t *cam_old_to_new, int32_t *lmk_old_to_new, int32_t *factor_old_to_new)

@@ -7,12 +7,10 @@
 //   gbp_capi_views.hip  state views (beliefs, messages, factors, relinearisation state), streaming means, eval_fn
 //   gbp_capi_state.hip  checkpoints (host blob, device slot)
 //   gbp_capi_extend.hip growth of a live handle (gbp_ba_extend): the union's inputs, the state transplant
-//   gbp_capi_retire.hip shrinking of a live handle (gbp_ba_retire): renumbering maps, the survivors' inputs, transplant through maps, the fold
-//   gbp_capi_cull.hip   removal of single observations from a live handle (gbp_ba_cull): survival flags from a factor list, no fold
-//   gbp_capi_retire_lmk.hip  letting go of landmarks by name (gbp_ba_retire_landmarks): survival flags from a landmark list, the fold
-//                       into the cameras' priors
-//   gbp_capi_window.hip one window step (gbp_ba_window_step): extend + cull + retire + retire_landmarks in a single rebuild
-//                       (gbp_graft.hpp: what these share; from the survival flags on, the three shrinking calls go the same way)
+//   gbp_capi_window.hip every other rebuild of a live handle, on one engine: one window step (gbp_ba_window_step: extend + cull +
+//                       retire + retire_landmarks in a single rebuild) and the three calls that are one part of it alone (gbp_ba_cull,
+//                       gbp_ba_retire, gbp_ba_retire_landmarks)
+//                       (gbp_graft.hpp: what the two rebuilding units share)
 //
 // Kernels live with the unit that launches them (a __global__ defined in a header may be instantiated by one unit only: the
 // dynamic-LDS attributes of the fused sweep are set on the very function objects that are launched).

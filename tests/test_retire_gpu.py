@@ -389,6 +389,49 @@ def test_snapshot_is_dropped_and_means_stream_after_retirement(lib):
     e.close()
 
 
+def test_a_camera_without_a_factor_stays_under_retire_and_goes_under_cull(lib):
+    """gbp_ba_retire drops the cameras on its list and no other (include/gbp_ba.h step 2; retire_host: keep_c), every other shrinking call
+    drops a camera no staying factor names.  window_host.bare_camera_problem: camera 8 of 16 has no factor.  The prior rule gives such a
+    camera Lambda = 0 (a singular belief), so it gets the strongest prior the rule gave any camera, on the handle and on the host."""
+    from cull_host import cull_numpy_ba
+    from window_host import bare_camera_problem
+    from gbp_amd.engine import BAEngine
+    p, bare = bare_camera_problem(), 8
+
+    def pair():
+        e, nb = BAEngine.from_problem(p, loss='huber'), make_numpy_ba(p, loss='huber')
+        e.generate_priors_var(W)
+        nb.generate_priors_var(W)
+        pr = e.priors()
+        lam = pr[1][:, 0, 0].max()
+        pr[1][bare], pr[0][bare] = lam * np.eye(6), lam * p.cam_means[bare]
+        e.set_priors(*pr)
+        nb.cams[bare].prior.lam, nb.cams[bare].prior.eta = pr[1][bare].copy(), pr[0][bare].copy()
+        for x in (e, nb):
+            x.update_all_beliefs()
+            x.iterate(3)
+        return e, nb
+    e, nb = pair()
+    md, mh = e.retire([0]), retire_numpy_ba(nb, [0])
+    assert md[0][bare] >= 0 and md[0][0] == -1
+    for a, b in zip(md, mh):
+        np.testing.assert_array_equal(a, b)
+    assert (e.C, e.L, e.F) == (nb.C, nb.L, len(nb.graph.factors)) and e.check_layout() == 0
+    worst = _belief_gap(e, nb, 'retire', 0.0)
+    for s in range(3):
+        worst = _same_step(e, nb, s, worst)
+    print(f'bare camera, retire: worst belief gap {worst:.3e}')
+    e.close()
+    e, nb = pair()
+    md, mh = e.cull([100]), cull_numpy_ba(nb, [100])
+    assert md[0][bare] == -1 and (md[0] >= 0).sum() == 15
+    for a, b in zip(md, mh):
+        np.testing.assert_array_equal(a, b)
+    assert e.check_layout() == 0
+    _belief_gap(e, nb, 'cull', 0.0)
+    e.close()
+
+
 # ---- 7. failures leave the handle as it was --------------------------------------------------------------------------------------
 def test_failures_leave_the_handle_untouched(lib):
     from gbp_amd.engine import BAEngine

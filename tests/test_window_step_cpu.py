@@ -112,3 +112,22 @@ def test_the_lists_of_the_gpu_tests_have_their_properties():
     goes = check_case(c)
     assert c.base.n_cams == 16 and 0 < goes.sum() < c.base.n_factors
     assert len(c.batch['cam_means']) == 2 and (c.batch['cam_idx'] < 16).sum() > 50
+
+
+def test_the_shrinking_calls_live_in_the_window_unit():
+    """gbp_ba_cull, gbp_ba_retire and gbp_ba_retire_landmarks are fronts of the window step's engine (gbp_capi_window.hip): the library
+    is built from files that exist, still exports all four, and each refuses a null handle before it touches a device."""
+    from gbp_amd import build, _capi
+    for name in build.SOURCES + build.HEADERS:
+        assert os.path.isfile(os.path.join(build.CSRC, name)), name
+    assert len(set(build.SOURCES)) == len(build.SOURCES) and 'gbp_capi_window.hip' in build.SOURCES
+    unit = open(os.path.join(build.CSRC, 'gbp_capi_window.hip')).read()
+    build.build()
+    lib = _capi.load()
+    ids = np.zeros(1, np.int32)
+    for name, args in (('gbp_ba_cull', (1, _capi.iptr(ids), None, None, None)), ('gbp_ba_retire', (1, _capi.iptr(ids), None, None, None)),
+                       ('gbp_ba_retire_landmarks', (1, _capi.iptr(ids), _capi.RETIRE_FOLD, None, None, None)),
+                       ('gbp_ba_window_step', (ct.byref(_capi.Window()), None))):
+        assert re.search(r'^int %s\(' % name, unit, re.M), name
+        assert getattr(lib, name)(None, *args) == -1, name
+        assert b'null handle' in lib.gbp_last_error(), name

@@ -127,6 +127,9 @@ def test_equals_the_four_calls(lib, case, fused, fold):
 # ---- 2. each part alone is the old call -------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('part', ['cull', 'retire', 'lmks fold', 'lmks drop', 'batch'])
 def test_each_part_alone_is_the_old_call(lib, case, part):
+    """gbp_ba_cull, gbp_ba_retire and gbp_ba_retire_landmarks are fronts of the window step's engine: each beside a window step that
+    carries only its part compares a front with the engine it calls (and 'batch' compares gbp_ba_extend, a path of its own, with it).
+    Maps and the whole state blob byte for byte, after the call and after three more sweeps."""
     a, b = _pair(case.base, loss='huber')
     ident = lambda n: np.arange(n, dtype=np.int32)
     C, L, F = a.C, a.L, a.F

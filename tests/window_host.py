@@ -231,3 +231,16 @@ def hold_back(problem, rows):
     batch = dict(cam_means=np.zeros((0, 6)), lmk_means=np.zeros((0, 3)), meas=problem.meas[rows].copy(),
                  cam_idx=problem.cam_idx[rows].astype(np.int32), lmk_idx=problem.lmk_idx[rows].astype(np.int32))
     return base, batch
+
+
+def bare_camera_problem(cam=8):
+    """base_case()'s 16-camera base without every observation of camera `cam`: the camera is in the graph and has no factor; every other
+    camera and every landmark keeps one.  gbp_ba_retire keeps such a camera (it drops what is on its list, nothing else), every other
+    shrinking call drops it with the other variables no staying factor names."""
+    import dataclasses
+    p = base_case().base
+    keep = p.cam_idx != cam
+    q = dataclasses.replace(p, meas=p.meas[keep], cam_idx=p.cam_idx[keep], lmk_idx=p.lmk_idx[keep])
+    assert 0 < cam < p.n_cams - 1 and np.array_equal(np.unique(q.cam_idx), np.delete(np.arange(p.n_cams), cam))
+    assert np.unique(q.lmk_idx).size == p.n_lmks and (q.cam_idx == 0).sum() < q.n_factors
+    return q

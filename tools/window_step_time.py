@@ -5,8 +5,9 @@ one realistic step of a fixed-lag front end: append the 2 keyframes, cull the 0.
 
 Prints one JSON line and writes it to profiles/window_step_time.json (--out PATH: elsewhere): medians of WINDOW_REPS (5) runs with
 min - max, all in one process, each run on a fresh live handle in the same state -- the step as ONE window_step, and as extend, cull,
-retire, retire_landmarks with the ids carried through the maps (the time of the four calls alone, and with the id translation a front
-end then has to do on the host)."""
+retire, retire_landmarks with the ids carried through the maps (the time of the four calls alone, each call's own median with min - max,
+and with the id translation a front end then has to do on the host).  GBP_HIP_LIB (gbp_amd/_capi.py) names another build of the library
+to time beside this one."""
 import json
 import os
 import sys
@@ -98,7 +99,7 @@ def main():
     res = dict(before=dict(cams=int(p.n_cams), lmks=int(p.n_lmks), factors=int(p.n_factors)), after=sizes, step=counts, reps=reps,
                window_step_ms=ms(t_one), four_calls_ms=ms(t_four_calls), four_calls_with_id_translation_ms=ms(t_four),
                four_calls_each_ms=dict(zip(('extend', 'cull', 'retire', 'retire_landmarks'),
-                                           [round(1e3 * float(np.median(c)), 3) for c in zip(*parts)])))
+                                           [ms(c) for c in zip(*parts)])))
     line = json.dumps(res)
     print(line)
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
