@@ -162,6 +162,7 @@ SIGNATURES = {
     'gbp_lin_solve_map': (ct.c_int, [ct.c_void_p, ct.c_void_p, ct.c_void_p]),
     'gbp_lin_get_map': (ct.c_int, [ct.c_void_p, _dp]),
     'gbp_lin_map_distance': (ct.c_int, [ct.c_void_p, _dp]),
+    'gbp_lin_solve_marginals': (ct.c_int, [ct.c_void_p, _ip, ct.c_int32, ct.c_void_p, _dp, _dp, ct.c_void_p]),
     'gbp_ba_get_lmk_order': (ct.c_int, [ct.c_void_p, _ip]),
     'gbp_ba_fused_max_cams': (ct.c_int, []),
     'gbp_ba_plan_info': (ct.c_int, [ct.c_void_p, _ip, ct.c_int32]),
@@ -188,6 +189,13 @@ class LinMapInfo(ct.Structure):
     """gbp_lin_map_info_t (include/gbp_lin.h)."""
     _fields_ = [('iters', ct.c_int32), ('converged', ct.c_int32), ('rel_residual', ct.c_double), ('eta_norm', ct.c_double)]
 
+
+class LinMargInfo(ct.Structure):
+    """gbp_lin_marg_info_t (include/gbp_lin.h)."""
+    _fields_ = [('iters', ct.c_int32), ('converged', ct.c_int32), ('batches', ct.c_int32), ('reserved', ct.c_int32), ('rel_residual', ct.c_double)]
+
+
+LIN_MARG_COLS = 8
 
 _lib = None
 

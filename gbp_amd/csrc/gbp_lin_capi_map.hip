@@ -162,6 +162,10 @@ int map_download(gbp_lin *h, const double *src, double *dst)
 
 }  // namespace
 
+namespace gbp {
+int lin_map_prepare(gbp_lin *h) { return map_prepare(h); }
+}
+
 extern "C" {
 
 int gbp_lin_joint_matvec(gbp_lin_t *h, const double *x, double *y)

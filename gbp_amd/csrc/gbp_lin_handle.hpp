@@ -2,6 +2,7 @@
 // handle behind gbp_lin_t, the error / entry macros and the two host helpers every entry point uses.
 //   gbp_lin_capi.hip       create / destroy, the sweep (k_lin_factor, k_lin_belief), energy, getters
 //   gbp_lin_capi_map.hip   the batch MAP by block-Jacobi conjugate gradients (kernels in gbp_lin_map.hpp)
+//   gbp_lin_capi_marg.hip  exact marginal covariances by the same iteration on 8 columns at a time (kernels in gbp_lin_marg.hpp)
 #pragma once
 #include "../../include/gbp_ba.h"
 #include "../../include/gbp_lin.h"
@@ -44,6 +45,17 @@ struct LinMap {
     int nb;                          // blocks of every per-variable kernel = number of partials
 };
 
+// Multi-column workspace of the marginal covariances (gbp_lin_marg.hpp), K = GBP_LIN_MARG_COLS columns innermost: device memory owned by
+// gbp_lin::allocs, allocated by the first gbp_lin_solve_marginals of a handle.  The LDL^T of the diagonal blocks is LinMap's.
+struct LinMarg {
+    double *x, *r, *z, *p, *q;       // [N][D][K] each
+    double *ebuf;                    // [2F][D][K]
+    double *pq_part, *rz_part, *rr_part;   // [nb][K], [2][nb][K], [nb][K]: per-block, per-column partial sums
+    int nb;                          // blocks of every per-variable kernel
+    void *stage;                     // the outputs (sigma | sigma_joint) then the ids of the call in progress; grows as calls need
+    size_t stage_bytes;
+};
+
 }  // namespace gbp
 
 using namespace gbp;
@@ -59,6 +71,8 @@ struct gbp_lin {
     LinMap map{};                    // gbp_lin_capi_map.hip
     bool map_ready = false, map_solved = false;
     double map_eta_norm = 0.0;
+    LinMarg marg{};                  // gbp_lin_capi_marg.hip
+    bool marg_ready = false;
 };
 
 #define LHIPCHK(expr)                                                                                       \
@@ -74,6 +88,10 @@ struct gbp_lin {
         if (!(h)) return set_error(GBP_EINVAL, "NULL handle");                           \
         LHIPCHK(hipSetDevice((h)->device));                                              \
     } while (0)
+
+namespace gbp {
+int lin_map_prepare(gbp_lin *h);                    // gbp_lin_capi_map.hip: LinMap's workspace, LDL^T and joint eta, once per handle
+}
 
 template <typename T>
 static int lin_upload(gbp_lin *h, T **out, const std::vector<T> &v)

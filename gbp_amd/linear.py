@@ -140,5 +140,32 @@ class LinearEngine:
         check(self._lib.gbp_lin_map_distance(self._h, ct.byref(out)))
         return out.value
 
+    # exact marginal covariances (the sigma of joint_distribution_cov gbp.py:128-144), by the same iteration on 8 columns at a time
+    def marginals(self, ids=None, rel_tol=1e-12, max_iters=10000, check_every=8, joint=False):
+        """Blocks of Lambda_joint^-1: (sigma (M, d, d), info), sigma[i] the marginal covariance of variable ids[i] (None: all
+        variables); with joint=True (sigma, sigma_joint (M d, M d), info), sigma_joint the inverse restricted to ids x ids.  Neither is
+        symmetrised.  info: iters (summed over the batches of 8 columns), converged, batches, rel_residual (the worst column's true
+        residual).  max_iters is per batch; running out of it is not an error."""
+        if ids is None:
+            ids = np.arange(self.N, dtype=np.int32)
+        else:
+            wide = np.asarray(ids, dtype=np.int64).reshape(-1)
+            if wide.size and (wide.min() < -2 ** 31 or wide.max() >= 2 ** 31):
+                raise ValueError("variable ids must fit int32")   # before the cast below can wrap them into range
+            ids = i32(wide)
+        M = ids.shape[0]
+        sigma = np.zeros((M, self.D, self.D))
+        sj = np.zeros((M * self.D, M * self.D)) if joint else None
+        o = _capi.LinMapOpts(float(rel_tol), int(max_iters), int(check_every), 0)
+        i = _capi.LinMargInfo()
+        check(self._lib.gbp_lin_solve_marginals(self._h, iptr(ids), M, ct.byref(o), dptr(sigma), dptr(sj), ct.byref(i)))
+        info = {'iters': i.iters, 'converged': bool(i.converged), 'batches': i.batches, 'rel_residual': i.rel_residual}
+        return (sigma, sj, info) if joint else (sigma, info)
+
+    def belief_covariances(self):
+        """(N, d, d): the inverses of the belief Lambdas of beliefs(), taken on the host -- what GBP holds for marginals()."""
+        _, lam = self.beliefs()
+        return np.linalg.inv(lam) if self.N else lam
+
     def sync(self):
         check(self._lib.gbp_lin_sync(self._h))

@@ -13,6 +13,9 @@
  * Variables and factors keep the caller's numbering; a variable's adjacency order (the order its
  * belief adds messages in, VariableNode.adj_factors gbp.py:160) is ascending factor id, which is what
  * ndim_posegraph.py:86-88 produces.
+ *
+ * Beside the sweep: the batch MAP (the `mu` of FactorGraph.joint_distribution_cov) and exact marginal covariances (its `sigma`, for
+ * chosen variables), both by block-Jacobi conjugate gradients on the block-sparse joint -- below.
  */
 #ifndef GBP_LIN_H
 #define GBP_LIN_H
@@ -73,6 +76,33 @@ int  gbp_lin_joint_eta(gbp_lin_t *h, double *eta);                              
 int  gbp_lin_solve_map(gbp_lin_t *h, const gbp_lin_map_opts_t *opts, gbp_lin_map_info_t *info);   /* joint_distribution_cov's mu gbp.py:128-144; stays on the device */
 int  gbp_lin_get_map(gbp_lin_t *h, double *mu);                                 /* N x d, the solution of the last solve (gbp.py:139-144); GBP_ESTATE before one   */
 int  gbp_lin_map_distance(gbp_lin_t *h, double *out);                           /* |means - map|_2 on the device (gbp.py:94-144, ndim_posegraph.py:108); GBP_ESTATE without beliefs or a solve */
+
+/* ---- exact marginal covariances: the `sigma` of FactorGraph.joint_distribution_cov (gbp.py:128-144) for chosen variables ----
+ * Block (ids[i], ids[i]) of Lambda_joint^-1 -- and, on request, Lambda_joint^-1 restricted to ids x ids -- without the dense inverse:
+ * column c = (ids[c / d], c % d) of the inverse solves Lambda x = e_c (a unit right-hand side), by the conjugate gradients above run on
+ * GBP_LIN_MARG_COLS columns at a time, in order, each column with scalars of its own; one pass over the factors per iteration serves
+ * the whole batch.  The last batch is padded with zero right-hand sides, which stay exactly zero.
+ *
+ * opts as for gbp_lin_solve_map (NULL = the same defaults, the same GBP_EINVAL rules); warm_start must be 0 (GBP_EINVAL).  max_iters is
+ * per batch.  A batch iterates until EVERY column has |e - Lambda x| <= rel_tol; the recurrence's residuals are read every check_every
+ * iterations (every iteration without factors); when all columns claim convergence or max_iters runs out the true residuals are formed
+ * with one more multi-column product, and the recurrence restarts from them if a claim was wrong.
+ * gbp_lin_marg_info_t: iters summed over the batches; converged = 1 only if every column of every batch passed (0 with GBP_OK when
+ * max_iters ran out); rel_residual = the worst column's true residual; batches = ceil(n_ids d / GBP_LIN_MARG_COLS).  info may be NULL.
+ * sigma[i] holds rows ids[i] of that variable's d columns, sigma_joint rows ids[*] of all columns, both as computed (not symmetrised)
+ * and gathered on the device: the N d-long columns never cross to the host.
+ * n_ids == 0: GBP_OK, nothing written, info {0, 1, 0, 0, 0.0}.  ids NULL with n_ids > 0, sigma NULL, an id out of range or listed twice:
+ * GBP_EINVAL.  The call neither reads nor writes the sweep's state, and leaves the MAP solver's alone (gbp_lin_get_map returns the
+ * same bits before and after); it shares the LDL^T of the diagonal blocks and has a workspace of its own (8 x that of the MAP solver),
+ * allocated on first use and freed with the handle; the device staging of the outputs is kept with it and grows to the largest call
+ * seen, so a repeated call allocates nothing.  No floating-point atomics: two identical calls on one handle are bit-identical. */
+#define GBP_LIN_MARG_COLS 8
+typedef struct { int32_t iters, converged, batches, reserved; double rel_residual; } gbp_lin_marg_info_t;
+
+int  gbp_lin_solve_marginals(gbp_lin_t *h, const int32_t *ids, int32_t n_ids, const gbp_lin_map_opts_t *opts,
+                             double *sigma,        /* n_ids x d x d: block (ids[i], ids[i]) of Lambda_joint^-1                   */
+                             double *sigma_joint,  /* NULL, or (n_ids d) x (n_ids d): Lambda_joint^-1 restricted to ids x ids   */
+                             gbp_lin_marg_info_t *info);
 
 #ifdef __cplusplus
 }

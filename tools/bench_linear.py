@@ -6,7 +6,7 @@ linear_displacement factor (gbp/factors/linear_displacement.py:8-14).  Prints on
 Algorithmic bytes per sweep (fp64, packed symmetric, P = d(d+1)/2): per factor read Lambda_f d(2d+1) + eta_f 2d +
 two belief records 2(d+P) + two old messages 2(d+P), write two messages 2(d+P), and the belief stage reads them again
 2(d+P); per variable prior d+P read, d+P+d written."""
-import argparse, json, os, sys, time
+import argparse, json, os, statistics, sys, time
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 from gbp_amd.linear import LinearEngine
@@ -19,20 +19,119 @@ ap.add_argument('--steps', type=int, default=100)
 ap.add_argument('--warmup', type=int, default=10)
 ap.add_argument('--no-cpu-baseline', action='store_true')
 ap.add_argument('--map', action='store_true', help='after the timed sweeps, solve the batch MAP (cold) and report the distance of the means from it')
+ap.add_argument('--marginals', action='store_true',
+                help='instead of the run above: on the two 1M-factor graphs (the defaults, and --vars 1000000 --k 1) time one multi-column CG iteration '
+                     'of gbp_lin_solve_marginals (8 columns) against one of gbp_lin_solve_map, and the sweeps, in one session; writes profiles/linear_marginals.json')
+ap.add_argument('--repeats', type=int, default=5, help='--marginals: repeats per timing (the median is reported)')
 a = ap.parse_args()
-rs = np.random.RandomState(0)
+
+
+def ring(N, D, k, rs):
+    mu0 = rs.rand(N, D) * 10
+    va = np.repeat(np.arange(N), k)
+    vb = (va + np.tile(np.arange(1, k + 1), N)) % N
+    z = mu0[vb] - mu0[va] + rs.normal(0, 1.0, (va.shape[0], D))
+    J = np.hstack([-np.eye(D), np.eye(D)])
+    return (va, vb, z @ J, np.ascontiguousarray(np.broadcast_to(J.T @ J, (va.shape[0], 2 * D, 2 * D))), mu0 / 3.0,
+            np.ascontiguousarray(np.broadcast_to(np.eye(D) / 3.0, (N, D, D)))), 0.5 * np.einsum('fd,fd->f', z, z)
+
+
+def marginals_profile():
+    """Host clock around DIRECT calls of the two C entry points, each of which ends in a stream synchronise (no device events in the
+    ABI); every figure is the median of --repeats calls after a warm-up call of the same shape, the two solvers alternating.
+    gbp_lin_solve_map is timed by itself: no download of the solution.  gbp_lin_solve_marginals is one batch (2 ids x 3 dofs = 6 live
+    columns and 2 zero ones, which run the same instructions) and brings back 18 doubles; its staging buffer exists after the warm-up,
+    so a timed call allocates nothing.
+    Two figures per solver.  per_iter: the difference between a solve cut at max_iters = 40 and one cut at 8, over 32 -- four kernels
+    per iteration and one read-back of the partial |r|^2 every 8, and nothing else: what both calls do once (the memset of x, the
+    first residual, the true-residual product at the end, and for the marginals the gather and the 18-double copy) cancels.
+    whole_solve: a solve to rel_tol 1e-12 over its iterations, with all of that in."""
+    import ctypes as ct
+    from gbp_amd import _capi
+    D, runs = 3, []
+    lo, hi = 8, 40
+    for N, k in ((200_000, 5), (1_000_000, 1)):
+        g, fc = ring(N, D, k, np.random.RandomState(0))
+        F = g[0].shape[0]
+        e = LinearEngine(*g, factor_const=fc)
+        e.update_all_beliefs()
+        e.iterate(a.warmup); e.sync()
+        ids, sigma = _capi.i32([N // 3, 7]), np.zeros((2, D, D))
+
+        def sweeps():
+            t = time.perf_counter(); e.iterate(a.steps); e.sync()
+            return (time.perf_counter() - t) / a.steps
+
+        def single(max_iters):
+            o, i = _capi.LinMapOpts(1e-12, max_iters, 8, 0), _capi.LinMapInfo()
+            t = time.perf_counter(); rc = e._lib.gbp_lin_solve_map(e._h, ct.byref(o), ct.byref(i)); t = time.perf_counter() - t
+            _capi.check(rc)
+            return t, i
+
+        def multi(max_iters):
+            o, i = _capi.LinMapOpts(1e-12, max_iters, 8, 0), _capi.LinMargInfo()
+            t = time.perf_counter()
+            rc = e._lib.gbp_lin_solve_marginals(e._h, _capi.iptr(ids), 2, ct.byref(o), _capi.dptr(sigma), None, ct.byref(i))
+            t = time.perf_counter() - t
+            _capi.check(rc)
+            return t, i
+        single(10000); multi(10000)                         # workspaces, LDL^T, staging, code objects
+        sw0 = [sweeps() for _ in range(a.repeats)]
+        rec = {key: [] for key in ('s_lo', 's_hi', 's_full', 'm_lo', 'm_hi', 'm_full')}
+        for _ in range(a.repeats):                          # alternating
+            for key, fn, n in (('s_lo', single, lo), ('m_lo', multi, lo), ('s_hi', single, hi), ('m_hi', multi, hi),
+                               ('s_full', single, 10000), ('m_full', multi, 10000)):
+                t, i = fn(n)
+                assert i.iters == n or n == 10000, (key, i.iters)
+                rec[key].append((t, i.iters))
+            i1, i8 = rec['s_full'][-1][1], rec['m_full'][-1][1]
+        conv = single(10000)[1].converged, multi(10000)[1]
+        med = {key: statistics.median(t for t, _ in v) for key, v in rec.items()}
+        t_single, t_multi = (med['s_hi'] - med['s_lo']) / (hi - lo), (med['m_hi'] - med['m_lo']) / (hi - lo)
+        w_single, w_multi = med['s_full'] / i1, med['m_full'] / i8
+        sw1 = [sweeps() for _ in range(a.repeats)]
+        runs.append({"vars": N, "dofs": D, "k": k, "factors": F,
+                     "per_iter": {"ms_map": 1e3 * t_single, "ms_marginals_8_columns": 1e3 * t_multi, "ratio_per_column": t_multi / (8.0 * t_single),
+                                  "cut_at_iterations": [lo, hi],
+                                  "ms_solve_map_cut": {str(lo): [1e3 * t for t, _ in rec['s_lo']], str(hi): [1e3 * t for t, _ in rec['s_hi']]},
+                                  "ms_solve_marginals_cut": {str(lo): [1e3 * t for t, _ in rec['m_lo']], str(hi): [1e3 * t for t, _ in rec['m_hi']]}},
+                     "whole_solve": {"ms_map_per_iter": 1e3 * w_single, "map_iters": i1, "map_converged": bool(conv[0]),
+                                     "ms_marginals_per_iter_8_columns": 1e3 * w_multi, "marginals_iters": i8, "marginals_converged": bool(conv[1].converged),
+                                     "marginals_rel_residual": conv[1].rel_residual, "ratio_per_column": w_multi / (8.0 * w_single),
+                                     "ms_solve_map": [1e3 * t for t, _ in rec['s_full']], "ms_solve_marginals": [1e3 * t for t, _ in rec['m_full']]},
+                     "ratio_derived_from_factor_traffic": traffic_ratio(D, 0.0), "ratio_derived_with_variable_traffic": traffic_ratio(D, 1.0 / k),
+                     "sweeps_per_s_before": 1.0 / statistics.median(sw0), "sweeps_per_s_after": 1.0 / statistics.median(sw1),
+                     "sweeps_per_s_all": [1.0 / t for t in sw0 + sw1]})
+        e.close()
+    out = {"what": "tools/bench_linear.py --marginals on one MI355X: one iteration of gbp_lin_solve_marginals (8 columns at a time) against one of "
+                   "gbp_lin_solve_map, and gbp_lin_iterate before and after, in one session; ratio_per_column = t_multi / (8 t_single)",
+           "method": " ".join(marginals_profile.__doc__.split()), "traffic": " ".join(traffic_ratio.__doc__.split()),
+           "repeats": a.repeats, "sweep_steps": a.steps, "runs": runs}
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'profiles', 'linear_marginals.json')
+    with open(path, 'w') as fh:
+        json.dump(out, fh, indent=1)
+        fh.write('\n')
+    print(json.dumps(out))
+
+
+def traffic_ratio(D, vars_per_factor):
+    """Doubles moved per factor and iteration, 8 columns together over 8 single solves.  Per factor: Lambda_f d(2d+1), read once by
+    either; per column the gather of p 2d, the edge buffer written and read 4d.  Per variable (vars_per_factor = N / F; 0 leaves this
+    part out, which is the bound of the design): per column p, q in the product, x, r, p, q read and x, r, z written in the step, z, p
+    read and p written in the direction: 12d; shared by the columns: the prior block d(d+1)/2 and the LDL^T d(d+1)/2 + d."""
+    P = D * (D + 1) // 2
+    lam, col = D * (2 * D + 1), 6 * D + vars_per_factor * 12 * D
+    shared = vars_per_factor * (2 * P + D)
+    return (lam + shared + 8 * col) / (8.0 * (lam + shared + col))
+
+
+if a.marginals:
+    marginals_profile()
+    sys.exit(0)
 N, D, k = a.vars, a.dofs, a.k
-mu0 = rs.rand(N, D) * 10
-va = np.repeat(np.arange(N), k)
-vb = (va + np.tile(np.arange(1, k + 1), N)) % N
+(va, vb, fe, fl, pe, pl), fc = ring(N, D, k, np.random.RandomState(0))
 F = va.shape[0]
-z = mu0[vb] - mu0[va] + rs.normal(0, 1.0, (F, D))
-J = np.hstack([-np.eye(D), np.eye(D)])
-fe = z @ J                                  # J^T z per factor, sigma = 1
-fl = np.broadcast_to(J.T @ J, (F, 2 * D, 2 * D))
-fc = 0.5 * np.einsum('fd,fd->f', z, z)
-pl = np.broadcast_to(np.eye(D) / 3.0, (N, D, D))
-e = LinearEngine(va, vb, fe, np.ascontiguousarray(fl), mu0 / 3.0, np.ascontiguousarray(pl), factor_const=fc)
+e = LinearEngine(va, vb, fe, fl, pe, pl, factor_const=fc)
 e.update_all_beliefs()
 e.iterate(a.warmup); e.sync()
 t0 = time.perf_counter(); e.iterate(a.steps); e.sync(); dt = time.perf_counter() - t0
@@ -55,7 +154,7 @@ if not a.no_cpu_baseline:
     from oracle.linear_oracle import LinearOracle
     n_s = 400
     sel = (va < n_s - k)
-    o = LinearOracle(va[sel], vb[sel], fe[sel], np.ascontiguousarray(fl[sel]), (mu0 / 3.0)[:n_s], np.ascontiguousarray(pl[:n_s]), factor_const=fc[sel])
+    o = LinearOracle(va[sel], vb[sel], fe[sel], np.ascontiguousarray(fl[sel]), pe[:n_s], np.ascontiguousarray(pl[:n_s]), factor_const=fc[sel])
     o.update_all_beliefs(); o.synchronous_iteration()
     tc = time.perf_counter(); o.iterate(3); tc = (time.perf_counter() - tc) / 3
     us_per_factor = 1e6 * tc / int(sel.sum())
