@@ -163,6 +163,10 @@ SIGNATURES = {
     'gbp_lin_get_map': (ct.c_int, [ct.c_void_p, _dp]),
     'gbp_lin_map_distance': (ct.c_int, [ct.c_void_p, _dp]),
     'gbp_lin_solve_marginals': (ct.c_int, [ct.c_void_p, _ip, ct.c_int32, ct.c_void_p, _dp, _dp, ct.c_void_p]),
+    'gbp_lin_set_robust': (ct.c_int, [ct.c_void_p, _ip, _dp, _dp]),
+    'gbp_lin_robustify': (ct.c_int, [ct.c_void_p]),
+    'gbp_lin_iterate_robust': (ct.c_int, [ct.c_void_p, ct.c_int32]),
+    'gbp_lin_get_weights': (ct.c_int, [ct.c_void_p, _dp, _ip]),
     'gbp_ba_get_lmk_order': (ct.c_int, [ct.c_void_p, _ip]),
     'gbp_ba_fused_max_cams': (ct.c_int, []),
     'gbp_ba_plan_info': (ct.c_int, [ct.c_void_p, _ip, ct.c_int32]),
@@ -196,6 +200,7 @@ class LinMargInfo(ct.Structure):
 
 
 LIN_MARG_COLS = 8
+LIN_LOSS = {None: 0, 'huber': 1, 'constant': 2}     # GBP_LIN_LOSS_* (include/gbp_lin.h)
 
 _lib = None
 

@@ -13,6 +13,7 @@
 // (eta | packed Lambda | mu) gathered per factor.  Lambda_f is constant: packed upper 2d x 2d, read every sweep.
 // HBM-bound like the BA sweep; d <= 6 keeps a factor's working set in registers (one wave per SIMD for d = 6).
 #include "gbp_lin_handle.hpp"
+#include "gbp_lin_robust.hpp"
 #include "gbp_math.hpp"
 
 #include <hip/hip_runtime.h>
@@ -58,7 +59,9 @@ GBP_DEV void lin_schur(const double (&akk)[Sym<D>::size], const double (&akn)[D]
     }
 }
 
-template <int D>
+// ROBUST: the factor is the stored nominal one times its weight p.w[f] (gbp_lin_robust.hpp; gbp.py:331-332), applied on load.  A handle
+// without losses launches only the `false` instantiation, which reads no weight.
+template <int D, bool ROBUST>
 __global__ __launch_bounds__(64) void k_lin_factor(LinParams p)
 {
     constexpr int P = LinDims<D>::P, REC = LinDims<D>::REC, R = D + P;
@@ -113,6 +116,17 @@ __global__ __launch_bounds__(64) void k_lin_factor(LinParams p)
         }
 #pragma unroll
         for (int j = 0; j < D; ++j) { const double v = p.flam[(size_t)Sym<2 * D>::at(i, D + j) * F + f]; aab[i][j] = v; aba[j][i] = v; }
+    }
+    if constexpr (ROBUST) {
+        const double w = p.w[f];
+#pragma unroll
+        for (int k = 0; k < D; ++k) { fa[k] *= w; fb[k] *= w; }
+#pragma unroll
+        for (int k = 0; k < P; ++k) { aaa[k] *= w; abb[k] *= w; }
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int j = 0; j < D; ++j) { aab[i][j] *= w; aba[j][i] = aab[i][j]; }
     }
     const double d = p.damping;
     double lam[P], eta[D], S[P], en[D];
@@ -185,70 +199,17 @@ __global__ __launch_bounds__(64) void k_lin_belief(LinParams p)
     }
 }
 
-// sum over factors of 0.5 |h(mu) - z|^2 / sigma^2 for linear h (gbp.py:36-44, 251-265), from (Lambda_f, eta_f, const) without
-// the cancellation of the expanded 0.5 x^T Lambda_f x - eta_f^T x + const (terms of |x|^2 / sigma^2 that cancel to the residual:
-// map coordinates with centimetre noise lose every digit).  A pivoted LDL^T of Lambda_f, stopped at a relative pivot tolerance
-// (a factor has rank m <= 2d), writes Lambda_f = sum_k d_k l_k l_k^T and eta_f = sum_k d_k y_k l_k, so the energy is
-//   0.5 sum_k d_k (l_k^T x - y_k)^2 + (const - 0.5 sum_k d_k y_k^2)
-// whose squares are of residuals.  For linear_displacement (Lambda_f = [I -I; -I I] / sigma^2) l_k^T x = x_a - x_b exactly.
+// sum over factors of w_f 0.5 |h(mu) - z|^2 / sigma^2 for linear h (gbp.py:36-44, 251-265; w_f = sigma^2 / adaptive_gauss_noise_var, 1 on a
+// handle without losses): the per-factor term is lin_factor_energy (gbp_lin_robust.hpp), the residual form without cancellation.
 template <int D>
 __global__ __launch_bounds__(256) void k_lin_energy(LinParams p, double *out)
 {
-    constexpr int P = LinDims<D>::P, REC = LinDims<D>::REC, N2 = 2 * D;
     __shared__ double red[256 / 64];
     const int f = blockIdx.x * 256 + threadIdx.x;
     double e = 0.0;
     if (f < p.F) {
-        const size_t F = (size_t)p.F;
-        double x[N2], eta[N2], a[Sym<N2>::size];
-        const double *ra = p.bel + (size_t)p.va[f] * REC + D + P, *rb = p.bel + (size_t)p.vb[f] * REC + D + P;
-#pragma unroll
-        for (int k = 0; k < D; ++k) { x[k] = ra[k]; x[D + k] = rb[k]; }
-#pragma unroll
-        for (int i = 0; i < N2; ++i) eta[i] = p.feta[i * F + f];
-#pragma unroll
-        for (int i = 0; i < Sym<N2>::size; ++i) a[i] = p.flam[(size_t)i * F + f];
-        double amax = 0.0;
-#pragma unroll
-        for (int i = 0; i < N2; ++i) amax = fmax(amax, a[Sym<N2>::at(i, i)]);
-        const double tol = N2 * 64 * __DBL_EPSILON__ * amax;
-        double cst = p.fconst ? p.fconst[f] : 0.0, sq = 0.0;
-        int done = 0;                                         // bit i: index i already eliminated
-#pragma unroll 1
-        for (int step = 0; step < N2; ++step) {
-            int piv = -1;
-            double dk = tol;
-#pragma unroll
-            for (int i = 0; i < N2; ++i)
-                if (!((done >> i) & 1) && a[Sym<N2>::at(i, i)] > dk) { dk = a[Sym<N2>::at(i, i)]; piv = i; }
-            if (piv < 0) break;                               // the rest of Lambda_f is rounding: rank reached
-            // column piv over the live indices (register arrays: selected, never indexed by piv)
-            double col[N2], raw[N2], zk = 0.0, lx = 0.0;
-#pragma unroll
-            for (int i = 0; i < N2; ++i) {
-                double c = 0.0;
-#pragma unroll
-                for (int j = 0; j < N2; ++j)
-                    if (j == piv) c = a[Sym<N2>::at(i < j ? i : j, i < j ? j : i)];
-                const bool live = !((done >> i) & 1) && i != piv;
-                raw[i] = live ? c : 0.0;
-                col[i] = live ? c / dk : 0.0;                 // l_k (exactly -1 / 0 for a displacement factor)
-                if (i == piv) { zk = eta[i]; lx = x[i]; }
-            }
-#pragma unroll
-            for (int i = 0; i < N2; ++i) lx += col[i] * x[i];
-            const double yk = zk / dk, t = lx - yk;
-            sq += 0.5 * dk * t * t;
-            cst -= 0.5 * zk * yk;
-#pragma unroll
-            for (int i = 0; i < N2; ++i) {
-                eta[i] -= col[i] * zk;
-#pragma unroll
-                for (int j = i; j < N2; ++j) a[Sym<N2>::at(i, j)] -= col[i] * raw[j];
-            }
-            done |= 1 << piv;
-        }
-        e = cst + sq;
+        e = lin_factor_energy<D>(p, f);
+        if (p.w) e *= p.w[f];
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) e += __shfl_down(e, off, 64);
@@ -270,6 +231,18 @@ static int lin_beliefs(gbp_lin *h)
     return GBP_OK;
 }
 
+namespace gbp {
+int lin_sweep(gbp_lin *h)
+{
+    if (h->p.F) lin_dispatch(h->D, [&](auto d) {
+        constexpr int DD = decltype(d)::value;
+        if (h->p.w) hipLaunchKernelGGL((k_lin_factor<DD, true>), dim3((h->p.F + 63) / 64), dim3(64), 0, h->stream, h->p);
+        else hipLaunchKernelGGL((k_lin_factor<DD, false>), dim3((h->p.F + 63) / 64), dim3(64), 0, h->stream, h->p);
+    });
+    return lin_beliefs(h);
+}
+}  // namespace gbp
+
 static int lin_create_impl(gbp_lin *h, const gbp_lin_desc_t *d)
 {
     const int N = d->n_vars, F = d->n_factors, D = d->dofs;
@@ -285,6 +258,7 @@ static int lin_create_impl(gbp_lin *h, const gbp_lin_desc_t *d)
         return set_error(GBP_ENODEV, "device %d is %s; this library is built for gfx950 (MI355X) only", h->device, prop.gcnArchName);
     LHIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     h->D = D;
+    h->has_const = d->factor_const != nullptr;
     const int P = D * (D + 1) / 2, P2 = D * (2 * D + 1), D2 = 2 * D;
     LinParams &p = h->p;
     p.N = N; p.F = F; p.damping = d->eta_damping;
@@ -385,12 +359,7 @@ int gbp_lin_iterate(gbp_lin_t *h, int32_t n_iters)
     LENTER(h);
     if (n_iters < 0) return set_error(GBP_EINVAL, "negative iteration count");
     if (!h->has_beliefs) return set_error(GBP_ESTATE, "call gbp_lin_update_beliefs first (ndim_posegraph.py:90)");
-    for (int it = 0; it < n_iters; ++it) {
-        if (h->p.F) lin_dispatch(h->D, [&](auto d) {
-            hipLaunchKernelGGL((k_lin_factor<decltype(d)::value>), dim3((h->p.F + 63) / 64), dim3(64), 0, h->stream, h->p);
-        });
-        LCHK(lin_beliefs(h));
-    }
+    for (int it = 0; it < n_iters; ++it) LCHK(lin_sweep(h));       // with losses set: at the weights as they stand (robustify=False)
     LHIPCHK(hipGetLastError());
     return GBP_OK;
 }

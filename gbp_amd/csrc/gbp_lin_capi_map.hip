@@ -1,8 +1,9 @@
 // gbp_lin_capi_map.hip -- the batch MAP entry points of include/gbp_lin.h: FactorGraph.joint_distribution_inf / _cov (gbp.py:94-144) on
 // the device, by block-Jacobi conjugate gradients over the handle's own arrays (kernels and method: gbp_lin_map.hpp).
 //
-// The engine has no setters, so the joint system of a handle never changes: the diagonal-block factors and the joint eta are made once,
-// by the first call that needs them, together with the workspace (all of it freed with the handle through `allocs`).  A solve queues
+// The joint system of a handle changes only with its robust weights (gbp_lin_capi_robust.hip): the diagonal-block factors and the joint
+// eta are made by the first call that needs them, and again after the weights changed; the workspace once (all of it freed with the
+// handle through `allocs`).  A solve queues
 // four kernels per iteration on the handle's stream and reads |r|^2 back only every `check_every` iterations; when the recurrence claims
 // convergence (or max_iters runs out) the TRUE residual eta - Lambda x is formed with one more product, and the recurrence restarts from
 // it if the claim was wrong.  Nothing here touches the sweep's state (messages, beliefs, has_beliefs).
@@ -36,21 +37,26 @@ int map_read_sum(gbp_lin *h, const double *part, double *out)
     return GBP_OK;
 }
 
-// workspace, LDL^T of the diagonal blocks, joint eta and its norm: once per handle
+// the workspace: once per handle.  LDL^T of the diagonal blocks, joint eta and its norm: by the first call that needs them, and again
+// -- into the same workspace, nothing allocated -- by the first call after the robust weights changed (gbp_lin_capi_robust.hip clears
+// map_ready).  The iterate x of the last solve is not touched.
 int map_prepare(gbp_lin *h)
 {
     if (h->map_ready) return GBP_OK;
     LinMap &m = h->map;
     const int D = h->D, P = D * (D + 1) / 2;
     const size_t nd = (size_t)h->p.N * D;
-    m.nb = std::min(MAP_MAX_BLOCKS, std::max(1, (h->p.N + MAP_BLOCK - 1) / MAP_BLOCK));
-    LCHK(map_alloc(h, &m.ldl, (size_t)h->p.N * (P + D))); LCHK(map_alloc(h, &m.jeta, nd));
-    LCHK(map_alloc(h, &m.x, nd)); LCHK(map_alloc(h, &m.r, nd)); LCHK(map_alloc(h, &m.z, nd)); LCHK(map_alloc(h, &m.p, nd)); LCHK(map_alloc(h, &m.q, nd));
-    LCHK(map_alloc(h, &m.ebuf, (size_t)2 * h->p.F * D));
-    LCHK(map_alloc(h, &m.pq_part, (size_t)m.nb)); LCHK(map_alloc(h, &m.rz_part, (size_t)2 * m.nb)); LCHK(map_alloc(h, &m.rr_part, (size_t)m.nb));
-    LHIPCHK(hipMemsetAsync(m.pq_part, 0, (size_t)m.nb * sizeof(double), h->stream));
-    LHIPCHK(hipMemsetAsync(m.rz_part, 0, (size_t)2 * m.nb * sizeof(double), h->stream));
-    LHIPCHK(hipMemsetAsync(m.rr_part, 0, (size_t)m.nb * sizeof(double), h->stream));
+    if (!h->map_alloc) {
+        m.nb = std::min(MAP_MAX_BLOCKS, std::max(1, (h->p.N + MAP_BLOCK - 1) / MAP_BLOCK));
+        LCHK(map_alloc(h, &m.ldl, (size_t)h->p.N * (P + D))); LCHK(map_alloc(h, &m.jeta, nd));
+        LCHK(map_alloc(h, &m.x, nd)); LCHK(map_alloc(h, &m.r, nd)); LCHK(map_alloc(h, &m.z, nd)); LCHK(map_alloc(h, &m.p, nd)); LCHK(map_alloc(h, &m.q, nd));
+        LCHK(map_alloc(h, &m.ebuf, (size_t)2 * h->p.F * D));
+        LCHK(map_alloc(h, &m.pq_part, (size_t)m.nb)); LCHK(map_alloc(h, &m.rz_part, (size_t)2 * m.nb)); LCHK(map_alloc(h, &m.rr_part, (size_t)m.nb));
+        LHIPCHK(hipMemsetAsync(m.pq_part, 0, (size_t)m.nb * sizeof(double), h->stream));
+        LHIPCHK(hipMemsetAsync(m.rz_part, 0, (size_t)2 * m.nb * sizeof(double), h->stream));
+        LHIPCHK(hipMemsetAsync(m.rr_part, 0, (size_t)m.nb * sizeof(double), h->stream));
+        h->map_alloc = true;
+    }
     double ee = 0.0;
     if (h->p.N) {
         lin_dispatch(D, [&](auto d) {

@@ -1,0 +1,153 @@
+// gbp_lin_capi_robust.hip -- the robust-loss entry points of include/gbp_lin.h: Factor(loss=, mahalanobis_threshold=),
+// Factor.robustify_loss (gbp.py:296-332), FactorGraph.robustify_all_factors (gbp.py:82-84) and synchronous_iteration(robustify=True)
+// (gbp.py:86-92) for the linear engine (kernels and semantics: gbp_lin_robust.hpp).
+//
+// The handle keeps its nominal factors; what a loss changes is one weight per factor, LinParams::w, which every user of
+// (eta_f, Lambda_f) multiplies in: the sweep (k_lin_factor<D, true>), the energy, and the joint behind the batch MAP and the marginals.
+// LinParams::w is nullptr until losses are set and again after they are cleared: such a handle runs the plain kernels only.  Every call
+// that changes the weights clears map_ready, so the next solve re-makes the LDL^T of the diagonal blocks and the joint eta in the same
+// workspace; the iterate of the last solve stays where it is (gbp_lin_get_map).  A robust sweep is three kernels queued on the handle's
+// stream (k_lin_robustify, k_lin_factor<D, true>, k_lin_belief): no host round trip, no floating-point atomics.
+#include "gbp_lin_robust.hpp"
+
+#include <cmath>
+
+using namespace gbp;
+
+namespace {
+
+template <typename T>
+int rob_alloc(gbp_lin *h, T **out, size_t n)
+{
+    void *q = nullptr;
+    LHIPCHK(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
+    h->allocs.push_back(q);
+    *out = static_cast<T *>(q);
+    return GBP_OK;
+}
+
+template <typename T>
+int rob_upload(gbp_lin *h, const T *dst, const std::vector<T> &v)
+{
+    if (!v.empty()) LHIPCHK(hipMemcpyAsync(const_cast<T *>(dst), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, h->stream));
+    return GBP_OK;
+}
+
+// every weight 1, every flag 0
+int rob_reset(gbp_lin *h)
+{
+    const size_t F = (size_t)h->p.F;
+    LCHK(rob_upload(h, h->rob.w, std::vector<double>(F, 1.0)));
+    if (F) LHIPCHK(hipMemsetAsync(h->rob.flag, 0, F * sizeof(int), h->stream));
+    LHIPCHK(hipStreamSynchronize(h->stream));              // the host vectors above are temporaries
+    return GBP_OK;
+}
+
+int rob_robustify(gbp_lin *h)
+{
+    if (h->p.F) {
+        lin_dispatch(h->D, [&](auto d) {
+            hipLaunchKernelGGL((k_lin_robustify<decltype(d)::value>), dim3((h->p.F + 255) / 256), dim3(256), 0, h->stream, h->p, h->rob);
+        });
+        LHIPCHK(hipGetLastError());
+    }
+    h->map_ready = false;                                   // the joint is that of the new weights
+    return GBP_OK;
+}
+
+int rob_check_state(gbp_lin *h)
+{
+    if (!h->p.w) return set_error(GBP_ESTATE, "no losses set: call gbp_lin_set_robust first");
+    if (!h->has_beliefs) return set_error(GBP_ESTATE, "call gbp_lin_update_beliefs first: the weights are taken at the belief means");
+    return GBP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gbp_lin_set_robust(gbp_lin_t *h, const int32_t *loss, const double *threshold, const double *noise_var)
+{
+    LENTER(h);
+    const int F = h->p.F;
+    if (!loss) {                                            // clear: back to the plain path
+        LHIPCHK(hipStreamSynchronize(h->stream));
+        if (h->p.w) { h->p.w = nullptr; h->map_ready = false; }
+        if (h->rob_alloc) LCHK(rob_reset(h));
+        return GBP_OK;
+    }
+    if (!threshold) return set_error(GBP_EINVAL, "threshold is NULL");
+    bool any = false;
+    for (int f = 0; f < F; ++f) {
+        if (loss[f] != GBP_LIN_LOSS_NONE && loss[f] != GBP_LIN_LOSS_HUBER && loss[f] != GBP_LIN_LOSS_CONSTANT)
+            return set_error(GBP_EINVAL, "factor %d: unknown loss %d", f, loss[f]);
+        if (loss[f] == GBP_LIN_LOSS_NONE) continue;
+        any = true;
+        if (!(threshold[f] > 0.0) || !std::isfinite(threshold[f])) return set_error(GBP_EINVAL, "factor %d: the threshold must be positive", f);
+        if (loss[f] == GBP_LIN_LOSS_CONSTANT) {
+            if (!noise_var) return set_error(GBP_EINVAL, "factor %d has the constant loss: noise_var must be given", f);
+            if (!(noise_var[f] > 0.0) || !std::isfinite(noise_var[f])) return set_error(GBP_EINVAL, "factor %d: noise_var must be positive", f);
+        }
+    }
+    if (any && !h->has_const)
+        return set_error(GBP_EINVAL, "a loss needs the factors' constants: the handle was created with factor_const == NULL");
+    if (!h->rob_alloc) {
+        int *dl = nullptr; double *dt = nullptr, *dn = nullptr;
+        LCHK(rob_alloc(h, &dl, (size_t)F)); LCHK(rob_alloc(h, &dt, (size_t)F)); LCHK(rob_alloc(h, &dn, (size_t)F));
+        LCHK(rob_alloc(h, &h->rob.w, (size_t)F)); LCHK(rob_alloc(h, &h->rob.flag, (size_t)F));
+        h->rob.loss = dl; h->rob.thr = dt; h->rob.nvar = dn;
+        h->rob_alloc = true;
+    }
+    std::vector<int> hl(loss, loss + F);
+    std::vector<double> ht((size_t)F, 1.0), hn((size_t)F, 1.0);
+    for (int f = 0; f < F; ++f) {
+        if (loss[f] != GBP_LIN_LOSS_NONE) ht[f] = threshold[f];
+        if (loss[f] == GBP_LIN_LOSS_CONSTANT) hn[f] = noise_var[f];
+    }
+    LHIPCHK(hipStreamSynchronize(h->stream));              // no sweep in flight reads the arrays about to change
+    LCHK(rob_upload(h, h->rob.loss, hl)); LCHK(rob_upload(h, h->rob.thr, ht)); LCHK(rob_upload(h, h->rob.nvar, hn));
+    LCHK(rob_reset(h));
+    h->p.w = h->rob.w;
+    h->map_ready = false;
+    return GBP_OK;
+}
+
+int gbp_lin_robustify(gbp_lin_t *h)
+{
+    LENTER(h);
+    LCHK(rob_check_state(h));
+    return rob_robustify(h);
+}
+
+int gbp_lin_iterate_robust(gbp_lin_t *h, int32_t n_iters)
+{
+    LENTER(h);
+    if (n_iters < 0) return set_error(GBP_EINVAL, "negative iteration count");
+    LCHK(rob_check_state(h));
+    for (int it = 0; it < n_iters; ++it) {
+        LCHK(rob_robustify(h));
+        LCHK(lin_sweep(h));
+    }
+    LHIPCHK(hipGetLastError());
+    return GBP_OK;
+}
+
+int gbp_lin_get_weights(gbp_lin_t *h, double *w, int32_t *robust_flag)
+{
+    LENTER(h);
+    if (!w) return set_error(GBP_EINVAL, "w is NULL");
+    const size_t F = (size_t)h->p.F;
+    LHIPCHK(hipStreamSynchronize(h->stream));
+    if (!h->p.w) {                                          // no losses set: every factor is Gaussian
+        for (size_t f = 0; f < F; ++f) { w[f] = 1.0; if (robust_flag) robust_flag[f] = 0; }
+        return GBP_OK;
+    }
+    if (F) {
+        LHIPCHK(hipMemcpyAsync(w, h->rob.w, F * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        if (robust_flag) LHIPCHK(hipMemcpyAsync(robust_flag, h->rob.flag, F * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    }
+    LHIPCHK(hipStreamSynchronize(h->stream));
+    return GBP_OK;
+}
+
+}  // extern "C"

@@ -3,6 +3,7 @@
 //   gbp_lin_capi.hip       create / destroy, the sweep (k_lin_factor, k_lin_belief), energy, getters
 //   gbp_lin_capi_map.hip   the batch MAP by block-Jacobi conjugate gradients (kernels in gbp_lin_map.hpp)
 //   gbp_lin_capi_marg.hip  exact marginal covariances by the same iteration on 8 columns at a time (kernels in gbp_lin_marg.hpp)
+//   gbp_lin_capi_robust.hip  robust losses: one weight per factor from the current belief means (kernels in gbp_lin_robust.hpp)
 #pragma once
 #include "../../include/gbp_ba.h"
 #include "../../include/gbp_lin.h"
@@ -28,6 +29,15 @@ struct LinParams {
     const int *vptr, *vadj;      // CSR: variable -> (factor << 1 | side), ascending factor id
     double *vmsg;                // [2F][D + P]: the same messages in VARIABLE-major (CSR edge) order, for the belief stage
     const int *epos_a, *epos_b;  // [F]: CSR edge index of (factor, side)
+    const double *w;             // [F] robust weights of the nominal factors (gbp_lin_robust.hpp), or nullptr: no losses set, all 1
+};
+
+// Robust losses (gbp_lin_robust.hpp): device memory owned by gbp_lin::allocs, allocated by the first gbp_lin_set_robust of a handle.
+struct LinRobust {
+    const int *loss;             // [F] GBP_LIN_LOSS_*
+    const double *thr, *nvar;    // [F] Mahalanobis threshold, noise variance (read for the constant loss only)
+    double *w;                   // [F] what LinParams::w points at while losses are set
+    int *flag;                   // [F] Factor.robust_flag
 };
 
 template <int D> struct LinDims {
@@ -67,12 +77,16 @@ struct gbp_lin {
     std::vector<void *> allocs;
     double *d_red = nullptr;
     int red_blocks = 0;
-    bool has_beliefs = false;
+    bool has_beliefs = false, has_const = false;
     LinMap map{};                    // gbp_lin_capi_map.hip
-    bool map_ready = false, map_solved = false;
+    bool map_alloc = false;          // the workspace exists
+    bool map_ready = false;          // the LDL^T of the diagonal blocks and the joint eta are those of the current weights
+    bool map_solved = false;
     double map_eta_norm = 0.0;
     LinMarg marg{};                  // gbp_lin_capi_marg.hip
     bool marg_ready = false;
+    LinRobust rob{};                 // gbp_lin_capi_robust.hip
+    bool rob_alloc = false;          // rob's arrays exist; losses are set while p.w != nullptr
 };
 
 #define LHIPCHK(expr)                                                                                       \
@@ -90,7 +104,8 @@ struct gbp_lin {
     } while (0)
 
 namespace gbp {
-int lin_map_prepare(gbp_lin *h);                    // gbp_lin_capi_map.hip: LinMap's workspace, LDL^T and joint eta, once per handle
+int lin_map_prepare(gbp_lin *h);                    // gbp_lin_capi_map.hip: LinMap's workspace (once per handle), LDL^T and joint eta (per set of weights)
+int lin_sweep(gbp_lin *h);                          // gbp_lin_capi.hip: one synchronous iteration at the weights as they stand, queued on the stream
 }
 
 template <typename T>

@@ -53,12 +53,17 @@ GBP_HD void map_factor_apply(const LinParams &p, int f, const double *src, doubl
             if (j != i) y[j] += a * x[i];
         }
     }
+    if (p.w) {                                            // the joint at the current robust weights (gbp_lin_robust.hpp; gbp.py:94-98)
+        const double w = p.w[f];
+#pragma unroll
+        for (int k = 0; k < N2; ++k) y[k] *= w;
+    }
 #pragma unroll
     for (int k = 0; k < D; ++k) { ya[k] = y[k]; yb[k] = y[D + k]; }
 }
 
-// D_v = prior Lambda_v + sum over the adjacency run of the factor's own diagonal block -> LDL^T in ldl[v] = (packed factor | 1/d);
-// eta_joint,v -> jeta[v].  Returns |eta_joint,v|^2.
+// D_v = prior Lambda_v + sum over the adjacency run of the factor's own diagonal block (times its robust weight, if losses are set)
+// -> LDL^T in ldl[v] = (packed factor | 1/d); eta_joint,v -> jeta[v].  Returns |eta_joint,v|^2.
 template <int D>
 GBP_HD double map_var_setup(const LinParams &p, int v, double *ldl, double *jeta)
 {
@@ -71,12 +76,13 @@ GBP_HD double map_var_setup(const LinParams &p, int v, double *ldl, double *jeta
     for (int k = 0; k < P; ++k) a[k] = p.prior[(size_t)v * R + D + k];
     for (int ed = p.vptr[v]; ed < p.vptr[v + 1]; ++ed) {
         const int f = p.vadj[ed] >> 1, o = (p.vadj[ed] & 1) * D;
+        const double w = p.w ? p.w[f] : 1.0;              // times 1 is exact: the plain joint keeps its bits
 #pragma unroll
-        for (int k = 0; k < D; ++k) e[k] += p.feta[(size_t)(o + k) * F + f];
+        for (int k = 0; k < D; ++k) e[k] += w * p.feta[(size_t)(o + k) * F + f];
 #pragma unroll
         for (int i = 0; i < D; ++i)
 #pragma unroll
-            for (int j = i; j < D; ++j) a[Sym<D>::at(i, j)] += p.flam[(size_t)(o ? Sym<2 * D>::at(D + i, D + j) : Sym<2 * D>::at(i, j)) * F + f];
+            for (int j = i; j < D; ++j) a[Sym<D>::at(i, j)] += w * p.flam[(size_t)(o ? Sym<2 * D>::at(D + i, D + j) : Sym<2 * D>::at(i, j)) * F + f];
     }
     ldl_factor<D>(a, invd);
     double ee = 0.0;

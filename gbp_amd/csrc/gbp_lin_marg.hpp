@@ -54,6 +54,11 @@ GBP_HD void marg_factor_apply(const LinParams &p, int f, int c, const double *sr
             if (j != i) y[j] += a * x[i];
         }
     }
+    if (p.w) {                                            // the joint at the current robust weights, as map_factor_apply
+        const double w = p.w[f];
+#pragma unroll
+        for (int k = 0; k < N2; ++k) y[k] *= w;
+    }
 #pragma unroll
     for (int k = 0; k < D; ++k) { ya[k] = y[k]; yb[k] = y[D + k]; }
 }

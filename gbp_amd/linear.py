@@ -3,7 +3,7 @@
 
 `LinearEngine.from_factor_graph(graph)` takes a host graph built with the drop-in `gbp.gbp` classes
 (after `compute_all_factors()`, ndim_posegraph.py:91) and runs its sweeps on the device; the host
-graph is left untouched.  No CPU fallback: without a GPU `gbp_lin_create` fails with GBP_ENODEV.
+graph is left untouched.  Factors that carry `loss='huber'` / `'constant'` keep it: `iterate(n, robustify=True)`.  No CPU fallback: without a GPU `gbp_lin_create` fails with GBP_ENODEV.
 """
 from __future__ import annotations
 
@@ -47,10 +47,14 @@ class LinearEngine:
         if len(dofs) != 1:
             raise ValueError("all variables must have the same number of dofs")
         D = dofs.pop()
-        va, vb, fe, fl, fc = [], [], [], [], []
+        va, vb, fe, fl, fc, loss, thr, nvar = [], [], [], [], [], [], [], []
         for fac in graph.factors:
             if len(fac.adj_vIDs) != 2:
                 raise ValueError("only two-variable factors")
+            if fac.adaptive_gauss_noise_var != fac.gauss_noise_var:
+                raise ValueError(f"factor {fac.factorID} arrives already rescaled by robustify_loss (adaptive_gauss_noise_var != "
+                                 "gauss_noise_var): the device stores nominal factors and makes the weights itself")
+            loss.append(fac.loss); thr.append(float(fac.mahalanobis_threshold)); nvar.append(float(fac.gauss_noise_var))
             va.append(index[fac.adj_vIDs[0]]); vb.append(index[fac.adj_vIDs[1]])
             fe.append(np.asarray(fac.factor.eta, dtype=float)); fl.append(np.asarray(fac.factor.lam, dtype=float))
             x0 = np.asarray(fac.linpoint, dtype=float)
@@ -61,10 +65,13 @@ class LinearEngine:
             ids = [f.factorID for f in v.adj_factors]
             if ids != sorted(ids):
                 raise ValueError("adj_factors must be in ascending factor id (ndim_posegraph.py:86-88)")
-        return cls(va, vb, np.array(fe).reshape(-1, 2 * D), np.array(fl).reshape(-1, 2 * D, 2 * D),
-                   np.array([v.prior.eta for v in graph.var_nodes]).reshape(-1, D),
-                   np.array([v.prior.lam for v in graph.var_nodes]).reshape(-1, D, D),
-                   factor_const=fc, eta_damping=graph.eta_damping, device=device)
+        eng = cls(va, vb, np.array(fe).reshape(-1, 2 * D), np.array(fl).reshape(-1, 2 * D, 2 * D),
+                  np.array([v.prior.eta for v in graph.var_nodes]).reshape(-1, D),
+                  np.array([v.prior.lam for v in graph.var_nodes]).reshape(-1, D, D),
+                  factor_const=fc, eta_damping=graph.eta_damping, device=device)
+        if any(l is not None for l in loss):                                           # Factor(loss=, mahalanobis_threshold=) gbp.py:209-210
+            eng.set_robust(loss, thr, nvar)
+        return eng
 
     def close(self):
         h, self._h = getattr(self, '_h', None), None
@@ -81,11 +88,46 @@ class LinearEngine:
     def update_all_beliefs(self):
         check(self._lib.gbp_lin_update_beliefs(self._h))
 
-    def synchronous_iteration(self):
-        check(self._lib.gbp_lin_iterate(self._h, 1))
+    def synchronous_iteration(self, robustify=False):
+        self.iterate(1, robustify)
 
-    def iterate(self, n):
-        check(self._lib.gbp_lin_iterate(self._h, int(n)))
+    def iterate(self, n, robustify=False):
+        """n sweeps; robustify=True: every sweep re-makes the weights first (synchronous_iteration(robustify=True) gbp.py:86-92)."""
+        check((self._lib.gbp_lin_iterate_robust if robustify else self._lib.gbp_lin_iterate)(self._h, int(n)))
+
+    # robust losses (Factor(loss=, mahalanobis_threshold=), Factor.robustify_loss gbp.py:296-332): one weight per factor
+    def set_robust(self, loss, threshold=2.0, noise_var=None):
+        """Per-factor losses: None, 'huber' or 'constant' (a scalar or F of them), Mahalanobis threshold(s), and -- for the constant
+        loss -- the factors' noise variance(s).  loss=None clears every loss: the handle is back on the plain path.  Resets the weights
+        to 1; they are re-made from the current belief means by robustify_all_factors() / iterate(n, robustify=True)."""
+        if loss is None:
+            check(self._lib.gbp_lin_set_robust(self._h, None, None, None))
+            return
+        names = [loss] * self.F if isinstance(loss, str) else list(loss)
+        if len(names) != self.F:
+            raise ValueError(f"expected {self.F} losses, got {len(names)}")
+        bad = [l for l in names if l not in _capi.LIN_LOSS]
+        if bad:
+            raise ValueError(f"unknown loss {bad[0]!r}: None, 'huber' or 'constant'")
+        n = max(self.F, 1)                                   # F = 0: still a non-NULL `loss`, which NULL would read as "clear"
+        codes = np.zeros(n, dtype=np.int32)
+        codes[:self.F] = [_capi.LIN_LOSS[l] for l in names]
+        thr = np.ones(n)
+        thr[:self.F] = np.broadcast_to(np.asarray(threshold, dtype=np.float64), (self.F,))
+        nv = None
+        if noise_var is not None:
+            nv = np.ones(n)
+            nv[:self.F] = np.broadcast_to(np.asarray(noise_var, dtype=np.float64), (self.F,))
+        check(self._lib.gbp_lin_set_robust(self._h, iptr(codes), dptr(thr), dptr(nv)))
+
+    def robustify_all_factors(self):
+        check(self._lib.gbp_lin_robustify(self._h))
+
+    def weights(self):
+        """(w (F,), robust_flag (F,) bool): sigma^2 / adaptive_gauss_noise_var and Factor.robust_flag of every factor."""
+        w, flag = np.ones(max(self.F, 1)), np.zeros(max(self.F, 1), dtype=np.int32)
+        check(self._lib.gbp_lin_get_weights(self._h, dptr(w), iptr(flag)))
+        return w[:self.F], flag[:self.F].astype(bool)
 
     def energy(self):
         out = ct.c_double()

@@ -104,6 +104,43 @@ int  gbp_lin_solve_marginals(gbp_lin_t *h, const int32_t *ids, int32_t n_ids, co
                              double *sigma_joint,  /* NULL, or (n_ids d) x (n_ids d): Lambda_joint^-1 restricted to ids x ids   */
                              gbp_lin_marg_info_t *info);
 
+/* ---- robust losses: Factor(loss=, mahalanobis_threshold=) and Factor.robustify_loss (gbp.py:209-210, 296-332) for linear factors ----
+ * A robust factor is the handle's stored NOMINAL factor (eta_f, Lambda_f, const_f; noise variance sigma_f^2) times one weight
+ * w_f = sigma_f^2 / adaptive_gauss_noise_var, re-made from the current belief means x = [mu_a; mu_b]:
+ *   M_f^2 = 2 (0.5 x^T Lambda_f x - eta_f^T x + const_f) = |h(x) - z|^2 / sigma_f^2                        (gbp.py:312, 322)
+ *   loss none     : w_f = 1
+ *   loss huber    : w_f = (2 t M - t^2) / M^2  if M > t, else 1                                             (gbp.py:313-319)
+ *   loss constant : w_f = sigma_f^2 / M^2      if M > t, else 1    (the reference sets the adaptive variance to M^2, not sigma^2 M^2:
+ *                                                                   kept, and the only use of noise_var)   (gbp.py:323-328)
+ *   robust_flag_f = (M > t)
+ * M_f^2 is evaluated in the residual form of gbp_lin_energy (no cancellation far from the origin), so it needs factor_const.  The
+ * weight multiplies the nominal factor wherever it is used: messages (gbp.py:334-373), the energy term w_f e_f (gbp.py:43) and the
+ * joint (gbp.py:94-126) -- the reference rescales its factor in place by old / new (gbp.py:331-332), which differs by rounding only.
+ * DEPARTURE from the reference: robustify_loss evaluates h at Factor.linpoint (gbp.py:309), which a linear factor never moves after
+ * compute_all_factors(), so read literally its weights stay those of the prior means.  Here M is taken at the CURRENT belief means:
+ * exactly the reference's own arithmetic with every factor.linpoint set to its adjacent belief means before each
+ * synchronous_iteration(robustify=True).
+ *
+ * With losses set, gbp_lin_iterate runs at the weights as they stand (the reference's robustify=False), gbp_lin_energy returns
+ * sum_f w_f e_f, and gbp_lin_joint_matvec / joint_eta / solve_map / solve_marginals describe the joint at the current weights (the
+ * reference takes it from factor.factor as it stands, gbp.py:94-98): a solve after a robustify is one step of iteratively reweighted
+ * least squares.  Every call that changes the weights marks the solver's diagonal-block LDL^T and joint eta stale; the next solve
+ * re-makes them in the same workspace (nothing allocated).  The last MAP iterate stays retrievable by gbp_lin_get_map until the next
+ * solve.  No floating-point atomics: two identical call sequences on two handles are bit-identical. */
+#define GBP_LIN_LOSS_NONE 0
+#define GBP_LIN_LOSS_HUBER 1
+#define GBP_LIN_LOSS_CONSTANT 2
+int  gbp_lin_set_robust(gbp_lin_t *h, const int32_t *loss, const double *threshold, const double *noise_var);
+        /* Factor(loss=, mahalanobis_threshold=) gbp.py:209-210, 243-244.  F each; loss NULL = clear (all weights 1, handle back to the
+           plain path); threshold > 0 where loss != none; noise_var may be NULL unless some loss is CONSTANT, then > 0 there; resets every
+           weight to 1.  An unknown loss, a bad threshold or noise_var, or any loss on a handle created with factor_const == NULL: GBP_EINVAL */
+int  gbp_lin_robustify(gbp_lin_t *h);                       /* robustify_all_factors gbp.py:82-84: weights from the current belief means;
+                                                               GBP_ESTATE before beliefs exist or without losses set */
+int  gbp_lin_iterate_robust(gbp_lin_t *h, int32_t n_iters); /* n x synchronous_iteration(robustify=True) gbp.py:86-92, no host round trip;
+                                                               GBP_ESTATE as gbp_lin_robustify */
+int  gbp_lin_get_weights(gbp_lin_t *h, double *w, int32_t *robust_flag /* NULL ok */);   /* F each: sigma^2 / Factor.adaptive_gauss_noise_var,
+                                                               Factor.robust_flag (gbp.py:314-328); all 1 / 0 without losses set */
+
 #ifdef __cplusplus
 }
 #endif

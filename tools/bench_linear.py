@@ -22,7 +22,10 @@ ap.add_argument('--map', action='store_true', help='after the timed sweeps, solv
 ap.add_argument('--marginals', action='store_true',
                 help='instead of the run above: on the two 1M-factor graphs (the defaults, and --vars 1000000 --k 1) time one multi-column CG iteration '
                      'of gbp_lin_solve_marginals (8 columns) against one of gbp_lin_solve_map, and the sweeps, in one session; writes profiles/linear_marginals.json')
-ap.add_argument('--repeats', type=int, default=5, help='--marginals: repeats per timing (the median is reported)')
+ap.add_argument('--robust', action='store_true',
+                help='instead of the run above: on the same two graphs with 10 %% outlier measurements time iterate(n, robustify=True) (huber, threshold 2) '
+                     'against the plain iterate(n) of a handle without losses, alternating; writes profiles/linear_robust.json')
+ap.add_argument('--repeats', type=int, default=5, help='--marginals / --robust: repeats per timing (the median is reported)')
 a = ap.parse_args()
 
 
@@ -125,8 +128,64 @@ def traffic_ratio(D, vars_per_factor):
     return (lam + shared + 8 * col) / (8.0 * (lam + shared + col))
 
 
+def sweep_doubles(D, vars_per_factor, robust):
+    """Doubles moved per factor and sweep (the module docstring's count).  A robust sweep adds k_lin_robustify, which re-reads Lambda_f
+    d(2d+1), eta_f 2d and the two means 2d, reads const_f, the threshold and the noise variance 3 and the loss code (4 bytes), writes
+    the weight 1 and the flag (4 bytes); and k_lin_factor<D, true> reads the weight 1."""
+    P = D * (D + 1) // 2
+    plain = D * (2 * D + 1) + 2 * D + 8 * (D + P) + vars_per_factor * (2 * (D + P) + D)
+    return plain + (D * (2 * D + 1) + 4 * D + 3 + 0.5 + 1 + 0.5 + 1 if robust else 0)
+
+
+def robust_profile():
+    """Host clock around iterate(steps) + sync on two handles of the same graph (one without losses: k_lin_factor<D, false>; one with the
+    huber loss, threshold 2, on every factor: k_lin_robustify + k_lin_factor<D, true> per sweep), after a warm-up of both; --repeats
+    alternating runs, medians reported.  Every tenth measurement is 20 sigma off, so that the robust branch of the weight is taken."""
+    D, runs = 3, []
+    for N, k in ((200_000, 5), (1_000_000, 1)):
+        rs = np.random.RandomState(0)
+        (va, vb, fe, fl, pe, pl), _ = ring(N, D, k, rs)
+        F = va.shape[0]
+        J = np.hstack([-np.eye(D), np.eye(D)])
+        z = fe @ J.T / 2.0                                  # J J^T = 2 I: the measurements back from eta_f = J^T z
+        z[::10] += 20.0
+        fe, fc = z @ J, 0.5 * np.einsum('fd,fd->f', z, z)
+        plain, rob = LinearEngine(va, vb, fe, fl, pe, pl, factor_const=fc), LinearEngine(va, vb, fe, fl, pe, pl, factor_const=fc)
+        rob.set_robust('huber', 2.0)
+        for e, r in ((plain, False), (rob, True)):
+            e.update_all_beliefs()
+            e.iterate(a.warmup, robustify=r); e.sync()
+
+        def timed(e, r):
+            t = time.perf_counter(); e.iterate(a.steps, robustify=r); e.sync()
+            return 1e3 * (time.perf_counter() - t) / a.steps
+        tp, tr = [], []
+        for _ in range(a.repeats):                          # alternating
+            tp.append(timed(plain, False)); tr.append(timed(rob, True))
+        w, flag = rob.weights()
+        bp, br = sweep_doubles(D, 1.0 / k, False), sweep_doubles(D, 1.0 / k, True)
+        mp, mr = statistics.median(tp), statistics.median(tr)
+        runs.append({"vars": N, "dofs": D, "k": k, "factors": F, "ms_per_plain_sweep": mp, "ms_per_robust_sweep": mr, "ratio_measured": mr / mp,
+                     "doubles_per_factor_plain": bp, "doubles_per_factor_robust": br, "ratio_counted_bytes": br / bp,
+                     "plain_sweeps_per_s": 1e3 / mp, "robust_factors": int(flag.sum()), "min_weight": float(w.min()),
+                     "ms_plain_all": tp, "ms_robust_all": tr})
+        plain.close(); rob.close()
+    out = {"what": "tools/bench_linear.py --robust on one MI355X: ms per sweep of iterate(n, robustify=True) against iterate(n) of a handle without "
+                   "losses, on the 200k x 3 ring (k = 5) and the 1M-variable chain (k = 1)",
+           "method": " ".join(robust_profile.__doc__.split()), "traffic": " ".join(sweep_doubles.__doc__.split()),
+           "repeats": a.repeats, "sweep_steps": a.steps, "runs": runs}
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'profiles', 'linear_robust.json')
+    with open(path, 'w') as fh:
+        json.dump(out, fh, indent=1)
+        fh.write('\n')
+    print(json.dumps(out))
+
+
 if a.marginals:
     marginals_profile()
+    sys.exit(0)
+if a.robust:
+    robust_profile()
     sys.exit(0)
 N, D, k = a.vars, a.dofs, a.k
 (va, vb, fe, fl, pe, pl), fc = ring(N, D, k, np.random.RandomState(0))
