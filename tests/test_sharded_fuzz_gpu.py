@@ -112,10 +112,16 @@ def test_sharded_random_shapes(oracle_mod, seed):
         assert ranks[0]['n_relin'] == ref.count_relinearising()
 
 
-def test_no_seed_was_skipped_and_most_ran_their_whole_schedule():
-    """(runs after the parametrised test above: same module, file order)  Every seed was compared -- none skipped -- and cutting a
-    schedule short stays the exception: if most seeds lost sweeps, the fuzz would no longer be testing relinearisation waves."""
-    assert sorted(SWEEPS_COMPARED) == list(range(N_SEEDS)), f"seeds that did not reach the comparison: {sorted(set(range(N_SEEDS)) - set(SWEEPS_COMPARED))}"
+def test_no_seed_was_skipped_and_most_ran_their_whole_schedule(request):
+    """(runs after the parametrised test above: same module, file order)  Every seed was compared -- none skipped, none cut down to no
+    sweep at all -- and cutting a schedule short stays the exception: if most seeds lost sweeps, the fuzz would no longer be testing
+    relinearisation waves."""
+    if os.environ.get('PYTEST_XDIST_WORKER'):
+        pytest.skip('the seeds are spread over xdist workers (soak runs): the tally lives in the other processes')
+    if request.config.getoption('keyword'):
+        pytest.skip('-k selected a subset: the tally is incomplete by construction')
+    counted = sorted(k for k, (cut, _) in SWEEPS_COMPARED.items() if cut >= 1)      # a schedule cut to 0 sweeps compared nothing
+    assert counted == list(range(N_SEEDS)), f"seeds that did not reach the comparison: {sorted(set(range(N_SEEDS)) - set(counted))}"
     whole = sum(1 for c, n in SWEEPS_COMPARED.values() if c == n)
     assert whole >= (3 * N_SEEDS) // 4, SWEEPS_COMPARED
     print("sharded fuzz, sweeps compared per seed:", {k: v[0] for k, v in sorted(SWEEPS_COMPARED.items()) if v[0] != v[1]} or "all whole")

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import rel_err_rows
+from window_fuzz_cases import carry_batch, carry_ids
 from window_host import (EngineOps, base_case, big_landmark_problem, check_case, filter_batch, four_calls, hold_back, result_problem,
                          three_chunk_problem, window_step_numpy_ba)
 
@@ -214,10 +215,8 @@ def test_sliding_window_tracks_the_reference_graph(lib):
         e.iterate(4)
         nb.iterate(4)
         fac = e.factors(dense=False)
-        dC, dL = len(raw['cam_means']), len(raw['lmk_means'])
-        cam_u, lmk_u = np.concatenate([cam_now, e.C + np.arange(dC)]), np.concatenate([lmk_now, e.L + np.arange(dL)])
-        alive = (cam_u[raw['cam_idx']] >= 0) & (lmk_u[raw['lmk_idx']] >= 0)
-        bt = dict(raw, meas=raw['meas'][alive], cam_idx=cam_u[raw['cam_idx']][alive].astype(np.int32), lmk_idx=lmk_u[raw['lmk_idx']][alive].astype(np.int32))
+        dL = len(raw['lmk_means'])
+        bt, cam_u, lmk_u = carry_batch(raw, cam_now, lmk_now, e.C, e.L)
         retire = np.array([0, 1], np.int32)
         top = np.full(e.L + dL, -1)
         np.maximum.at(top, fac['lmk'], fac['cam'])
@@ -232,8 +231,7 @@ def test_sliding_window_tracks_the_reference_graph(lib):
         assert (e.C, e.L, e.F) == (nb.C, nb.L, len(nb.graph.factors)) and e.check_layout() == 0
         _gap_to_host(e, nb, f'step {k}')
         _same_relin(e, nb)
-        full_c, full_l = np.concatenate([me.cam_map, me.new_cam_ids]), np.concatenate([me.lmk_map, me.new_lmk_ids])
-        cam_now, lmk_now = np.where(cam_u >= 0, full_c[np.maximum(cam_u, 0)], -1), np.where(lmk_u >= 0, full_l[np.maximum(lmk_u, 0)], -1)
+        cam_now, lmk_now = carry_ids(cam_u, lmk_u, me)
     e.iterate(4)
     nb.iterate(4)
     _gap_to_host(e, nb, '4 sweeps after the last step')
