@@ -167,6 +167,8 @@ SIGNATURES = {
     'gbp_lin_robustify': (ct.c_int, [ct.c_void_p]),
     'gbp_lin_iterate_robust': (ct.c_int, [ct.c_void_p, ct.c_int32]),
     'gbp_lin_get_weights': (ct.c_int, [ct.c_void_p, _dp, _ip]),
+    'gbp_lin_extend': (ct.c_int, [ct.c_void_p, ct.c_void_p]),
+    'gbp_lin_get_sizes': (ct.c_int, [ct.c_void_p, _ip, _ip]),
     'gbp_ba_get_lmk_order': (ct.c_int, [ct.c_void_p, _ip]),
     'gbp_ba_fused_max_cams': (ct.c_int, []),
     'gbp_ba_plan_info': (ct.c_int, [ct.c_void_p, _ip, ct.c_int32]),
@@ -182,6 +184,13 @@ class LinDesc(ct.Structure):
     _fields_ = [('n_vars', ct.c_int32), ('dofs', ct.c_int32), ('n_factors', ct.c_int32), ('device', ct.c_int32),
                 ('var_a', _ip), ('var_b', _ip), ('factor_eta', _dp), ('factor_lam', _dp), ('factor_const', _dp),
                 ('prior_eta', _dp), ('prior_lam', _dp), ('eta_damping', ct.c_double)]
+
+
+class LinExt(ct.Structure):
+    """gbp_lin_extend_desc_t (include/gbp_lin.h)."""
+    _fields_ = [('n_new_vars', ct.c_int32), ('n_new_factors', ct.c_int32),
+                ('var_a', _ip), ('var_b', _ip), ('factor_eta', _dp), ('factor_lam', _dp), ('factor_const', _dp),
+                ('prior_eta', _dp), ('prior_lam', _dp), ('loss', _ip), ('threshold', _dp), ('noise_var', _dp)]
 
 
 class LinMapOpts(ct.Structure):

@@ -15,6 +15,26 @@ from . import _capi
 from ._capi import check, dptr, iptr, f64, i32
 
 
+def _host_factors(factors, index):
+    """(var_a, var_b, eta, lam, const, loss, threshold, noise_var) of host Factors (gbp.py:201-294) in the order given; `index` maps
+    a variableID to its position in graph.var_nodes."""
+    va, vb, fe, fl, fc, loss, thr, nvar = [], [], [], [], [], [], [], []
+    for fac in factors:
+        if len(fac.adj_vIDs) != 2:
+            raise ValueError("only two-variable factors")
+        if fac.adaptive_gauss_noise_var != fac.gauss_noise_var:
+            raise ValueError(f"factor {fac.factorID} arrives already rescaled by robustify_loss (adaptive_gauss_noise_var != "
+                             "gauss_noise_var): the device stores nominal factors and makes the weights itself")
+        loss.append(fac.loss); thr.append(float(fac.mahalanobis_threshold)); nvar.append(float(fac.gauss_noise_var))
+        va.append(index[fac.adj_vIDs[0]]); vb.append(index[fac.adj_vIDs[1]])
+        fe.append(np.asarray(fac.factor.eta, dtype=float)); fl.append(np.asarray(fac.factor.lam, dtype=float))
+        x0 = np.asarray(fac.linpoint, dtype=float)
+        J = np.atleast_2d(fac.jac_fn(fac.linpoint, *fac.args))
+        r = J @ x0 + fac.measurement - fac.meas_fn(fac.linpoint, *fac.args)        # = z - h(0) for a linear h
+        fc.append(0.5 * float(np.dot(np.atleast_1d(r), np.atleast_1d(r))) / fac.adaptive_gauss_noise_var)
+    return va, vb, fe, fl, fc, loss, thr, nvar
+
+
 class LinearEngine:
     def __init__(self, var_a, var_b, factor_eta, factor_lam, prior_eta, prior_lam, factor_const=None, eta_damping=0.0, device=0):
         self._lib = _capi.load()
@@ -47,20 +67,7 @@ class LinearEngine:
         if len(dofs) != 1:
             raise ValueError("all variables must have the same number of dofs")
         D = dofs.pop()
-        va, vb, fe, fl, fc, loss, thr, nvar = [], [], [], [], [], [], [], []
-        for fac in graph.factors:
-            if len(fac.adj_vIDs) != 2:
-                raise ValueError("only two-variable factors")
-            if fac.adaptive_gauss_noise_var != fac.gauss_noise_var:
-                raise ValueError(f"factor {fac.factorID} arrives already rescaled by robustify_loss (adaptive_gauss_noise_var != "
-                                 "gauss_noise_var): the device stores nominal factors and makes the weights itself")
-            loss.append(fac.loss); thr.append(float(fac.mahalanobis_threshold)); nvar.append(float(fac.gauss_noise_var))
-            va.append(index[fac.adj_vIDs[0]]); vb.append(index[fac.adj_vIDs[1]])
-            fe.append(np.asarray(fac.factor.eta, dtype=float)); fl.append(np.asarray(fac.factor.lam, dtype=float))
-            x0 = np.asarray(fac.linpoint, dtype=float)
-            J = np.atleast_2d(fac.jac_fn(fac.linpoint, *fac.args))
-            r = J @ x0 + fac.measurement - fac.meas_fn(fac.linpoint, *fac.args)        # = z - h(0) for a linear h
-            fc.append(0.5 * float(np.dot(np.atleast_1d(r), np.atleast_1d(r))) / fac.adaptive_gauss_noise_var)
+        va, vb, fe, fl, fc, loss, thr, nvar = _host_factors(graph.factors, index)
         for v in graph.var_nodes:                                                       # adjacency order the device assumes
             ids = [f.factorID for f in v.adj_factors]
             if ids != sorted(ids):
@@ -72,6 +79,78 @@ class LinearEngine:
         if any(l is not None for l in loss):                                           # Factor(loss=, mahalanobis_threshold=) gbp.py:209-210
             eng.set_robust(loss, thr, nvar)
         return eng
+
+    # growing a live graph (var_nodes.append / factors.append / adj_factors.append ndim_posegraph.py:67-88 + update_all_beliefs gbp.py:56-58)
+    def extend(self, var_a, var_b, factor_eta, factor_lam, prior_eta=None, prior_lam=None, factor_const=None, loss=None, threshold=2.0,
+               noise_var=None):
+        """Append dN variables (their priors: ids N .. N + dN - 1) and dF factors (ids F .. F + dF - 1, joining any variables old or
+        new) on the device; the messages of the old factors are kept, the new ones start at zero.  loss: None, or one name or dF of
+        None / 'huber' / 'constant' for the new factors (rules of set_robust).  Beliefs, where the handle had them, are re-made for
+        the grown graph; solve_map / marginals results are dropped until the next solve."""
+        var_a, var_b = i32(var_a).reshape(-1), i32(var_b).reshape(-1)
+        dF = var_a.shape[0]
+        if var_b.shape[0] != dF:
+            raise ValueError("var_a / var_b length mismatch")
+        dN = 0 if prior_eta is None else f64(prior_eta).reshape(-1, self.D).shape[0]
+        pe = f64(np.zeros((0, self.D)) if prior_eta is None else prior_eta, (dN, self.D))
+        pl = f64(np.zeros((0, self.D, self.D)) if prior_lam is None else prior_lam, (dN, self.D, self.D))
+        fe = f64(np.asarray(factor_eta, dtype=np.float64).reshape(dF, 2 * self.D))
+        fl = f64(np.asarray(factor_lam, dtype=np.float64).reshape(dF, 2 * self.D, 2 * self.D))
+        fc = None if factor_const is None else f64(factor_const, (dF,))
+        d = _capi.LinExt()
+        d.n_new_vars, d.n_new_factors = dN, dF
+        d.var_a, d.var_b = iptr(var_a), iptr(var_b)
+        d.factor_eta, d.factor_lam, d.factor_const = dptr(fe), dptr(fl), dptr(fc)
+        d.prior_eta, d.prior_lam = dptr(pe), dptr(pl)
+        keep = None
+        if loss is not None and dF:
+            names = [loss] * dF if isinstance(loss, str) else list(loss)
+            if len(names) != dF:
+                raise ValueError(f"expected {dF} losses, got {len(names)}")
+            bad = [l for l in names if l not in _capi.LIN_LOSS]
+            if bad:
+                raise ValueError(f"unknown loss {bad[0]!r}: None, 'huber' or 'constant'")
+            codes = np.array([_capi.LIN_LOSS[l] for l in names], dtype=np.int32)
+            thr = np.ascontiguousarray(np.broadcast_to(np.asarray(threshold, dtype=np.float64), (dF,)))
+            nv = None if noise_var is None else np.ascontiguousarray(np.broadcast_to(np.asarray(noise_var, dtype=np.float64), (dF,)))
+            keep = (codes, thr, nv)
+            d.loss, d.threshold, d.noise_var = iptr(codes), dptr(thr), dptr(nv)
+        check(self._lib.gbp_lin_extend(self._h, ct.byref(d)))
+        del keep
+        self.N, self.F = self.N + dN, self.F + dF
+
+    def sizes(self):
+        """(N, F) as the handle holds them."""
+        n, f = ct.c_int32(), ct.c_int32()
+        check(self._lib.gbp_lin_get_sizes(self._h, ct.byref(n), ct.byref(f)))
+        return n.value, f.value
+
+    def extend_from_factor_graph(self, graph):
+        """Append graph.var_nodes[self.N:] and graph.factors[self.F:] of a host graph that was grown (with compute_factor() on the new
+        factors) after from_factor_graph; the same checks.  Returns (dN, dF)."""
+        if len(graph.var_nodes) < self.N or len(graph.factors) < self.F:
+            raise ValueError(f"the graph holds {len(graph.var_nodes)} variables and {len(graph.factors)} factors, the handle {self.N} and {self.F}: "
+                             "a device graph only grows")
+        new_vars, new_facs = graph.var_nodes[self.N:], graph.factors[self.F:]
+        for i, fac in enumerate(new_facs, start=self.F):                               # the device numbers factors by position
+            if fac.factorID != i:
+                raise ValueError(f"graph.factors[{i}] has factorID {fac.factorID}: new factors must continue the append order "
+                                 "(factorID == position, ndim_posegraph.py:76-88)")
+        if any(v.dofs != self.D for v in new_vars):
+            raise ValueError("all variables must have the same number of dofs")
+        index = {v.variableID: i for i, v in enumerate(graph.var_nodes)}
+        D = self.D
+        args = _host_factors(new_facs, index)
+        for v in graph.var_nodes:
+            ids = [f.factorID for f in v.adj_factors]
+            if ids != sorted(ids):
+                raise ValueError("adj_factors must be in ascending factor id (ndim_posegraph.py:86-88)")
+        va, vb, fe, fl, fc, loss, thr, nvar = args
+        robust = any(l is not None for l in loss)
+        self.extend(va, vb, np.array(fe).reshape(-1, 2 * D), np.array(fl).reshape(-1, 2 * D, 2 * D),
+                    np.array([v.prior.eta for v in new_vars]).reshape(-1, D), np.array([v.prior.lam for v in new_vars]).reshape(-1, D, D),
+                    factor_const=fc, loss=loss if robust else None, threshold=thr if robust else 2.0, noise_var=nvar if robust else None)
+        return len(new_vars), len(new_facs)
 
     def close(self):
         h, self._h = getattr(self, '_h', None), None

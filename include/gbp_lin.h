@@ -141,6 +141,35 @@ int  gbp_lin_iterate_robust(gbp_lin_t *h, int32_t n_iters); /* n x synchronous_i
 int  gbp_lin_get_weights(gbp_lin_t *h, double *w, int32_t *robust_flag /* NULL ok */);   /* F each: sigma^2 / Factor.adaptive_gauss_noise_var,
                                                                Factor.robust_flag (gbp.py:314-328); all 1 / 0 without losses set */
 
+/* ---- growing a live graph: graph.var_nodes.append / graph.factors.append / adj_factors.append (ndim_posegraph.py:67-88) followed by
+ * FactorGraph.update_all_beliefs (gbp.py:56-58), without gbp_lin_destroy + gbp_lin_create and without losing the messages ----
+ * New variables get ids N .. N + dN - 1, new factors F .. F + dF - 1; everything older keeps the caller's numbering.  The state of the
+ * old factors is kept bit for bit (both messages; weight and flag where losses are set); new factors start with zero messages
+ * (gbp.py:222), weight 1 and flag 0.  Adjacency stays ascending in factor id: an old variable's list is its old list followed by its
+ * new factors, which is what adj_factors.append produces.  If the handle had beliefs the call ends with the belief stage over all
+ * variables: old variables' records come out bit-identical (the same sum in the same order, plus zero messages), new variables hold
+ * their prior and its mean; a handle without beliefs stays without.
+ * Losses: `loss` != NULL on a handle without losses turns them on with the old factors at NONE (needs factor_const, as
+ * gbp_lin_set_robust does); `loss` == NULL on a handle with losses gives the new factors NONE.
+ * Solvers: the MAP and marginal workspaces are sized by N and F and are dropped; gbp_lin_get_map and gbp_lin_map_distance return
+ * GBP_ESTATE until the next solve, which describes the joint of the grown graph at the current weights.
+ * GBP_EINVAL -- after validation, before anything is changed, so the handle goes on bit-identically -- for a needed array that is NULL,
+ * an id outside [0, N + dN) or a == b, factor_const given to a handle created without it or missing on one created with it, a bad
+ * loss / threshold / noise_var, or 2 (F + dF) not fitting int32.  An allocation failure (GBP_ENOMEM) also leaves the handle as it was.
+ * dN == dF == 0: GBP_OK, nothing changes.  All of the rebuild runs on the device; host work and traffic are proportional to dN and dF.
+ * Replaced arrays are freed in the call.  No atomics: two identical call sequences on two handles are bit-identical. */
+typedef struct {
+    int32_t n_new_vars, n_new_factors;      /* dN, dF >= 0                                                          */
+    const int32_t *var_a, *var_b;           /* dF: ids in [0, N + dN), a != b; old-old, old-new and new-new allowed */
+    const double *factor_eta, *factor_lam;  /* dF x 2d, dF x 2d x 2d                                                */
+    const double *factor_const;             /* dF; required iff the handle was created with factor_const            */
+    const double *prior_eta, *prior_lam;    /* dN x d, dN x d x d                                                   */
+    const int32_t *loss;                    /* dF GBP_LIN_LOSS_* or NULL (= none for the new factors)               */
+    const double *threshold, *noise_var;    /* dF, rules of gbp_lin_set_robust                                      */
+} gbp_lin_extend_desc_t;
+int  gbp_lin_extend(gbp_lin_t *h, const gbp_lin_extend_desc_t *d);              /* ndim_posegraph.py:67-88 appends + gbp.py:56-58 */
+int  gbp_lin_get_sizes(gbp_lin_t *h, int32_t *n_vars, int32_t *n_factors);      /* len(graph.var_nodes), len(graph.factors) gbp.py:13-14; either may be NULL */
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,7 +25,13 @@ ap.add_argument('--marginals', action='store_true',
 ap.add_argument('--robust', action='store_true',
                 help='instead of the run above: on the same two graphs with 10 %% outlier measurements time iterate(n, robustify=True) (huber, threshold 2) '
                      'against the plain iterate(n) of a handle without losses, alternating; writes profiles/linear_robust.json')
-ap.add_argument('--repeats', type=int, default=5, help='--marginals / --robust: repeats per timing (the median is reported)')
+ap.add_argument('--extend', action='store_true',
+                help='instead of the run above: on the 200k x 3 ring (k = 5, 1M factors) time one extend by 1000 variables and 5000 factors against '
+                     'gbp_lin_create of the grown graph, alternating, and the sweeps of the grown handle against one created whole; writes profiles/linear_extend.json')
+ap.add_argument('--parent-results', default=None,
+                help="--extend: a file of lines 'parent {json}' / 'here {json}', each the JSON line of a plain run of this tool from the parent "
+                     "commit's tree or from this one (run alternating, in the same session); summarised per workload under sweeps_per_s_vs_parent")
+ap.add_argument('--repeats', type=int, default=5, help='--marginals / --robust / --extend: repeats per timing (the median is reported)')
 a = ap.parse_args()
 
 
@@ -181,8 +187,101 @@ def robust_profile():
     print(json.dumps(out))
 
 
+def extend_profile():
+    """Host clock, call to gbp_lin_sync.  extend: on a handle of the 200k x 3 ring (k = 5) that has beliefs and 10 sweeps behind it,
+    LinearEngine.extend by 1000 variables, each joined to the 5 variables before it (5000 factors), then sync.  re-create: what the
+    parent commit offers for the same step, LinearEngine(...) of the grown graph from host arrays already in the ABI's types
+    (contiguous float64 / int32), then sync; its messages start at zero again, which is not charged.  --repeats alternating pairs
+    after one warm-up pair, medians reported; the base handle of every extend is made outside the clock.  Then iterate(steps) of the
+    last grown handle against a handle created at the final size after it and one created at the final size before anything else in the process, alternating, with the spread of each.  --parent-results adds plain runs of this tool from the parent commit's tree and this one."""
+    from gbp_amd import _capi
+    D, N, k, dN = 3, 200_000, 5, 1000
+    rs = np.random.RandomState(0)
+    (va, vb, fe, fl, pe, pl), fc = ring(N, D, k, rs)
+    mu1 = rs.rand(dN, D) * 10
+    na = np.repeat(np.arange(N, N + dN), k)
+    nb = na - np.tile(np.arange(1, k + 1), dN)
+    mu = np.concatenate([pe * 3.0, mu1])
+    z = mu[nb] - mu[na] + rs.normal(0, 1.0, (na.shape[0], D))
+    J = np.hstack([-np.eye(D), np.eye(D)])
+    nfe, nfl, nfc = z @ J, np.ascontiguousarray(np.broadcast_to(J.T @ J, (na.shape[0], 2 * D, 2 * D))), 0.5 * np.einsum('fd,fd->f', z, z)
+    npe, npl = mu1 / 3.0, np.ascontiguousarray(np.broadcast_to(np.eye(D) / 3.0, (dN, D, D)))
+    va, vb, na, nb = _capi.i32(va), _capi.i32(vb), _capi.i32(na), _capi.i32(nb)
+    whole_args = (np.concatenate([va, na]), np.concatenate([vb, nb]), np.concatenate([fe, nfe]), np.concatenate([fl, nfl]),
+                  np.concatenate([pe, npe]), np.concatenate([pl, npl]))
+    whole_fc = np.concatenate([fc, nfc])
+
+    first = LinearEngine(*whole_args, factor_const=whole_fc)   # created whole before anything else exists in the process
+    first.update_all_beliefs(); first.iterate(a.warmup); first.sync()
+
+    def base():
+        e = LinearEngine(va, vb, fe, fl, pe, pl, factor_const=fc)
+        e.update_all_beliefs(); e.iterate(a.warmup); e.sync()
+        return e
+
+    def timed_extend(e):
+        t = time.perf_counter(); e.extend(na, nb, nfe, nfl, npe, npl, factor_const=nfc); e.sync()
+        return 1e3 * (time.perf_counter() - t)
+
+    def timed_create():
+        t = time.perf_counter(); e = LinearEngine(*whole_args, factor_const=whole_fc); e.sync()
+        return 1e3 * (time.perf_counter() - t), e
+    t_ext, t_new, grown, whole = [], [], None, None
+    for r in range(a.repeats + 1):                          # alternating; the first pair warms up
+        e = base()
+        te = timed_extend(e)
+        tc, w = timed_create()
+        if r:
+            t_ext.append(te); t_new.append(tc)
+        if r == a.repeats:
+            grown, whole = e, w
+        else:
+            e.close(); w.close()
+    assert grown.sizes() == (N + dN, va.shape[0] + na.shape[0])
+    whole.update_all_beliefs(); whole.iterate(a.warmup); whole.sync()
+    grown.iterate(a.warmup); grown.sync()
+
+    def sweeps(e):
+        t = time.perf_counter(); e.iterate(a.steps); e.sync()
+        return a.steps / (time.perf_counter() - t)
+    sg, sw, sf = [], [], []
+    for _ in range(a.repeats):
+        sg.append(sweeps(grown)); sw.append(sweeps(whole)); sf.append(sweeps(first))
+    vs_parent = None
+    if a.parent_results:
+        runs = {}
+        for ln in open(a.parent_results):
+            who, js = ln.split(' ', 1)
+            r = json.loads(js)
+            runs.setdefault(r['config']['workload'], {'parent': [], 'here': []})[who].append(r['value'])
+        vs_parent = [{"workload": w, "parent": v['parent'], "here": v['here'], "median_parent": statistics.median(v['parent']),
+                      "median_here": statistics.median(v['here']),
+                      "spread_parent": (max(v['parent']) - min(v['parent'])) / statistics.median(v['parent']),
+                      "spread_here": (max(v['here']) - min(v['here'])) / statistics.median(v['here'])} for w, v in runs.items()]
+    me, mc = statistics.median(t_ext), statistics.median(t_new)
+    out = {"what": "tools/bench_linear.py --extend on one MI355X: one gbp_lin_extend of the 200k x 3 ring (1M factors) by 1000 variables and 5000 "
+                   "factors against gbp_lin_create of the grown graph, and the sweeps of the grown handle against a handle created whole",
+           "method": " ".join(extend_profile.__doc__.split()), "repeats": a.repeats, "sweep_steps": a.steps,
+           "vars": N, "dofs": D, "factors": int(va.shape[0]), "new_vars": dN, "new_factors": int(na.shape[0]),
+           "ms_extend": me, "ms_recreate": mc, "ratio_recreate_over_extend": mc / me, "ms_extend_all": t_ext, "ms_recreate_all": t_new,
+           "sweeps_per_s_grown": statistics.median(sg), "sweeps_per_s_created_whole": statistics.median(sw),
+           "ratio_grown_over_whole": statistics.median(sg) / statistics.median(sw),
+           "spread_grown": (max(sg) - min(sg)) / statistics.median(sg), "spread_whole": (max(sw) - min(sw)) / statistics.median(sw),
+           "sweeps_per_s_created_whole_first_in_process": statistics.median(sf), "spread_whole_first": (max(sf) - min(sf)) / statistics.median(sf),
+           "sweeps_per_s_grown_all": sg, "sweeps_per_s_whole_all": sw, "sweeps_per_s_whole_first_all": sf,
+           "sweeps_per_s_vs_parent": vs_parent}
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'profiles', 'linear_extend.json')
+    with open(path, 'w') as fh:
+        json.dump(out, fh, indent=1)
+        fh.write('\n')
+    print(json.dumps(out))
+
+
 if a.marginals:
     marginals_profile()
+    sys.exit(0)
+if a.extend:
+    extend_profile()
     sys.exit(0)
 if a.robust:
     robust_profile()
