@@ -169,6 +169,7 @@ SIGNATURES = {
     'gbp_lin_get_weights': (ct.c_int, [ct.c_void_p, _dp, _ip]),
     'gbp_lin_extend': (ct.c_int, [ct.c_void_p, ct.c_void_p]),
     'gbp_lin_get_sizes': (ct.c_int, [ct.c_void_p, _ip, _ip]),
+    'gbp_lin_shrink': (ct.c_int, [ct.c_void_p, ct.c_void_p]),
     'gbp_ba_get_lmk_order': (ct.c_int, [ct.c_void_p, _ip]),
     'gbp_ba_fused_max_cams': (ct.c_int, []),
     'gbp_ba_plan_info': (ct.c_int, [ct.c_void_p, _ip, ct.c_int32]),
@@ -191,6 +192,12 @@ class LinExt(ct.Structure):
     _fields_ = [('n_new_vars', ct.c_int32), ('n_new_factors', ct.c_int32),
                 ('var_a', _ip), ('var_b', _ip), ('factor_eta', _dp), ('factor_lam', _dp), ('factor_const', _dp),
                 ('prior_eta', _dp), ('prior_lam', _dp), ('loss', _ip), ('threshold', _dp), ('noise_var', _dp)]
+
+
+class LinShrink(ct.Structure):
+    """gbp_lin_shrink_desc_t (include/gbp_lin.h)."""
+    _fields_ = [('n_retire_vars', ct.c_int32), ('retire_vars', _ip), ('n_drop_factors', ct.c_int32), ('drop_factors', _ip),
+                ('fold', ct.c_int32), ('var_map', _ip), ('factor_map', _ip)]
 
 
 class LinMapOpts(ct.Structure):

@@ -1,0 +1,241 @@
+// gbp_lin_capi_shrink.hip -- gbp_lin_shrink of include/gbp_lin.h: retiring variables and dropping factors from a live handle without
+// gbp_lin_destroy + gbp_lin_create, the surviving messages kept and the leaving ones folded into the survivors' priors (kernels and the
+// renumbering argument: gbp_lin_shrink.hpp).
+//
+// One call: validate the two lists on the host (range and repeats: sorted copies, so the work is that of the lists), upload them, make
+// the flags, scan them once and bring N', F', 2F' back in one copy; allocate EVERY new array, build them on the device from the old
+// ones -- which are only read -- and synchronise; only then swap the pointers in, free the arrays that were replaced (and take them
+// out of `allocs`: a handle shrunk and grown a thousand times holds one generation), drop the MAP and marginal workspaces (sized by N
+// and F; the next solve re-makes them) and, where the handle had beliefs, run the belief stage over the survivors.  A failure before
+// the swap frees what was allocated and leaves the handle as it was.  Host work and host <-> device traffic are proportional to the two
+// lists, plus the maps where the caller asks for them; no existing array crosses to the host.
+#include "gbp_lin_shrink.hpp"
+
+#include <rocprim/device/device_scan.hpp>
+
+#include <climits>
+
+using namespace gbp;
+
+namespace {
+
+// device memory of one call: `keep` becomes the handle's after the swap, `temp` is freed at the end of the call either way
+struct ShrMem {
+    std::vector<void *> keep, temp;
+    template <typename T> int get(T **out, size_t n, bool kept)
+    {
+        void *q = nullptr;
+        LHIPCHK(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
+        (kept ? keep : temp).push_back(q);
+        *out = static_cast<T *>(q);
+        return GBP_OK;
+    }
+    static void release(std::vector<void *> &v) { for (void *q : v) (void)hipFree(q); v.clear(); }
+};
+
+// the arrays that replace the handle's
+struct ShrNew {
+    int N = 0, F = 0;
+    int *va = nullptr, *vb = nullptr, *vptr = nullptr, *vadj = nullptr, *epos_a = nullptr, *epos_b = nullptr;
+    double *feta = nullptr, *flam = nullptr, *fconst = nullptr, *msg_a = nullptr, *msg_b = nullptr, *bel = nullptr, *prior = nullptr, *vmsg = nullptr;
+    int *loss = nullptr, *flag = nullptr;           // the robust arrays, where losses are set
+    double *thr = nullptr, *nvar = nullptr, *w = nullptr;
+    int *maps = nullptr;                            // [N | F] of before the call (temp)
+};
+
+int shr_blocks(size_t n) { return (int)((n + SHR_BLOCK - 1) / SHR_BLOCK); }
+
+template <typename T>
+void shr_gather(gbp_lin *h, const T *src, const int *surv_f, T *dst, int rows, int F, int F1)
+{
+    if (F1 > 0) hipLaunchKernelGGL((k_shr_gather<T>), dim3(shr_blocks((size_t)F1), rows), dim3(SHR_BLOCK), 0, h->stream, src, surv_f, dst, F, F1);
+}
+
+void shr_forget(gbp_lin *h, const void *q)
+{
+    if (!q) return;
+    auto at = std::find(h->allocs.begin(), h->allocs.end(), q);
+    if (at != h->allocs.end()) h->allocs.erase(at);
+    (void)hipFree(const_cast<void *>(q));
+}
+
+// ids in [0, n), none twice; `what` names the list in the message
+int shr_check_list(const int32_t *ids, int count, int n, const char *what)
+{
+    if (count < 0) return set_error(GBP_EINVAL, "negative count of %s", what);
+    if (count && !ids) return set_error(GBP_EINVAL, "the list of %s is NULL", what);
+    if (count > n) return set_error(GBP_EINVAL, "%d %s listed, the handle holds %d: an id is out of range or listed twice", count, what, n);
+    std::vector<int32_t> s(ids, ids + count);
+    std::sort(s.begin(), s.end());
+    if (count && (s.front() < 0 || s.back() >= n)) return set_error(GBP_EINVAL, "%s: id %d outside [0, %d)", what, s.front() < 0 ? s.front() : s.back(), n);
+    for (int i = 1; i < count; ++i)
+        if (s[i] == s[i - 1]) return set_error(GBP_EINVAL, "%s: id %d is listed twice", what, s[i]);
+    return GBP_OK;
+}
+
+// everything up to and including the synchronisation after which nothing can fail: the new arrays, built on the device
+int shr_build(gbp_lin *h, const gbp_lin_shrink_desc_t *d, bool robust, ShrMem &mem, ShrNew &n)
+{
+    const LinParams &p = h->p;
+    const int D = h->D, D2 = 2 * D, P = D * (D + 1) / 2, P2 = D * (2 * D + 1), R = D + P, REC = D + P + D;
+    const int N = p.N, F = p.F, nr = d->n_retire_vars, nd = d->n_drop_factors;
+    const size_t total = (size_t)N + 3 * (size_t)F;             // the union index space [ N | F | 2F ], + 1 for the scan's total
+
+    // ---- flags over the union index space, one scan, the sizes in one copy ----
+    int *ids_r = nullptr, *ids_d = nullptr, *vret = nullptr, *fdrop = nullptr, *keep = nullptr, *pos = nullptr, *fold_side = nullptr, *sizes = nullptr;
+    LCHK(mem.get(&ids_r, (size_t)nr, false)); LCHK(mem.get(&ids_d, (size_t)nd, false));
+    LCHK(mem.get(&vret, (size_t)N, false)); LCHK(mem.get(&fdrop, (size_t)F, false));
+    LCHK(mem.get(&keep, total + 1, false)); LCHK(mem.get(&pos, total + 1, false));
+    LCHK(mem.get(&fold_side, (size_t)F, false)); LCHK(mem.get(&sizes, 3, false));
+    size_t scan_bytes = 0;
+    LHIPCHK(rocprim::exclusive_scan(nullptr, scan_bytes, keep, pos, 0, total + 1, rocprim::plus<int>(), h->stream));
+    { char *q = nullptr; LCHK(mem.get(&q, scan_bytes, false)); }
+    void *scan_tmp = mem.temp.back();
+    if (nr) LHIPCHK(hipMemcpyAsync(ids_r, d->retire_vars, (size_t)nr * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    if (nd) LHIPCHK(hipMemcpyAsync(ids_d, d->drop_factors, (size_t)nd * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    if (N) LHIPCHK(hipMemsetAsync(vret, 0, (size_t)N * sizeof(int), h->stream));
+    if (F) LHIPCHK(hipMemsetAsync(fdrop, 0, (size_t)F * sizeof(int), h->stream));
+    if (nr) hipLaunchKernelGGL(k_shr_mark, dim3(shr_blocks((size_t)nr)), dim3(SHR_BLOCK), 0, h->stream, (const int *)ids_r, nr, vret);
+    if (nd) hipLaunchKernelGGL(k_shr_mark, dim3(shr_blocks((size_t)nd)), dim3(SHR_BLOCK), 0, h->stream, (const int *)ids_d, nd, fdrop);
+    hipLaunchKernelGGL(k_shr_flags, dim3(shr_blocks(total + 1)), dim3(SHR_BLOCK), 0, h->stream, p.va, p.vb, p.vadj, N, F, (const int *)vret, (const int *)fdrop,
+                       (int)d->fold, keep, fold_side);
+    LHIPCHK(hipGetLastError());
+    LHIPCHK(rocprim::exclusive_scan(scan_tmp, scan_bytes, keep, pos, 0, total + 1, rocprim::plus<int>(), h->stream));
+    hipLaunchKernelGGL(k_shr_sizes, dim3(1), dim3(64), 0, h->stream, (const int *)pos, N, F, sizes);
+    LHIPCHK(hipGetLastError());
+    int hs[3] = {0, 0, 0};
+    LHIPCHK(hipMemcpyAsync(hs, sizes, sizeof(hs), hipMemcpyDeviceToHost, h->stream));
+    LHIPCHK(hipStreamSynchronize(h->stream));
+    const int N1 = hs[0], F1 = hs[1];
+    if (N1 != N - nr || F1 < 0 || F1 > F - nd || hs[2] != 2 * F1)
+        return set_error(GBP_EHIP, "the scan of the keep flags gave %d variables, %d factors, %d edges from %d - %d and %d - %d", N1, F1, hs[2], N, nr, F, nd);
+    n.N = N1; n.F = F1;
+
+    // ---- every allocation of the new generation, before the first kernel that builds it ----
+    int *surv_v = nullptr, *surv_f = nullptr;
+    LCHK(mem.get(&n.maps, (size_t)N + F, false)); LCHK(mem.get(&surv_v, (size_t)N1, false)); LCHK(mem.get(&surv_f, (size_t)F1, false));
+    LCHK(mem.get(&n.va, (size_t)F1, true)); LCHK(mem.get(&n.vb, (size_t)F1, true));
+    LCHK(mem.get(&n.feta, (size_t)D2 * F1, true)); LCHK(mem.get(&n.flam, (size_t)P2 * F1, true)); LCHK(mem.get(&n.fconst, (size_t)F1, true));
+    LCHK(mem.get(&n.msg_a, (size_t)R * F1, true)); LCHK(mem.get(&n.msg_b, (size_t)R * F1, true));
+    LCHK(mem.get(&n.bel, (size_t)N1 * REC, true)); LCHK(mem.get(&n.prior, (size_t)N1 * R, true));
+    LCHK(mem.get(&n.vptr, (size_t)N1 + 1, true)); LCHK(mem.get(&n.vadj, (size_t)2 * F1, true));
+    LCHK(mem.get(&n.epos_a, (size_t)F1, true)); LCHK(mem.get(&n.epos_b, (size_t)F1, true));
+    LCHK(mem.get(&n.vmsg, (size_t)2 * F1 * R, true));
+    if (robust) {
+        LCHK(mem.get(&n.loss, (size_t)F1, true)); LCHK(mem.get(&n.thr, (size_t)F1, true)); LCHK(mem.get(&n.nvar, (size_t)F1, true));
+        LCHK(mem.get(&n.w, (size_t)F1, true)); LCHK(mem.get(&n.flag, (size_t)F1, true));
+    }
+
+    // ---- the maps and the lists of survivors ----
+    const int *ckeep = keep, *cpos = pos, *csurv = surv_f, *cmaps = n.maps;
+    if (N + F) hipLaunchKernelGGL(k_shr_maps, dim3(shr_blocks((size_t)N + F)), dim3(SHR_BLOCK), 0, h->stream, ckeep, cpos, N, F, n.maps, surv_v, surv_f);
+    // ---- factor-strided arrays: [row][F] -> [row][F1] ----
+    if (F1) {
+        hipLaunchKernelGGL(k_shr_ends, dim3(shr_blocks((size_t)F1)), dim3(SHR_BLOCK), 0, h->stream, p.va, csurv, cmaps, n.va, F1);
+        hipLaunchKernelGGL(k_shr_ends, dim3(shr_blocks((size_t)F1)), dim3(SHR_BLOCK), 0, h->stream, p.vb, csurv, cmaps, n.vb, F1);
+    }
+    shr_gather<double>(h, p.feta, csurv, n.feta, D2, F, F1); shr_gather<double>(h, p.flam, csurv, n.flam, P2, F, F1);
+    shr_gather<double>(h, p.fconst, csurv, n.fconst, 1, F, F1);
+    shr_gather<double>(h, p.msg_a, csurv, n.msg_a, R, F, F1); shr_gather<double>(h, p.msg_b, csurv, n.msg_b, R, F, F1);
+    if (robust) {
+        shr_gather<int>(h, h->rob.loss, csurv, n.loss, 1, F, F1); shr_gather<double>(h, h->rob.thr, csurv, n.thr, 1, F, F1);
+        shr_gather<double>(h, h->rob.nvar, csurv, n.nvar, 1, F, F1); shr_gather<double>(h, h->rob.w, csurv, n.w, 1, F, F1);
+        shr_gather<int>(h, h->rob.flag, csurv, n.flag, 1, F, F1);
+    }
+    LHIPCHK(hipGetLastError());
+    // ---- the CSR of the survivors, the rows of vmsg with it ----
+    hipLaunchKernelGGL(k_shr_vptr, dim3(shr_blocks((size_t)N + 1)), dim3(SHR_BLOCK), 0, h->stream, ckeep, cpos, p.vptr, N, F, N1, n.vptr);
+    if (F)
+        hipLaunchKernelGGL(k_shr_edges, dim3(shr_blocks((size_t)2 * F * R)), dim3(SHR_BLOCK), 0, h->stream, ckeep, cpos, p.vadj, N, F, R, (const double *)p.vmsg, n.vadj,
+                           n.epos_a, n.epos_b, n.vmsg);
+    // ---- the fold into the priors; the survivors' belief records ----
+    if (N)
+        hipLaunchKernelGGL(k_shr_fold, dim3(shr_blocks((size_t)N * REC)), dim3(SHR_BLOCK), 0, h->stream, ckeep, cpos, p.vptr, p.vadj, (const int *)fold_side, N, R, REC,
+                           p.prior, (const double *)p.vmsg, (const double *)p.bel, n.prior, n.bel);
+    LHIPCHK(hipGetLastError());
+    if (d->var_map && N) LHIPCHK(hipMemcpyAsync(d->var_map, n.maps, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (d->factor_map && F) LHIPCHK(hipMemcpyAsync(d->factor_map, n.maps + N, (size_t)F * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    LHIPCHK(hipStreamSynchronize(h->stream));              // nothing below can fail
+    return GBP_OK;
+}
+
+int shr_validate(gbp_lin *h, const gbp_lin_shrink_desc_t *d)
+{
+    const int N = h->p.N, F = h->p.F;
+    if (d->fold != 0 && d->fold != 1) return set_error(GBP_EINVAL, "fold is %d: 0 or 1", d->fold);
+    LCHK(shr_check_list(d->retire_vars, d->n_retire_vars, N, "retired variables"));
+    LCHK(shr_check_list(d->drop_factors, d->n_drop_factors, F, "dropped factors"));
+    if ((long long)N + 3LL * F + 1 > INT_MAX) return set_error(GBP_EINVAL, "%d variables and %d factors: N + 3 F + 1 must fit int32 (one scan over variables, factors and edges)", N, F);
+    return GBP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gbp_lin_shrink(gbp_lin_t *h, const gbp_lin_shrink_desc_t *d)
+{
+    LENTER(h);
+    if (!d) return set_error(GBP_EINVAL, "NULL descriptor");
+    LCHK(shr_validate(h, d));
+    if (!d->n_retire_vars && !d->n_drop_factors) {          // nothing leaves: the maps are the identity
+        if (d->var_map) for (int v = 0; v < h->p.N; ++v) d->var_map[v] = v;
+        if (d->factor_map) for (int f = 0; f < h->p.F; ++f) d->factor_map[f] = f;
+        return GBP_OK;
+    }
+    const bool robust = h->p.w != nullptr;                  // a handle whose losses were cleared keeps stale arrays: they are freed, not carried
+    LHIPCHK(hipStreamSynchronize(h->stream));
+    ShrMem mem;
+    ShrNew n;
+    const int rc = shr_build(h, d, robust, mem, n);
+    if (rc != GBP_OK) {                                     // the handle's arrays were only read: it goes on as it was
+        (void)hipStreamSynchronize(h->stream);
+        ShrMem::release(mem.keep); ShrMem::release(mem.temp);
+        return rc;
+    }
+    ShrMem::release(mem.temp);
+    // ---- the swap ----
+    LinParams &p = h->p;
+    for (const void *q : {(const void *)p.va, (const void *)p.vb, (const void *)p.feta, (const void *)p.flam, (const void *)p.fconst, (const void *)p.msg_a,
+                          (const void *)p.msg_b, (const void *)p.bel, (const void *)p.prior, (const void *)p.vptr, (const void *)p.vadj, (const void *)p.vmsg,
+                          (const void *)p.epos_a, (const void *)p.epos_b})
+        shr_forget(h, q);
+    if (h->rob_alloc) {
+        for (const void *q : {(const void *)h->rob.loss, (const void *)h->rob.thr, (const void *)h->rob.nvar, (const void *)h->rob.w, (const void *)h->rob.flag}) shr_forget(h, q);
+        h->rob = LinRobust{};
+        h->rob_alloc = false;
+    }
+    if (h->map_alloc) {                                     // sized by N and F: re-made by the next solve
+        const LinMap &m = h->map;
+        for (const void *q : {(const void *)m.ldl, (const void *)m.jeta, (const void *)m.x, (const void *)m.r, (const void *)m.z, (const void *)m.p, (const void *)m.q,
+                              (const void *)m.ebuf, (const void *)m.pq_part, (const void *)m.rz_part, (const void *)m.rr_part})
+            shr_forget(h, q);
+        h->map = LinMap{};
+    }
+    h->map_alloc = h->map_ready = h->map_solved = false;
+    h->map_eta_norm = 0.0;
+    if (h->marg_ready) {                                    // the staging of the outputs does not depend on N or F and stays
+        LinMarg &m = h->marg;
+        for (const void *q : {(const void *)m.x, (const void *)m.r, (const void *)m.z, (const void *)m.p, (const void *)m.q, (const void *)m.ebuf, (const void *)m.pq_part,
+                              (const void *)m.rz_part, (const void *)m.rr_part})
+            shr_forget(h, q);
+        m.x = m.r = m.z = m.p = m.q = m.ebuf = m.pq_part = m.rz_part = m.rr_part = nullptr;
+        h->marg_ready = false;
+    }
+    // d_red stays: it holds ceil(F / 256) >= max(1, ceil(F' / 256)) partials, and the energy's launch goes by red_blocks
+    h->allocs.insert(h->allocs.end(), mem.keep.begin(), mem.keep.end());
+    p.N = n.N; p.F = n.F;
+    p.va = n.va; p.vb = n.vb; p.feta = n.feta; p.flam = n.flam; p.fconst = n.fconst; p.msg_a = n.msg_a; p.msg_b = n.msg_b;
+    p.bel = n.bel; p.prior = n.prior; p.vptr = n.vptr; p.vadj = n.vadj; p.vmsg = n.vmsg; p.epos_a = n.epos_a; p.epos_b = n.epos_b;
+    p.w = nullptr;
+    if (robust) {
+        h->rob = LinRobust{n.loss, n.thr, n.nvar, n.w, n.flag};
+        h->rob_alloc = true;
+        p.w = n.w;
+    }
+    // beliefs of the shrunk graph (update_all_beliefs gbp.py:56-58): the folded prior, then the surviving messages in adjacency order
+    if (h->has_beliefs) return gbp_lin_update_beliefs(h);
+    return GBP_OK;
+}
+
+}  // extern "C"

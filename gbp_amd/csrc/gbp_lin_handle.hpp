@@ -5,6 +5,7 @@
 //   gbp_lin_capi_marg.hip  exact marginal covariances by the same iteration on 8 columns at a time (kernels in gbp_lin_marg.hpp)
 //   gbp_lin_capi_robust.hip  robust losses: one weight per factor from the current belief means (kernels in gbp_lin_robust.hpp)
 //   gbp_lin_capi_extend.hip  growing a live graph: the layout rebuilt on the device (kernels in gbp_lin_extend.hpp)
+//   gbp_lin_capi_shrink.hip  shrinking a live graph: retired variables folded into priors (kernels in gbp_lin_shrink.hpp)
 #pragma once
 #include "../../include/gbp_ba.h"
 #include "../../include/gbp_lin.h"

@@ -125,6 +125,31 @@ class LinearEngine:
         check(self._lib.gbp_lin_get_sizes(self._h, ct.byref(n), ct.byref(f)))
         return n.value, f.value
 
+    # shrinking a live graph: retired variables and dropped factors leave, their last messages folded into the survivors' priors
+    def shrink(self, retire_vars=(), drop_factors=(), fold=True):
+        """Retire variables and drop factors on the device.  A factor leaves if it is listed or has a retired end; with fold=True a
+        leaving factor that is not listed and has one surviving end adds its stored message to that end's prior (GBP's own
+        marginalisation), otherwise its messages are dropped.  Survivors are renumbered monotonically and keep their messages; beliefs,
+        where the handle had them, are re-made; solve_map / marginals results are dropped until the next solve.
+        Returns (var_map, factor_map): int32 arrays over the ids of before the call, the new id or -1."""
+        rv, df = i32(np.asarray(retire_vars, dtype=np.int64).reshape(-1)), i32(np.asarray(drop_factors, dtype=np.int64).reshape(-1))
+        vmap, fmap = np.empty(max(self.N, 1), dtype=np.int32), np.empty(max(self.F, 1), dtype=np.int32)
+        d = _capi.LinShrink()
+        d.n_retire_vars, d.retire_vars = rv.shape[0], iptr(rv)
+        d.n_drop_factors, d.drop_factors = df.shape[0], iptr(df)
+        d.fold = int(fold)
+        d.var_map, d.factor_map = iptr(vmap), iptr(fmap)
+        check(self._lib.gbp_lin_shrink(self._h, ct.byref(d)))
+        vmap, fmap = vmap[:self.N], fmap[:self.F]
+        self.N, self.F = self.sizes()
+        return vmap, fmap
+
+    def retire(self, ids, fold=True):
+        return self.shrink(retire_vars=ids, fold=fold)
+
+    def cull(self, factor_ids):
+        return self.shrink(drop_factors=factor_ids)
+
     def extend_from_factor_graph(self, graph):
         """Append graph.var_nodes[self.N:] and graph.factors[self.F:] of a host graph that was grown (with compute_factor() on the new
         factors) after from_factor_graph; the same checks.  Returns (dN, dF)."""

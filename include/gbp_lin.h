@@ -170,6 +170,44 @@ typedef struct {
 int  gbp_lin_extend(gbp_lin_t *h, const gbp_lin_extend_desc_t *d);              /* ndim_posegraph.py:67-88 appends + gbp.py:56-58 */
 int  gbp_lin_get_sizes(gbp_lin_t *h, int32_t *n_vars, int32_t *n_factors);      /* len(graph.var_nodes), len(graph.factors) gbp.py:13-14; either may be NULL */
 
+/* ---- shrinking a live graph: variables and factors taken out of graph.var_nodes / graph.factors / adj_factors (gbp.py:13-14, 160), what
+ * the leaving factors last told the surviving variables folded into those variables' priors, followed by FactorGraph.update_all_beliefs
+ * (gbp.py:56-58) -- without gbp_lin_destroy + gbp_lin_create and without losing the surviving messages.  With gbp_lin_extend: a
+ * fixed-lag smoother ----
+ * Which factors leave: every factor on drop_factors, and every factor with at least one retired end; every other factor survives.  A
+ * variable left without factors survives unless it is listed.
+ * The fold (fold == 1): a leaving factor that is NOT on drop_factors and has exactly one surviving end s hands s its stored message to s
+ * (Factor.messages gbp.py:222) as it stands -- the robust weight and the damping are already inside it -- and that message is added to
+ * s's prior, eta and Lambda (VariableNode.prior gbp.py:170).  GBP's own marginalisation: exact on a tree with converged messages, no
+ * fill-in among the neighbours.  Per variable the order is the prior first, then the folded messages one after the other in adjacency
+ * order (ascending old factor id), in fp64.  A factor on drop_factors, or with both ends retired, folds nothing: its messages are
+ * dropped (the `cull` meaning).  fold == 0: every leaving message is dropped.
+ * Renumbering is monotone: new id = old id - the number of removed ids below it, for variables and for factors; adjacency stays
+ * ascending in factor id.  var_map / factor_map (host, N / F of BEFORE the call, either may be NULL) receive the new id or -1.
+ * What stays bit for bit: a surviving factor keeps eta_f, Lambda_f, const_f, both messages, weight, flag, loss, threshold and noise
+ * variance.  A surviving variable none of whose factors leaves keeps its prior and its belief record.  A surviving variable whose
+ * leaving factors are all folded and form a PREFIX of its adjacency list keeps its belief record (the same sum in the same order: the
+ * fixed-lag case, where the oldest factors go).  Any other surviving variable's belief is equal up to the order of the sum (folded) or
+ * changed (dropped).
+ * Beliefs: if the handle had beliefs the call ends with the belief stage over all survivors; a handle without beliefs stays without.
+ * Solvers: as gbp_lin_extend -- the MAP and marginal workspaces are dropped (the marginals' output staging stays); gbp_lin_get_map and
+ * gbp_lin_map_distance return GBP_ESTATE until the next solve, which describes the joint of the shrunk graph, with the folded priors, at
+ * the current weights.  Losses stay set if they were; a handle whose losses were cleared stays on the plain path.
+ * GBP_EINVAL -- after validation, before anything is changed, so the handle goes on bit-identically -- for a NULL list with a positive
+ * count, a negative count, an id out of range, an id listed twice, fold not 0 or 1, or N + 3 F + 1 not fitting int32.  An allocation
+ * failure (GBP_ENOMEM) also leaves the handle as it was.  Both counts 0: GBP_OK, nothing changes, the maps are the identity.  Retiring
+ * every variable is legal (N' = F' = 0; gbp_lin_extend grows such a handle again).
+ * All of the rebuild runs on the device; host work and traffic are proportional to the two lists, plus the maps where they are asked
+ * for.  Replaced arrays are freed in the call.  No floating-point atomics and no write that two threads race for: two identical call
+ * sequences on two handles are bit-identical. */
+typedef struct {
+    int32_t n_retire_vars;  const int32_t *retire_vars;   /* ids in [0, N), none listed twice                                     */
+    int32_t n_drop_factors; const int32_t *drop_factors;  /* ids in [0, F), none listed twice                                     */
+    int32_t fold;                                         /* 1: fold (above); 0: every leaving message is dropped                 */
+    int32_t *var_map, *factor_map;                        /* out, host, N / F of BEFORE the call: new id or -1; either may be NULL */
+} gbp_lin_shrink_desc_t;
+int  gbp_lin_shrink(gbp_lin_t *h, const gbp_lin_shrink_desc_t *d);
+
 #ifdef __cplusplus
 }
 #endif

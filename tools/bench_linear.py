@@ -28,6 +28,9 @@ ap.add_argument('--robust', action='store_true',
 ap.add_argument('--extend', action='store_true',
                 help='instead of the run above: on the 200k x 3 ring (k = 5, 1M factors) time one extend by 1000 variables and 5000 factors against '
                      'gbp_lin_create of the grown graph, alternating, and the sweeps of the grown handle against one created whole; writes profiles/linear_extend.json')
+ap.add_argument('--shrink', action='store_true',
+                help='instead of the run above: on the 200k x 3 ring (k = 5, 1M factors) time one shrink retiring the 1000 lowest-numbered variables (folded) '
+                     "against gbp_lin_create of the survivors' graph, alternating, and the sweeps of the shrunk handle against the created one; writes profiles/linear_shrink.json")
 ap.add_argument('--parent-results', default=None,
                 help="--extend: a file of lines 'parent {json}' / 'here {json}', each the JSON line of a plain run of this tool from the parent "
                      "commit's tree or from this one (run alternating, in the same session); summarised per workload under sweeps_per_s_vs_parent")
@@ -277,6 +280,91 @@ def extend_profile():
     print(json.dumps(out))
 
 
+def shrink_profile():
+    """Host clock, call to gbp_lin_sync.  shrink: on a handle of the 200k x 3 ring (k = 5, 1M factors) that has beliefs and 10 sweeps
+    behind it, LinearEngine.shrink retiring the 1000 lowest-numbered variables with the fold (the maps are asked for), then sync.
+    re-create: what the parent commit offers for the same step, LinearEngine(...) of the survivors' graph from host arrays already in
+    the ABI's types, then sync; it loses every message, which is not charged.  --repeats alternating pairs after one warm-up pair,
+    medians reported; the base handle of every shrink is made outside the clock.  Then iterate(steps) of the last shrunk handle against
+    the handle created at the survivors' size after it, alternating, with the spread of each.  --parent-results adds plain runs of this
+    tool from the parent commit's tree and this one."""
+    from gbp_amd import _capi
+    D, N, k, gone = 3, 200_000, 5, 1000
+    rs = np.random.RandomState(0)
+    (va, vb, fe, fl, pe, pl), fc = ring(N, D, k, rs)
+    va, vb = _capi.i32(va), _capi.i32(vb)
+    retire = np.arange(gone, dtype=np.int32)
+    keep = (va >= gone) & (vb >= gone)
+    surv_args = (_capi.i32(va[keep] - gone), _capi.i32(vb[keep] - gone), np.ascontiguousarray(fe[keep]), np.ascontiguousarray(fl[keep]),
+                 np.ascontiguousarray(pe[gone:]), np.ascontiguousarray(pl[gone:]))
+    surv_fc = np.ascontiguousarray(fc[keep])
+
+    def base():
+        e = LinearEngine(va, vb, fe, fl, pe, pl, factor_const=fc)
+        e.update_all_beliefs(); e.iterate(a.warmup); e.sync()
+        return e
+
+    def timed_shrink(e):
+        t = time.perf_counter(); e.shrink(retire_vars=retire, fold=True); e.sync()
+        return 1e3 * (time.perf_counter() - t)
+
+    def timed_create():
+        t = time.perf_counter(); e = LinearEngine(*surv_args, factor_const=surv_fc); e.sync()
+        return 1e3 * (time.perf_counter() - t), e
+    t_shr, t_new, shrunk, created = [], [], None, None
+    for r in range(a.repeats + 1):                          # alternating; the first pair warms up
+        e = base()
+        ts = timed_shrink(e)
+        tc, w = timed_create()
+        if r:
+            t_shr.append(ts); t_new.append(tc)
+        if r == a.repeats:
+            shrunk, created = e, w
+        else:
+            e.close(); w.close()
+    assert shrunk.sizes() == created.sizes() == (N - gone, int(keep.sum()))
+    created.update_all_beliefs(); created.iterate(a.warmup); created.sync()
+    shrunk.iterate(a.warmup); shrunk.sync()
+
+    def sweeps(e):
+        t = time.perf_counter(); e.iterate(a.steps); e.sync()
+        return a.steps / (time.perf_counter() - t)
+    ss, sc = [], []
+    for _ in range(a.repeats):
+        ss.append(sweeps(shrunk)); sc.append(sweeps(created))
+    vs_parent = None
+    if a.parent_results:
+        runs = {}
+        for ln in open(a.parent_results):
+            who, js = ln.split(' ', 1)
+            r = json.loads(js)
+            runs.setdefault(r['config']['workload'], {'parent': [], 'here': []})[who].append(r['value'])
+        vs_parent = [{"workload": w, "parent": v['parent'], "here": v['here'], "median_parent": statistics.median(v['parent']),
+                      "median_here": statistics.median(v['here']),
+                      "spread_parent": (max(v['parent']) - min(v['parent'])) / statistics.median(v['parent']),
+                      "spread_here": (max(v['here']) - min(v['here'])) / statistics.median(v['here'])} for w, v in runs.items()]
+    ms, mc = statistics.median(t_shr), statistics.median(t_new)
+    out = {"what": "tools/bench_linear.py --shrink on one MI355X: one gbp_lin_shrink of the 200k x 3 ring (1M factors) retiring its 1000 "
+                   "lowest-numbered variables with the fold against gbp_lin_create of the survivors' graph, and the sweeps of the shrunk "
+                   "handle against a handle created at the survivors' size",
+           "method": " ".join(shrink_profile.__doc__.split()), "repeats": a.repeats, "sweep_steps": a.steps,
+           "vars": N, "dofs": D, "factors": int(va.shape[0]), "retired_vars": gone, "factors_left": int(keep.sum()),
+           "ms_shrink": ms, "ms_recreate": mc, "ratio_recreate_over_shrink": mc / ms, "ms_shrink_all": t_shr, "ms_recreate_all": t_new,
+           "spread_shrink": (max(t_shr) - min(t_shr)) / ms, "spread_recreate": (max(t_new) - min(t_new)) / mc,
+           "sweeps_per_s_shrunk": statistics.median(ss), "sweeps_per_s_created": statistics.median(sc),
+           "ratio_shrunk_over_created": statistics.median(ss) / statistics.median(sc),
+           "spread_shrunk": (max(ss) - min(ss)) / statistics.median(ss), "spread_created": (max(sc) - min(sc)) / statistics.median(sc),
+           "sweeps_per_s_shrunk_all": ss, "sweeps_per_s_created_all": sc, "sweeps_per_s_vs_parent": vs_parent}
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'profiles', 'linear_shrink.json')
+    with open(path, 'w') as fh:
+        json.dump(out, fh, indent=1)
+        fh.write('\n')
+    print(json.dumps(out))
+
+
+if a.shrink:
+    shrink_profile()
+    sys.exit(0)
 if a.marginals:
     marginals_profile()
     sys.exit(0)
