@@ -12,7 +12,7 @@
 // edge order (vmsg, through an LDS transpose) for the belief stage; beliefs are records [N][d + d(d+1)/2 + d]
 // (eta | packed Lambda | mu) gathered per factor.  Lambda_f is constant: packed upper 2d x 2d, read every sweep.
 // HBM-bound like the BA sweep; d <= 6 keeps a factor's working set in registers (one wave per SIMD for d = 6).
-#include "gbp_lin_handle.hpp"
+#include "gbp_lin_generation.hpp"
 #include "gbp_lin_robust.hpp"
 #include "gbp_math.hpp"
 
@@ -259,26 +259,20 @@ static int lin_create_impl(gbp_lin *h, const gbp_lin_desc_t *d)
     LHIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     h->D = D;
     h->has_const = d->factor_const != nullptr;
-    const int P = D * (D + 1) / 2, P2 = D * (2 * D + 1), D2 = 2 * D;
-    LinParams &p = h->p;
-    p.N = N; p.F = F; p.damping = d->eta_damping;
+    const int P = D * (D + 1) / 2, P2 = D * (2 * D + 1), D2 = 2 * D, R = D + P;
+    h->p.damping = d->eta_damping;
 
     // factor data -> SoA, packed upper; adjacency CSR in ascending factor id (= append order, ndim_posegraph.py:86-88)
     std::vector<int32_t> va(d->var_a, d->var_a + F), vb(d->var_b, d->var_b + F), vptr((size_t)N + 1, 0), vadj((size_t)2 * F);
-    std::vector<double> feta((size_t)D2 * F), flam((size_t)P2 * F), fconst((size_t)F, 0.0);
+    std::vector<double> feta((size_t)D2 * F), flam((size_t)P2 * F), fconst((size_t)F, 0.0), prior((size_t)N * R);
     for (int f = 0; f < F; ++f) {
         if (va[f] < 0 || va[f] >= N || vb[f] < 0 || vb[f] >= N || va[f] == vb[f])
             return set_error(GBP_EINVAL, "factor %d joins variables (%d, %d): need two different ids in [0, %d)", f, va[f], vb[f], N);
         ++vptr[va[f] + 1]; ++vptr[vb[f] + 1];
-        for (int i = 0; i < D2; ++i) {
-            feta[(size_t)i * F + f] = d->factor_eta[(size_t)f * D2 + i];
-            for (int j = i; j < D2; ++j) {
-                const int at = i * D2 - (i * (i - 1)) / 2 + (j - i);
-                flam[(size_t)at * F + f] = d->factor_lam[((size_t)f * D2 + i) * D2 + j];
-            }
-        }
-        if (d->factor_const) fconst[f] = d->factor_const[f];
     }
+    lin_pack_factors(D, F, d->factor_eta, d->factor_lam, feta.data(), flam.data());
+    if (d->factor_const) fconst.assign(d->factor_const, d->factor_const + F);
+    lin_pack_priors(D, N, d->prior_eta, d->prior_lam, prior.data());
     for (int v = 0; v < N; ++v) vptr[v + 1] += vptr[v];
     std::vector<int32_t> epos_a((size_t)F), epos_b((size_t)F);
     {
@@ -288,28 +282,28 @@ static int lin_create_impl(gbp_lin *h, const gbp_lin_desc_t *d)
             epos_b[f] = fill[vb[f]]; vadj[fill[vb[f]]++] = (f << 1) | 1;
         }
     }
-    std::vector<double> prior((size_t)N * (D + P)), zeros_msg((size_t)(D + P) * F, 0.0), zeros_bel((size_t)N * (D + P + D), 0.0);
-    for (int v = 0; v < N; ++v) {
-        for (int i = 0; i < D; ++i) {
-            prior[(size_t)v * (D + P) + i] = d->prior_eta[(size_t)v * D + i];
-            for (int j = i; j < D; ++j) prior[(size_t)v * (D + P) + D + i * D - (i * (i - 1)) / 2 + (j - i)] = d->prior_lam[((size_t)v * D + i) * D + j];
-        }
+
+    // the first generation: allocated, filled and committed like every later one (gbp_lin_generation.hpp), with nothing to replace.
+    // The host vectors above are the sources of the copies and outlive the one synchronisation, on the failure path too.
+    LinScratch mem;
+    LinGen g;
+    auto copy = [&](auto *dst, const auto &v) { return v.empty() ? hipSuccess : hipMemcpyAsync(dst, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice, h->stream); };
+    auto zero = [&](double *dst, size_t n) { return n ? hipMemsetAsync(dst, 0, n * sizeof(double), h->stream) : hipSuccess; };
+    const int rc = [&]() -> int {
+        LCHK(lin_gen_alloc(h, mem, g, N, F, false, true));
+        LHIPCHK(copy(g.va, va)); LHIPCHK(copy(g.vb, vb)); LHIPCHK(copy(g.vptr, vptr)); LHIPCHK(copy(g.vadj, vadj));
+        LHIPCHK(copy(g.feta, feta)); LHIPCHK(copy(g.flam, flam)); LHIPCHK(copy(g.fconst, fconst)); LHIPCHK(copy(g.prior, prior));
+        LHIPCHK(copy(g.epos_a, epos_a)); LHIPCHK(copy(g.epos_b, epos_b));
+        LHIPCHK(zero(g.msg_a, (size_t)R * F)); LHIPCHK(zero(g.msg_b, (size_t)R * F)); LHIPCHK(zero(g.vmsg, (size_t)2 * F * R));
+        LHIPCHK(zero(g.bel, (size_t)N * (R + D))); LHIPCHK(zero(g.d_red, (size_t)g.red_blocks));
+        LHIPCHK(hipStreamSynchronize(h->stream));
+        return GBP_OK;
+    }();
+    if (rc != GBP_OK) {
+        (void)hipStreamSynchronize(h->stream);              // before `mem` frees what the stream may still be writing
+        return rc;
     }
-    int *dva, *dvb, *dvptr, *dvadj;
-    double *dfeta, *dflam, *dfconst, *dprior;
-    LCHK(lin_upload(h, &dva, va)); LCHK(lin_upload(h, &dvb, vb)); LCHK(lin_upload(h, &dvptr, vptr)); LCHK(lin_upload(h, &dvadj, vadj));
-    LCHK(lin_upload(h, &dfeta, feta)); LCHK(lin_upload(h, &dflam, flam)); LCHK(lin_upload(h, &dfconst, fconst)); LCHK(lin_upload(h, &dprior, prior));
-    LCHK(lin_upload(h, &p.msg_a, zeros_msg)); LCHK(lin_upload(h, &p.msg_b, zeros_msg)); LCHK(lin_upload(h, &p.bel, zeros_bel));
-    {
-        std::vector<double> zeros_v((size_t)2 * F * (D + P), 0.0);
-        int *dea, *deb;
-        LCHK(lin_upload(h, &p.vmsg, zeros_v)); LCHK(lin_upload(h, &dea, epos_a)); LCHK(lin_upload(h, &deb, epos_b));
-        p.epos_a = dea; p.epos_b = deb;
-    }
-    p.va = dva; p.vb = dvb; p.vptr = dvptr; p.vadj = dvadj; p.feta = dfeta; p.flam = dflam; p.fconst = dfconst; p.prior = dprior;
-    h->red_blocks = std::max(1, (F + 255) / 256);
-    std::vector<double> zr((size_t)h->red_blocks, 0.0);
-    LCHK(lin_upload(h, &h->d_red, zr));
+    lin_gen_commit(h, mem, g);
     return GBP_OK;
 }
 
@@ -396,7 +390,7 @@ static void unpack_sym(int D, const double *packed, size_t stride, double *dense
 {
     for (int i = 0; i < D; ++i)
         for (int j = i; j < D; ++j) {
-            const double v = packed[(size_t)(i * D - (i * (i - 1)) / 2 + (j - i)) * stride];
+            const double v = packed[(size_t)lin_packed_at(D, i, j) * stride];
             dense[i * D + j] = v; dense[j * D + i] = v;
         }
 }

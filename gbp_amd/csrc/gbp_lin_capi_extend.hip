@@ -3,15 +3,14 @@
 // losing the messages (kernels and the placement argument: gbp_lin_extend.hpp).
 //
 // One call: validate on the host (only the appended part is looked at), pack and upload the new factors and priors, allocate EVERY new
-// array, build them on the device from the old ones -- which are only read -- and synchronise; only then swap the pointers in, free
-// the arrays that were replaced (and take them out of `allocs`: a handle grown a thousand times holds one generation), drop the MAP
-// and marginal workspaces (sized by N and F; the next solve re-makes them) and, where the handle had beliefs, run the belief stage
-// over all variables.  A failure before the swap frees what was allocated and leaves the handle as it was.  Host work and host <->
-// device traffic are proportional to dN and dF; no existing array crosses to the host.
+// array (lin_gen_alloc), build them on the device from the old ones -- which are only read -- and synchronise; only then commit the
+// new generation (lin_gen_commit, gbp_lin_generation.hpp) and, where the handle had beliefs, run the belief stage over all variables.
+// A failure before the commit frees what was allocated and leaves the handle as it was.  Host work and host <-> device traffic are
+// proportional to dN and dF; no existing array crosses to the host.
 #include "gbp_lin_extend.hpp"
+#include "gbp_lin_generation.hpp"
 
 #include <climits>
-#include <cmath>
 
 namespace gbp {
 size_t sort_pairs_tmp_bytes(size_t n, int bits);                                              // gbp_sort.hip
@@ -23,20 +22,6 @@ using namespace gbp;
 
 namespace {
 
-// device memory of one call: `keep` becomes the handle's after the swap, `temp` is freed at the end of the call either way
-struct ExtMem {
-    std::vector<void *> keep, temp;
-    template <typename T> int get(T **out, size_t n, bool kept)
-    {
-        void *q = nullptr;
-        LHIPCHK(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
-        (kept ? keep : temp).push_back(q);
-        *out = static_cast<T *>(q);
-        return GBP_OK;
-    }
-    static void release(std::vector<void *> &v) { for (void *q : v) (void)hipFree(q); v.clear(); }
-};
-
 // the appended part packed for upload: owned by gbp_lin_extend, so that these sources of asynchronous copies outlive the stream's work on
 // every path, a failure in the middle of ext_build included
 struct ExtHost {
@@ -44,17 +29,8 @@ struct ExtHost {
     std::vector<double> feta, flam, fconst, prior, thr, nvar;
 };
 
-// the arrays that replace the handle's
-struct ExtNew {
-    int *va = nullptr, *vb = nullptr, *vptr = nullptr, *vadj = nullptr, *epos_a = nullptr, *epos_b = nullptr;
-    double *feta = nullptr, *flam = nullptr, *fconst = nullptr, *msg_a = nullptr, *msg_b = nullptr, *bel = nullptr, *prior = nullptr, *vmsg = nullptr;
-    double *d_red = nullptr;                        // nullptr: the old one is large enough
-    int *loss = nullptr, *flag = nullptr;           // the robust arrays, where the grown handle has them
-    double *thr = nullptr, *nvar = nullptr, *w = nullptr;
-};
-
 template <typename T>
-int ext_upload(gbp_lin *h, ExtMem &mem, const T **out, const std::vector<T> &v)
+int ext_upload(gbp_lin *h, LinScratch &mem, const T **out, const std::vector<T> &v)
 {
     T *q = nullptr;
     LCHK(mem.get(&q, v.size(), false));
@@ -72,16 +48,8 @@ void ext_restride(gbp_lin *h, const T *src, const T *tail, T *dst, int rows, int
 
 int ext_blocks(size_t n) { return (int)((n + EXT_BLOCK - 1) / EXT_BLOCK); }
 
-void ext_forget(gbp_lin *h, const void *q)
-{
-    if (!q) return;
-    auto at = std::find(h->allocs.begin(), h->allocs.end(), q);
-    if (at != h->allocs.end()) h->allocs.erase(at);
-    (void)hipFree(const_cast<void *>(q));
-}
-
 // everything up to and including the synchronisation after which nothing can fail: the new arrays, built on the device
-int ext_build(gbp_lin *h, const gbp_lin_extend_desc_t *d, bool robust, ExtMem &mem, ExtHost &host, ExtNew &n)
+int ext_build(gbp_lin *h, const gbp_lin_extend_desc_t *d, bool robust, LinScratch &mem, ExtHost &host, LinGen &n)
 {
     const LinParams &p = h->p;
     const int D = h->D, D2 = 2 * D, P = D * (D + 1) / 2, P2 = D * (2 * D + 1), R = D + P, REC = D + P + D;
@@ -92,18 +60,9 @@ int ext_build(gbp_lin *h, const gbp_lin_extend_desc_t *d, bool robust, ExtMem &m
     std::vector<double> &hfeta = host.feta, &hflam = host.flam, &hfconst = host.fconst, &hprior = host.prior, &hthr = host.thr, &hnvar = host.nvar;
     ha.assign(d->var_a, d->var_a + dF); hb.assign(d->var_b, d->var_b + dF);
     hfeta.resize((size_t)D2 * dF); hflam.resize((size_t)P2 * dF); hprior.resize((size_t)dN * R);
-    for (int f = 0; f < dF; ++f)
-        for (int i = 0; i < D2; ++i) {
-            hfeta[(size_t)i * dF + f] = d->factor_eta[(size_t)f * D2 + i];
-            for (int j = i; j < D2; ++j)
-                hflam[(size_t)(i * D2 - (i * (i - 1)) / 2 + (j - i)) * dF + f] = d->factor_lam[((size_t)f * D2 + i) * D2 + j];
-        }
+    lin_pack_factors(D, dF, d->factor_eta, d->factor_lam, hfeta.data(), hflam.data());
     if (h->has_const) hfconst.assign(d->factor_const, d->factor_const + dF);
-    for (int v = 0; v < dN; ++v)
-        for (int i = 0; i < D; ++i) {
-            hprior[(size_t)v * R + i] = d->prior_eta[(size_t)v * D + i];
-            for (int j = i; j < D; ++j) hprior[(size_t)v * R + D + i * D - (i * (i - 1)) / 2 + (j - i)] = d->prior_lam[((size_t)v * D + i) * D + j];
-        }
+    lin_pack_priors(D, dN, d->prior_eta, d->prior_lam, hprior.data());
     if (robust && d->loss && dF) {
         hloss.assign(d->loss, d->loss + dF);
         hthr.assign((size_t)dF, 1.0); hnvar.assign((size_t)dF, 1.0);
@@ -120,19 +79,7 @@ int ext_build(gbp_lin *h, const gbp_lin_extend_desc_t *d, bool robust, ExtMem &m
     if (!hloss.empty()) { LCHK(ext_upload(h, mem, &tloss, hloss)); LCHK(ext_upload(h, mem, &tthr, hthr)); LCHK(ext_upload(h, mem, &tnvar, hnvar)); }
 
     // ---- every allocation of the call, before the first kernel ----
-    LCHK(mem.get(&n.va, (size_t)F1, true)); LCHK(mem.get(&n.vb, (size_t)F1, true));
-    LCHK(mem.get(&n.feta, (size_t)D2 * F1, true)); LCHK(mem.get(&n.flam, (size_t)P2 * F1, true)); LCHK(mem.get(&n.fconst, (size_t)F1, true));
-    LCHK(mem.get(&n.msg_a, (size_t)R * F1, true)); LCHK(mem.get(&n.msg_b, (size_t)R * F1, true));
-    LCHK(mem.get(&n.bel, (size_t)N1 * REC, true)); LCHK(mem.get(&n.prior, (size_t)N1 * R, true));
-    LCHK(mem.get(&n.vptr, (size_t)N1 + 1, true)); LCHK(mem.get(&n.vadj, (size_t)2 * F1, true));
-    LCHK(mem.get(&n.epos_a, (size_t)F1, true)); LCHK(mem.get(&n.epos_b, (size_t)F1, true));
-    LCHK(mem.get(&n.vmsg, (size_t)2 * F1 * R, true));
-    const int red_blocks = std::max(1, (F1 + 255) / 256);
-    if (red_blocks > h->red_blocks) LCHK(mem.get(&n.d_red, (size_t)red_blocks, true));
-    if (robust) {
-        LCHK(mem.get(&n.loss, (size_t)F1, true)); LCHK(mem.get(&n.thr, (size_t)F1, true)); LCHK(mem.get(&n.nvar, (size_t)F1, true));
-        LCHK(mem.get(&n.w, (size_t)F1, true)); LCHK(mem.get(&n.flag, (size_t)F1, true));
-    }
+    LCHK(lin_gen_alloc(h, mem, n, N1, F1, robust, true));     // d_red grows when ceil(F / 256) does
     int *keys = nullptr, *vals = nullptr, *keys_s = nullptr, *vals_s = nullptr, *enew = nullptr;
     void *sort_tmp = nullptr;
     int bits = 1;
@@ -167,7 +114,7 @@ int ext_build(gbp_lin *h, const gbp_lin_extend_desc_t *d, bool robust, ExtMem &m
         LHIPCHK(hipMemsetAsync(n.bel + (size_t)N * REC, 0, (size_t)dN * REC * sizeof(double), h->stream));
         LHIPCHK(hipMemcpyAsync(n.prior + (size_t)N * R, hprior.data(), hprior.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     }
-    if (n.d_red) LHIPCHK(hipMemsetAsync(n.d_red, 0, (size_t)red_blocks * sizeof(double), h->stream));
+    if (n.d_red) LHIPCHK(hipMemsetAsync(n.d_red, 0, (size_t)n.red_blocks * sizeof(double), h->stream));
     // ---- the CSR: new edges sorted by variable (stable: ascending factor id within one), merged behind each variable's old list ----
     const int *skeys = keys_s, *svals = vals_s;
     if (dF) {
@@ -212,19 +159,8 @@ int ext_validate(gbp_lin *h, const gbp_lin_extend_desc_t *d)
             return set_error(GBP_EINVAL, "new factor %d joins variables (%d, %d): need two different ids in [0, %d)", f, a, b, N1);
     }
     if (d->loss && dF) {                                    // the rules of gbp_lin_set_robust
-        if (!d->threshold) return set_error(GBP_EINVAL, "threshold is NULL");
         bool any = false;
-        for (int f = 0; f < dF; ++f) {
-            const int l = d->loss[f];
-            if (l != GBP_LIN_LOSS_NONE && l != GBP_LIN_LOSS_HUBER && l != GBP_LIN_LOSS_CONSTANT) return set_error(GBP_EINVAL, "new factor %d: unknown loss %d", f, l);
-            if (l == GBP_LIN_LOSS_NONE) continue;
-            any = true;
-            if (!(d->threshold[f] > 0.0) || !std::isfinite(d->threshold[f])) return set_error(GBP_EINVAL, "new factor %d: the threshold must be positive", f);
-            if (l == GBP_LIN_LOSS_CONSTANT) {
-                if (!d->noise_var) return set_error(GBP_EINVAL, "new factor %d has the constant loss: noise_var must be given", f);
-                if (!(d->noise_var[f] > 0.0) || !std::isfinite(d->noise_var[f])) return set_error(GBP_EINVAL, "new factor %d: noise_var must be positive", f);
-            }
-        }
+        LCHK(lin_check_losses(d->loss, d->threshold, d->noise_var, dF, "new factor", &any));
         if ((any || !h->p.w) && !h->has_const)
             return set_error(GBP_EINVAL, "a loss needs the factors' constants: the handle was created with factor_const == NULL");
     }
@@ -253,54 +189,15 @@ int gbp_lin_extend(gbp_lin_t *h, const gbp_lin_extend_desc_t *d)
     // losses are on after the call if they are now, or if the new factors bring some
     const bool robust = h->p.w != nullptr || (d->loss && dF);
     LHIPCHK(hipStreamSynchronize(h->stream));
-    ExtMem mem;
+    LinScratch mem;
     ExtHost host;                                           // read by the stream until the synchronisation in ext_build, or the one below
-    ExtNew n;
+    LinGen n;
     const int rc = ext_build(h, d, robust, mem, host, n);
     if (rc != GBP_OK) {                                     // the handle's arrays were only read: it goes on as it was
-        (void)hipStreamSynchronize(h->stream);
-        ExtMem::release(mem.keep); ExtMem::release(mem.temp);
+        (void)hipStreamSynchronize(h->stream);              // before `mem` frees what the stream may still be writing
         return rc;
     }
-    ExtMem::release(mem.temp);
-    // ---- the swap ----
-    LinParams &p = h->p;
-    for (const void *q : {(const void *)p.va, (const void *)p.vb, (const void *)p.feta, (const void *)p.flam, (const void *)p.fconst, (const void *)p.msg_a,
-                          (const void *)p.msg_b, (const void *)p.bel, (const void *)p.prior, (const void *)p.vptr, (const void *)p.vadj, (const void *)p.vmsg,
-                          (const void *)p.epos_a, (const void *)p.epos_b})
-        ext_forget(h, q);
-    if (h->rob_alloc) {
-        for (const void *q : {(const void *)h->rob.loss, (const void *)h->rob.thr, (const void *)h->rob.nvar, (const void *)h->rob.w, (const void *)h->rob.flag}) ext_forget(h, q);
-        h->rob = LinRobust{};
-        h->rob_alloc = false;
-    }
-    if (h->map_alloc) {                                     // sized by N and F: re-made by the next solve
-        const LinMap &m = h->map;
-        for (const void *q : {(const void *)m.ldl, (const void *)m.jeta, (const void *)m.x, (const void *)m.r, (const void *)m.z, (const void *)m.p, (const void *)m.q,
-                              (const void *)m.ebuf, (const void *)m.pq_part, (const void *)m.rz_part, (const void *)m.rr_part})
-            ext_forget(h, q);
-        h->map = LinMap{};
-    }
-    h->map_alloc = h->map_ready = h->map_solved = false;
-    h->map_eta_norm = 0.0;
-    if (h->marg_ready) {                                    // the staging of the outputs does not depend on N or F and stays
-        LinMarg &m = h->marg;
-        for (const void *q : {(const void *)m.x, (const void *)m.r, (const void *)m.z, (const void *)m.p, (const void *)m.q, (const void *)m.ebuf, (const void *)m.pq_part,
-                              (const void *)m.rz_part, (const void *)m.rr_part})
-            ext_forget(h, q);
-        m.x = m.r = m.z = m.p = m.q = m.ebuf = m.pq_part = m.rz_part = m.rr_part = nullptr;
-        h->marg_ready = false;
-    }
-    if (n.d_red) { ext_forget(h, h->d_red); h->d_red = n.d_red; h->red_blocks = std::max(1, (p.F + dF + 255) / 256); }
-    h->allocs.insert(h->allocs.end(), mem.keep.begin(), mem.keep.end());
-    p.N += dN; p.F += dF;
-    p.va = n.va; p.vb = n.vb; p.feta = n.feta; p.flam = n.flam; p.fconst = n.fconst; p.msg_a = n.msg_a; p.msg_b = n.msg_b;
-    p.bel = n.bel; p.prior = n.prior; p.vptr = n.vptr; p.vadj = n.vadj; p.vmsg = n.vmsg; p.epos_a = n.epos_a; p.epos_b = n.epos_b;
-    if (robust) {
-        h->rob = LinRobust{n.loss, n.thr, n.nvar, n.w, n.flag};
-        h->rob_alloc = true;
-        p.w = n.w;
-    }
+    lin_gen_commit(h, mem, n);
     // beliefs of the grown graph (update_all_beliefs gbp.py:56-58): old variables add the same messages in the same order plus zeros,
     // new ones hold their prior
     if (h->has_beliefs) return gbp_lin_update_beliefs(h);

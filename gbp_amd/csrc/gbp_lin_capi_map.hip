@@ -16,15 +16,6 @@ using namespace gbp;
 
 namespace {
 
-int map_alloc(gbp_lin *h, double **out, size_t n)
-{
-    void *q = nullptr;
-    LHIPCHK(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(double)));
-    h->allocs.push_back(q);
-    *out = static_cast<double *>(q);
-    return GBP_OK;
-}
-
 // sum of the first nb doubles of a partials array, in index order
 int map_read_sum(gbp_lin *h, const double *part, double *out)
 {
@@ -48,10 +39,10 @@ int map_prepare(gbp_lin *h)
     const size_t nd = (size_t)h->p.N * D;
     if (!h->map_alloc) {
         m.nb = std::min(MAP_MAX_BLOCKS, std::max(1, (h->p.N + MAP_BLOCK - 1) / MAP_BLOCK));
-        LCHK(map_alloc(h, &m.ldl, (size_t)h->p.N * (P + D))); LCHK(map_alloc(h, &m.jeta, nd));
-        LCHK(map_alloc(h, &m.x, nd)); LCHK(map_alloc(h, &m.r, nd)); LCHK(map_alloc(h, &m.z, nd)); LCHK(map_alloc(h, &m.p, nd)); LCHK(map_alloc(h, &m.q, nd));
-        LCHK(map_alloc(h, &m.ebuf, (size_t)2 * h->p.F * D));
-        LCHK(map_alloc(h, &m.pq_part, (size_t)m.nb)); LCHK(map_alloc(h, &m.rz_part, (size_t)2 * m.nb)); LCHK(map_alloc(h, &m.rr_part, (size_t)m.nb));
+        LCHK(lin_alloc(h, &m.ldl, (size_t)h->p.N * (P + D))); LCHK(lin_alloc(h, &m.jeta, nd));
+        LCHK(lin_alloc(h, &m.x, nd)); LCHK(lin_alloc(h, &m.r, nd)); LCHK(lin_alloc(h, &m.z, nd)); LCHK(lin_alloc(h, &m.p, nd)); LCHK(lin_alloc(h, &m.q, nd));
+        LCHK(lin_alloc(h, &m.ebuf, (size_t)2 * h->p.F * D));
+        LCHK(lin_alloc(h, &m.pq_part, (size_t)m.nb)); LCHK(lin_alloc(h, &m.rz_part, (size_t)2 * m.nb)); LCHK(lin_alloc(h, &m.rr_part, (size_t)m.nb));
         LHIPCHK(hipMemsetAsync(m.pq_part, 0, (size_t)m.nb * sizeof(double), h->stream));
         LHIPCHK(hipMemsetAsync(m.rz_part, 0, (size_t)2 * m.nb * sizeof(double), h->stream));
         LHIPCHK(hipMemsetAsync(m.rr_part, 0, (size_t)m.nb * sizeof(double), h->stream));

@@ -18,30 +18,17 @@ namespace {
 
 constexpr int K = MARG_COLS;
 
-int marg_alloc(gbp_lin *h, double **out, size_t n)
-{
-    void *q = nullptr;
-    LHIPCHK(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(double)));
-    h->allocs.push_back(q);
-    *out = static_cast<double *>(q);
-    return GBP_OK;
-}
-
 // The staging of a call's outputs and ids: kept with the workspace and only ever grown, so that a call of a size seen before allocates
-// nothing.  The old block is released here and its entry in `allocs` taken over, so the handle still frees everything once.
+// nothing.  The old block is given back here, so the handle still holds one.
 int marg_stage_reserve(gbp_lin *h, size_t bytes)
 {
     LinMarg &m = h->marg;
     if (bytes <= m.stage_bytes) return GBP_OK;
-    void *q = nullptr;
-    LHIPCHK(hipMalloc(&q, bytes));
-    auto at = std::find(h->allocs.begin(), h->allocs.end(), m.stage);
-    if (m.stage && at != h->allocs.end()) {
+    char *q = nullptr;
+    LCHK(lin_alloc(h, &q, bytes));
+    if (m.stage) {
         LHIPCHK(hipStreamSynchronize(h->stream));
-        (void)hipFree(m.stage);
-        *at = q;
-    } else {
-        h->allocs.push_back(q);
+        lin_free(h, m.stage);
     }
     m.stage = q;
     m.stage_bytes = bytes;
@@ -55,11 +42,11 @@ int marg_prepare(gbp_lin *h)
     LinMarg &m = h->marg;
     const size_t ndk = (size_t)h->p.N * h->D * K;
     m.nb = std::min(MAP_MAX_BLOCKS, std::max(1, (h->p.N + MAP_BLOCK / K - 1) / (MAP_BLOCK / K)));
-    LCHK(marg_alloc(h, &m.x, ndk)); LCHK(marg_alloc(h, &m.r, ndk)); LCHK(marg_alloc(h, &m.z, ndk)); LCHK(marg_alloc(h, &m.p, ndk));
-    LCHK(marg_alloc(h, &m.q, ndk));
-    LCHK(marg_alloc(h, &m.ebuf, (size_t)2 * h->p.F * h->D * K));
-    LCHK(marg_alloc(h, &m.pq_part, (size_t)m.nb * K)); LCHK(marg_alloc(h, &m.rz_part, (size_t)2 * m.nb * K));
-    LCHK(marg_alloc(h, &m.rr_part, (size_t)m.nb * K));
+    LCHK(lin_alloc(h, &m.x, ndk)); LCHK(lin_alloc(h, &m.r, ndk)); LCHK(lin_alloc(h, &m.z, ndk)); LCHK(lin_alloc(h, &m.p, ndk));
+    LCHK(lin_alloc(h, &m.q, ndk));
+    LCHK(lin_alloc(h, &m.ebuf, (size_t)2 * h->p.F * h->D * K));
+    LCHK(lin_alloc(h, &m.pq_part, (size_t)m.nb * K)); LCHK(lin_alloc(h, &m.rz_part, (size_t)2 * m.nb * K));
+    LCHK(lin_alloc(h, &m.rr_part, (size_t)m.nb * K));
     LHIPCHK(hipMemsetAsync(m.pq_part, 0, (size_t)m.nb * K * sizeof(double), h->stream));
     LHIPCHK(hipMemsetAsync(m.rz_part, 0, (size_t)2 * m.nb * K * sizeof(double), h->stream));
     LHIPCHK(hipMemsetAsync(m.rr_part, 0, (size_t)m.nb * K * sizeof(double), h->stream));

@@ -9,22 +9,11 @@
 // workspace; the iterate of the last solve stays where it is (gbp_lin_get_map).  A robust sweep is three kernels queued on the handle's
 // stream (k_lin_robustify, k_lin_factor<D, true>, k_lin_belief): no host round trip, no floating-point atomics.
 #include "gbp_lin_robust.hpp"
-
-#include <cmath>
+#include "gbp_lin_generation.hpp"
 
 using namespace gbp;
 
 namespace {
-
-template <typename T>
-int rob_alloc(gbp_lin *h, T **out, size_t n)
-{
-    void *q = nullptr;
-    LHIPCHK(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
-    h->allocs.push_back(q);
-    *out = static_cast<T *>(q);
-    return GBP_OK;
-}
 
 template <typename T>
 int rob_upload(gbp_lin *h, const T *dst, const std::vector<T> &v)
@@ -76,26 +65,13 @@ int gbp_lin_set_robust(gbp_lin_t *h, const int32_t *loss, const double *threshol
         if (h->rob_alloc) LCHK(rob_reset(h));
         return GBP_OK;
     }
-    if (!threshold) return set_error(GBP_EINVAL, "threshold is NULL");
     bool any = false;
-    for (int f = 0; f < F; ++f) {
-        if (loss[f] != GBP_LIN_LOSS_NONE && loss[f] != GBP_LIN_LOSS_HUBER && loss[f] != GBP_LIN_LOSS_CONSTANT)
-            return set_error(GBP_EINVAL, "factor %d: unknown loss %d", f, loss[f]);
-        if (loss[f] == GBP_LIN_LOSS_NONE) continue;
-        any = true;
-        if (!(threshold[f] > 0.0) || !std::isfinite(threshold[f])) return set_error(GBP_EINVAL, "factor %d: the threshold must be positive", f);
-        if (loss[f] == GBP_LIN_LOSS_CONSTANT) {
-            if (!noise_var) return set_error(GBP_EINVAL, "factor %d has the constant loss: noise_var must be given", f);
-            if (!(noise_var[f] > 0.0) || !std::isfinite(noise_var[f])) return set_error(GBP_EINVAL, "factor %d: noise_var must be positive", f);
-        }
-    }
+    LCHK(lin_check_losses(loss, threshold, noise_var, F, "factor", &any));
     if (any && !h->has_const)
         return set_error(GBP_EINVAL, "a loss needs the factors' constants: the handle was created with factor_const == NULL");
     if (!h->rob_alloc) {
-        int *dl = nullptr; double *dt = nullptr, *dn = nullptr;
-        LCHK(rob_alloc(h, &dl, (size_t)F)); LCHK(rob_alloc(h, &dt, (size_t)F)); LCHK(rob_alloc(h, &dn, (size_t)F));
-        LCHK(rob_alloc(h, &h->rob.w, (size_t)F)); LCHK(rob_alloc(h, &h->rob.flag, (size_t)F));
-        h->rob.loss = dl; h->rob.thr = dt; h->rob.nvar = dn;
+        LCHK(lin_alloc(h, &h->rob.loss, (size_t)F)); LCHK(lin_alloc(h, &h->rob.thr, (size_t)F)); LCHK(lin_alloc(h, &h->rob.nvar, (size_t)F));
+        LCHK(lin_alloc(h, &h->rob.w, (size_t)F)); LCHK(lin_alloc(h, &h->rob.flag, (size_t)F));
         h->rob_alloc = true;
     }
     std::vector<int> hl(loss, loss + F);

@@ -3,13 +3,13 @@
 // renumbering argument: gbp_lin_shrink.hpp).
 //
 // One call: validate the two lists on the host (range and repeats: sorted copies, so the work is that of the lists), upload them, make
-// the flags, scan them once and bring N', F', 2F' back in one copy; allocate EVERY new array, build them on the device from the old
-// ones -- which are only read -- and synchronise; only then swap the pointers in, free the arrays that were replaced (and take them
-// out of `allocs`: a handle shrunk and grown a thousand times holds one generation), drop the MAP and marginal workspaces (sized by N
-// and F; the next solve re-makes them) and, where the handle had beliefs, run the belief stage over the survivors.  A failure before
-// the swap frees what was allocated and leaves the handle as it was.  Host work and host <-> device traffic are proportional to the two
-// lists, plus the maps where the caller asks for them; no existing array crosses to the host.
+// the flags, scan them once and bring N', F', 2F' back in one copy; allocate EVERY new array (lin_gen_alloc), build them on the device
+// from the old ones -- which are only read -- and synchronise; only then commit the new generation (lin_gen_commit,
+// gbp_lin_generation.hpp) and, where the handle had beliefs, run the belief stage over the survivors.  A failure before the commit
+// frees what was allocated and leaves the handle as it was.  Host work and host <-> device traffic are proportional to the two lists,
+// plus the maps where the caller asks for them; no existing array crosses to the host.
 #include "gbp_lin_shrink.hpp"
+#include "gbp_lin_generation.hpp"
 
 #include <rocprim/device/device_scan.hpp>
 
@@ -19,44 +19,12 @@ using namespace gbp;
 
 namespace {
 
-// device memory of one call: `keep` becomes the handle's after the swap, `temp` is freed at the end of the call either way
-struct ShrMem {
-    std::vector<void *> keep, temp;
-    template <typename T> int get(T **out, size_t n, bool kept)
-    {
-        void *q = nullptr;
-        LHIPCHK(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
-        (kept ? keep : temp).push_back(q);
-        *out = static_cast<T *>(q);
-        return GBP_OK;
-    }
-    static void release(std::vector<void *> &v) { for (void *q : v) (void)hipFree(q); v.clear(); }
-};
-
-// the arrays that replace the handle's
-struct ShrNew {
-    int N = 0, F = 0;
-    int *va = nullptr, *vb = nullptr, *vptr = nullptr, *vadj = nullptr, *epos_a = nullptr, *epos_b = nullptr;
-    double *feta = nullptr, *flam = nullptr, *fconst = nullptr, *msg_a = nullptr, *msg_b = nullptr, *bel = nullptr, *prior = nullptr, *vmsg = nullptr;
-    int *loss = nullptr, *flag = nullptr;           // the robust arrays, where losses are set
-    double *thr = nullptr, *nvar = nullptr, *w = nullptr;
-    int *maps = nullptr;                            // [N | F] of before the call (temp)
-};
-
 int shr_blocks(size_t n) { return (int)((n + SHR_BLOCK - 1) / SHR_BLOCK); }
 
 template <typename T>
 void shr_gather(gbp_lin *h, const T *src, const int *surv_f, T *dst, int rows, int F, int F1)
 {
     if (F1 > 0) hipLaunchKernelGGL((k_shr_gather<T>), dim3(shr_blocks((size_t)F1), rows), dim3(SHR_BLOCK), 0, h->stream, src, surv_f, dst, F, F1);
-}
-
-void shr_forget(gbp_lin *h, const void *q)
-{
-    if (!q) return;
-    auto at = std::find(h->allocs.begin(), h->allocs.end(), q);
-    if (at != h->allocs.end()) h->allocs.erase(at);
-    (void)hipFree(const_cast<void *>(q));
 }
 
 // ids in [0, n), none twice; `what` names the list in the message
@@ -74,7 +42,7 @@ int shr_check_list(const int32_t *ids, int count, int n, const char *what)
 }
 
 // everything up to and including the synchronisation after which nothing can fail: the new arrays, built on the device
-int shr_build(gbp_lin *h, const gbp_lin_shrink_desc_t *d, bool robust, ShrMem &mem, ShrNew &n)
+int shr_build(gbp_lin *h, const gbp_lin_shrink_desc_t *d, bool robust, LinScratch &mem, LinGen &n)
 {
     const LinParams &p = h->p;
     const int D = h->D, D2 = 2 * D, P = D * (D + 1) / 2, P2 = D * (2 * D + 1), R = D + P, REC = D + P + D;
@@ -109,26 +77,16 @@ int shr_build(gbp_lin *h, const gbp_lin_shrink_desc_t *d, bool robust, ShrMem &m
     const int N1 = hs[0], F1 = hs[1];
     if (N1 != N - nr || F1 < 0 || F1 > F - nd || hs[2] != 2 * F1)
         return set_error(GBP_EHIP, "the scan of the keep flags gave %d variables, %d factors, %d edges from %d - %d and %d - %d", N1, F1, hs[2], N, nr, F, nd);
-    n.N = N1; n.F = F1;
 
     // ---- every allocation of the new generation, before the first kernel that builds it ----
-    int *surv_v = nullptr, *surv_f = nullptr;
-    LCHK(mem.get(&n.maps, (size_t)N + F, false)); LCHK(mem.get(&surv_v, (size_t)N1, false)); LCHK(mem.get(&surv_f, (size_t)F1, false));
-    LCHK(mem.get(&n.va, (size_t)F1, true)); LCHK(mem.get(&n.vb, (size_t)F1, true));
-    LCHK(mem.get(&n.feta, (size_t)D2 * F1, true)); LCHK(mem.get(&n.flam, (size_t)P2 * F1, true)); LCHK(mem.get(&n.fconst, (size_t)F1, true));
-    LCHK(mem.get(&n.msg_a, (size_t)R * F1, true)); LCHK(mem.get(&n.msg_b, (size_t)R * F1, true));
-    LCHK(mem.get(&n.bel, (size_t)N1 * REC, true)); LCHK(mem.get(&n.prior, (size_t)N1 * R, true));
-    LCHK(mem.get(&n.vptr, (size_t)N1 + 1, true)); LCHK(mem.get(&n.vadj, (size_t)2 * F1, true));
-    LCHK(mem.get(&n.epos_a, (size_t)F1, true)); LCHK(mem.get(&n.epos_b, (size_t)F1, true));
-    LCHK(mem.get(&n.vmsg, (size_t)2 * F1 * R, true));
-    if (robust) {
-        LCHK(mem.get(&n.loss, (size_t)F1, true)); LCHK(mem.get(&n.thr, (size_t)F1, true)); LCHK(mem.get(&n.nvar, (size_t)F1, true));
-        LCHK(mem.get(&n.w, (size_t)F1, true)); LCHK(mem.get(&n.flag, (size_t)F1, true));
-    }
+    // d_red stays: it holds ceil(F / 256) >= max(1, ceil(F' / 256)) partials, and the energy's launch goes by red_blocks
+    int *maps = nullptr, *surv_v = nullptr, *surv_f = nullptr;          // maps: [N | F] of before the call
+    LCHK(mem.get(&maps, (size_t)N + F, false)); LCHK(mem.get(&surv_v, (size_t)N1, false)); LCHK(mem.get(&surv_f, (size_t)F1, false));
+    LCHK(lin_gen_alloc(h, mem, n, N1, F1, robust, false));
 
     // ---- the maps and the lists of survivors ----
-    const int *ckeep = keep, *cpos = pos, *csurv = surv_f, *cmaps = n.maps;
-    if (N + F) hipLaunchKernelGGL(k_shr_maps, dim3(shr_blocks((size_t)N + F)), dim3(SHR_BLOCK), 0, h->stream, ckeep, cpos, N, F, n.maps, surv_v, surv_f);
+    const int *ckeep = keep, *cpos = pos, *csurv = surv_f, *cmaps = maps;
+    if (N + F) hipLaunchKernelGGL(k_shr_maps, dim3(shr_blocks((size_t)N + F)), dim3(SHR_BLOCK), 0, h->stream, ckeep, cpos, N, F, maps, surv_v, surv_f);
     // ---- factor-strided arrays: [row][F] -> [row][F1] ----
     if (F1) {
         hipLaunchKernelGGL(k_shr_ends, dim3(shr_blocks((size_t)F1)), dim3(SHR_BLOCK), 0, h->stream, p.va, csurv, cmaps, n.va, F1);
@@ -153,8 +111,8 @@ int shr_build(gbp_lin *h, const gbp_lin_shrink_desc_t *d, bool robust, ShrMem &m
         hipLaunchKernelGGL(k_shr_fold, dim3(shr_blocks((size_t)N * REC)), dim3(SHR_BLOCK), 0, h->stream, ckeep, cpos, p.vptr, p.vadj, (const int *)fold_side, N, R, REC,
                            p.prior, (const double *)p.vmsg, (const double *)p.bel, n.prior, n.bel);
     LHIPCHK(hipGetLastError());
-    if (d->var_map && N) LHIPCHK(hipMemcpyAsync(d->var_map, n.maps, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    if (d->factor_map && F) LHIPCHK(hipMemcpyAsync(d->factor_map, n.maps + N, (size_t)F * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (d->var_map && N) LHIPCHK(hipMemcpyAsync(d->var_map, maps, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (d->factor_map && F) LHIPCHK(hipMemcpyAsync(d->factor_map, maps + N, (size_t)F * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     LHIPCHK(hipStreamSynchronize(h->stream));              // nothing below can fail
     return GBP_OK;
 }
@@ -185,54 +143,14 @@ int gbp_lin_shrink(gbp_lin_t *h, const gbp_lin_shrink_desc_t *d)
     }
     const bool robust = h->p.w != nullptr;                  // a handle whose losses were cleared keeps stale arrays: they are freed, not carried
     LHIPCHK(hipStreamSynchronize(h->stream));
-    ShrMem mem;
-    ShrNew n;
+    LinScratch mem;
+    LinGen n;
     const int rc = shr_build(h, d, robust, mem, n);
     if (rc != GBP_OK) {                                     // the handle's arrays were only read: it goes on as it was
-        (void)hipStreamSynchronize(h->stream);
-        ShrMem::release(mem.keep); ShrMem::release(mem.temp);
+        (void)hipStreamSynchronize(h->stream);              // before `mem` frees what the stream may still be writing
         return rc;
     }
-    ShrMem::release(mem.temp);
-    // ---- the swap ----
-    LinParams &p = h->p;
-    for (const void *q : {(const void *)p.va, (const void *)p.vb, (const void *)p.feta, (const void *)p.flam, (const void *)p.fconst, (const void *)p.msg_a,
-                          (const void *)p.msg_b, (const void *)p.bel, (const void *)p.prior, (const void *)p.vptr, (const void *)p.vadj, (const void *)p.vmsg,
-                          (const void *)p.epos_a, (const void *)p.epos_b})
-        shr_forget(h, q);
-    if (h->rob_alloc) {
-        for (const void *q : {(const void *)h->rob.loss, (const void *)h->rob.thr, (const void *)h->rob.nvar, (const void *)h->rob.w, (const void *)h->rob.flag}) shr_forget(h, q);
-        h->rob = LinRobust{};
-        h->rob_alloc = false;
-    }
-    if (h->map_alloc) {                                     // sized by N and F: re-made by the next solve
-        const LinMap &m = h->map;
-        for (const void *q : {(const void *)m.ldl, (const void *)m.jeta, (const void *)m.x, (const void *)m.r, (const void *)m.z, (const void *)m.p, (const void *)m.q,
-                              (const void *)m.ebuf, (const void *)m.pq_part, (const void *)m.rz_part, (const void *)m.rr_part})
-            shr_forget(h, q);
-        h->map = LinMap{};
-    }
-    h->map_alloc = h->map_ready = h->map_solved = false;
-    h->map_eta_norm = 0.0;
-    if (h->marg_ready) {                                    // the staging of the outputs does not depend on N or F and stays
-        LinMarg &m = h->marg;
-        for (const void *q : {(const void *)m.x, (const void *)m.r, (const void *)m.z, (const void *)m.p, (const void *)m.q, (const void *)m.ebuf, (const void *)m.pq_part,
-                              (const void *)m.rz_part, (const void *)m.rr_part})
-            shr_forget(h, q);
-        m.x = m.r = m.z = m.p = m.q = m.ebuf = m.pq_part = m.rz_part = m.rr_part = nullptr;
-        h->marg_ready = false;
-    }
-    // d_red stays: it holds ceil(F / 256) >= max(1, ceil(F' / 256)) partials, and the energy's launch goes by red_blocks
-    h->allocs.insert(h->allocs.end(), mem.keep.begin(), mem.keep.end());
-    p.N = n.N; p.F = n.F;
-    p.va = n.va; p.vb = n.vb; p.feta = n.feta; p.flam = n.flam; p.fconst = n.fconst; p.msg_a = n.msg_a; p.msg_b = n.msg_b;
-    p.bel = n.bel; p.prior = n.prior; p.vptr = n.vptr; p.vadj = n.vadj; p.vmsg = n.vmsg; p.epos_a = n.epos_a; p.epos_b = n.epos_b;
-    p.w = nullptr;
-    if (robust) {
-        h->rob = LinRobust{n.loss, n.thr, n.nvar, n.w, n.flag};
-        h->rob_alloc = true;
-        p.w = n.w;
-    }
+    lin_gen_commit(h, mem, n);
     // beliefs of the shrunk graph (update_all_beliefs gbp.py:56-58): the folded prior, then the surviving messages in adjacency order
     if (h->has_beliefs) return gbp_lin_update_beliefs(h);
     return GBP_OK;

@@ -1,5 +1,6 @@
 // gbp_lin_handle.hpp -- what the translation units of the linear engine (include/gbp_lin.h) share: the kernel parameter block, the
-// handle behind gbp_lin_t, the error / entry macros and the two host helpers every entry point uses.
+// handle behind gbp_lin_t, the error / entry macros and the host helpers every entry point uses (the handle's one allocator among them).
+// What create, extend and shrink share on the host -- a generation of the graph's arrays and its commit -- is gbp_lin_generation.hpp.
 //   gbp_lin_capi.hip       create / destroy, the sweep (k_lin_factor, k_lin_belief), energy, getters
 //   gbp_lin_capi_map.hip   the batch MAP by block-Jacobi conjugate gradients (kernels in gbp_lin_map.hpp)
 //   gbp_lin_capi_marg.hip  exact marginal covariances by the same iteration on 8 columns at a time (kernels in gbp_lin_marg.hpp)
@@ -110,16 +111,24 @@ int lin_map_prepare(gbp_lin *h);                    // gbp_lin_capi_map.hip: Lin
 int lin_sweep(gbp_lin *h);                          // gbp_lin_capi.hip: one synchronous iteration at the weights as they stand, queued on the stream
 }
 
+// n elements of device memory (at least one), owned by the handle: gbp_lin_destroy frees whatever `allocs` still lists
 template <typename T>
-static int lin_upload(gbp_lin *h, T **out, const std::vector<T> &v)
+static int lin_alloc(gbp_lin *h, T **out, size_t n)
 {
     void *q = nullptr;
-    LHIPCHK(hipMalloc(&q, std::max<size_t>(v.size(), 1) * sizeof(T)));
+    LHIPCHK(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
     h->allocs.push_back(q);
-    if (!v.empty()) LHIPCHK(hipMemcpyAsync(q, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, h->stream));
-    LHIPCHK(hipStreamSynchronize(h->stream));            // `v` may be a temporary of the caller
     *out = static_cast<T *>(q);
     return GBP_OK;
+}
+
+// gives one of the handle's arrays back before the handle goes; nullptr is nothing to free
+inline void lin_free(gbp_lin *h, const void *q)
+{
+    if (!q) return;
+    auto at = std::find(h->allocs.begin(), h->allocs.end(), q);
+    if (at != h->allocs.end()) h->allocs.erase(at);
+    (void)hipFree(const_cast<void *>(q));
 }
 
 template <typename K>
