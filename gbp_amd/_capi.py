@@ -170,6 +170,8 @@ SIGNATURES = {
     'gbp_lin_extend': (ct.c_int, [ct.c_void_p, ct.c_void_p]),
     'gbp_lin_get_sizes': (ct.c_int, [ct.c_void_p, _ip, _ip]),
     'gbp_lin_shrink': (ct.c_int, [ct.c_void_p, ct.c_void_p]),
+    'gbp_lin_iterate_until': (ct.c_int, [ct.c_void_p, ct.c_void_p, _dp, ct.c_void_p]),
+    'gbp_lin_get_alloc_count': (ct.c_int, [ct.c_void_p, _ip]),
     'gbp_ba_get_lmk_order': (ct.c_int, [ct.c_void_p, _ip]),
     'gbp_ba_fused_max_cams': (ct.c_int, []),
     'gbp_ba_plan_info': (ct.c_int, [ct.c_void_p, _ip, ct.c_int32]),
@@ -215,6 +217,19 @@ class LinMargInfo(ct.Structure):
     _fields_ = [('iters', ct.c_int32), ('converged', ct.c_int32), ('batches', ct.c_int32), ('reserved', ct.c_int32), ('rel_residual', ct.c_double)]
 
 
+class LinUntilOpts(ct.Structure):
+    """gbp_lin_until_opts_t (include/gbp_lin.h)."""
+    _fields_ = [('max_iters', ct.c_int32), ('check_every', ct.c_int32), ('robustify', ct.c_int32), ('want', ct.c_int32),
+                ('tol_step', ct.c_double), ('tol_map', ct.c_double)]
+
+
+class LinUntilInfo(ct.Structure):
+    """gbp_lin_until_info_t (include/gbp_lin.h)."""
+    _fields_ = [('iters', ct.c_int32), ('converged', ct.c_int32), ('reason', ct.c_int32), ('reserved', ct.c_int32)]
+
+
+LIN_TRACE_ENERGY, LIN_TRACE_MAP = 1, 2              # GBP_LIN_TRACE_* (include/gbp_lin.h)
+LIN_STOP_NONE, LIN_STOP_STEP, LIN_STOP_MAP = 0, 1, 2   # GBP_LIN_STOP_*
 LIN_MARG_COLS = 8
 LIN_LOSS = {None: 0, 'huber': 1, 'constant': 2}     # GBP_LIN_LOSS_* (include/gbp_lin.h)
 

@@ -86,6 +86,10 @@ inline void lin_drop_solvers(gbp_lin *h)
         m.x = m.r = m.z = m.p = m.q = m.ebuf = m.pq_part = m.rz_part = m.rr_part = nullptr;
         h->marg_ready = false;
     }
+    // gbp_lin_iterate_until's partials are one per block of the belief and energy stages; its stop word and trace buffer stay
+    lin_free(h, h->until.bel_part); lin_free(h, h->until.en_part);
+    h->until.bel_part = h->until.en_part = nullptr;
+    h->until.nbel = h->until.nen = 0;
 }
 
 // The swap, after the synchronisation that ends the build of `g`: nothing here can fail.  The arrays that are replaced are freed and

@@ -7,6 +7,8 @@
 //   gbp_lin_capi_robust.hip  robust losses: one weight per factor from the current belief means (kernels in gbp_lin_robust.hpp)
 //   gbp_lin_capi_extend.hip  growing a live graph: the layout rebuilt on the device (kernels in gbp_lin_extend.hpp)
 //   gbp_lin_capi_shrink.hip  shrinking a live graph: retired variables folded into priors (kernels in gbp_lin_shrink.hpp)
+//   gbp_lin_capi_until.hip   sweeps until a tolerance is met, decided on the device, with a per-sweep trace (kernels in gbp_lin_until.hpp;
+//                            the factor stage both sweeps share is gbp_lin_sweep.hpp)
 #pragma once
 #include "../../include/gbp_ba.h"
 #include "../../include/gbp_lin.h"
@@ -69,6 +71,17 @@ struct LinMarg {
     size_t stage_bytes;
 };
 
+// Workspace of gbp_lin_iterate_until (gbp_lin_until.hpp): device memory owned by gbp_lin::allocs, allocated by the first call.  The
+// partials are sized by N and F and go with a generation (lin_drop_solvers); the stop word and the trace buffer stay.
+struct LinUntil {
+    double *bel_part;                // [2][nbel] per block of the traced belief stage: max |mu_new - mu_old|, then sum (mu - x)^2
+    double *en_part;                 // [nen] per block of the energy pass
+    int nbel, nen;
+    double *trace;                   // [cap][3]: row i = (step, energy, MAP distance) after sweep i + 1 of the call in progress
+    int cap;                         // rows of `trace`: the largest max_iters seen
+    int *stop;                       // [2]: GBP_LIN_STOP_* (0: go on), and the sweep that decided
+};
+
 }  // namespace gbp
 
 using namespace gbp;
@@ -90,6 +103,7 @@ struct gbp_lin {
     bool marg_ready = false;
     LinRobust rob{};                 // gbp_lin_capi_robust.hip
     bool rob_alloc = false;          // rob's arrays exist; losses are set while p.w != nullptr
+    LinUntil until{};                // gbp_lin_capi_until.hip
 };
 
 #define LHIPCHK(expr)                                                                                       \

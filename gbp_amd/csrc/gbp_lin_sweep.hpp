@@ -1,0 +1,158 @@
+// gbp_lin_sweep.hpp -- the factor stage of a sweep of the linear engine (k_lin_factor<D, ROBUST> and its Schur step), in a header so
+// that two translation units can instantiate it: gbp_lin_capi.hip launches the plain forms (PT = LinParams), gbp_lin_capi_until.hip the
+// gated ones (PT = LinGated), which return at their head once gbp_lin_iterate_until's stop word is set.  For PT = LinParams
+// lin_stopped() is the constant false and the gate compiles away.
+#pragma once
+#include "gbp_lin_handle.hpp"
+#include "gbp_math.hpp"
+
+#include <hip/hip_runtime.h>
+
+namespace gbp {
+
+// the kernel parameters of a sweep queued by gbp_lin_iterate_until: stop[0] != 0 once an earlier sweep of the call met a tolerance
+struct LinGated : LinParams {
+    const int *stop;
+};
+GBP_DEV bool lin_stopped(const LinParams &) { return false; }
+GBP_DEV bool lin_stopped(const LinGated &p) { return p.stop[0] != 0; }
+
+// Message to the KEPT variable from  [ A_kk  A_kn ; A_nk  A_nn ] , with the eliminated block S = A_nn + cavity already
+// formed (consumed):  Lambda = A_kk - A_kn S^-1 A_nk,  eta = e_k - A_kn S^-1 e_n   (gbp.py:353-367).
+// akn(i, j) = A[k_i][n_j] is supplied by the caller as a dense D x D array.
+template <int D>
+GBP_DEV void lin_schur(const double (&akk)[Sym<D>::size], const double (&akn)[D][D], double (&S)[Sym<D>::size],
+                       const double (&ek)[D], double (&en)[D], double (&lam)[Sym<D>::size], double (&eta)[D])
+{
+    double invd[D];
+    ldl_factor<D>(S, invd);
+    ldl_forward<D>(S, en);                            // L^-1 e_n
+    double y[D][D];                                   // y[i] = L^-1 (A_nk column i) = L^-1 akn[i][:]
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+#pragma unroll
+        for (int j = 0; j < D; ++j) y[i][j] = akn[i][j];
+        ldl_forward<D>(S, y[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+        double e = ek[i];
+#pragma unroll
+        for (int k = 0; k < D; ++k) e -= y[i][k] * invd[k] * en[k];
+        eta[i] = e;
+#pragma unroll
+        for (int j = i; j < D; ++j) {
+            double v = akk[Sym<D>::at(i, j)];
+#pragma unroll
+            for (int k = 0; k < D; ++k) v -= y[i][k] * invd[k] * y[j][k];
+            lam[Sym<D>::at(i, j)] = v;
+        }
+    }
+}
+
+// ROBUST: the factor is the stored nominal one times its weight p.w[f] (gbp_lin_robust.hpp; gbp.py:331-332), applied on load.  A handle
+// without losses launches only the `false` instantiation, which reads no weight.
+template <int D, bool ROBUST, typename PT = LinParams>
+__global__ __launch_bounds__(64) void k_lin_factor(PT p)
+{
+    if (lin_stopped(p)) return;                             // PT = LinParams: never
+    constexpr int P = LinDims<D>::P, REC = LinDims<D>::REC, R = D + P;
+    __shared__ double tr[64 * R];                           // transposes a wave's messages for the variable-major copy
+    __shared__ int tp[64];
+    const int lane = threadIdx.x;
+    const int nlive = min(64, p.F - (int)blockIdx.x * 64);  // factors of this wave (> 0 by the launch grid)
+    const int f = blockIdx.x * 64 + min(lane, nlive - 1);   // lanes past the end redo the last factor and store nothing
+    const bool live = lane < nlive;
+    const size_t F = (size_t)p.F;
+    // the belief stage reads messages in CSR edge order: stage this wave's 64 records in LDS and write them out as
+    // contiguous (D+P)-double runs, 64/(D+P) records per store instruction (a lane-per-record store would touch 64 lines)
+    auto stage_out = [&](const double (&eta)[D], const double (&lam)[P], const int *epos) {
+#pragma unroll
+        for (int k = 0; k < D; ++k) tr[lane * R + k] = eta[k];
+#pragma unroll
+        for (int k = 0; k < P; ++k) tr[lane * R + D + k] = lam[k];
+        tp[lane] = epos[f];
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // one wave per block
+        constexpr int G = 64 / R;
+        const int g = lane / R, k = lane - g * R;
+        if (g < G) {
+            if (nlive == 64) {                              // full wave: fixed trip count, LDS reads batched ahead of the stores
+#pragma unroll
+                for (int j0 = 0; j0 < 64; j0 += G) {
+                    const int j = j0 + g;
+                    if (j < 64) p.vmsg[(size_t)tp[j] * R + k] = tr[j * R + k];
+                }
+            } else {
+                for (int j = g; j < nlive; j += G) p.vmsg[(size_t)tp[j] * R + k] = tr[j * R + k];
+            }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    };
+    const double *ra = p.bel + (size_t)p.va[f] * REC, *rb = p.bel + (size_t)p.vb[f] * REC;
+    // cavities: belief minus this factor's old message (gbp.py:341-350)
+    double cea[D], cla[P], ceb[D], clb[P], oea[D], oeb[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) { oea[k] = p.msg_a[k * F + f]; oeb[k] = p.msg_b[k * F + f]; cea[k] = ra[k] - oea[k]; ceb[k] = rb[k] - oeb[k]; }
+#pragma unroll
+    for (int k = 0; k < P; ++k) { cla[k] = ra[D + k] - p.msg_a[(D + k) * F + f]; clb[k] = rb[D + k] - p.msg_b[(D + k) * F + f]; }
+    // the factor: packed upper 2D x 2D = [ A_aa A_ab ; . A_bb ]
+    double aaa[P], abb[P], aab[D][D], aba[D][D], fa[D], fb[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) { fa[k] = p.feta[k * F + f]; fb[k] = p.feta[(D + k) * F + f]; }
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+#pragma unroll
+        for (int j = i; j < D; ++j) {
+            aaa[Sym<D>::at(i, j)] = p.flam[(size_t)Sym<2 * D>::at(i, j) * F + f];
+            abb[Sym<D>::at(i, j)] = p.flam[(size_t)Sym<2 * D>::at(D + i, D + j) * F + f];
+        }
+#pragma unroll
+        for (int j = 0; j < D; ++j) { const double v = p.flam[(size_t)Sym<2 * D>::at(i, D + j) * F + f]; aab[i][j] = v; aba[j][i] = v; }
+    }
+    if constexpr (ROBUST) {
+        const double w = p.w[f];
+#pragma unroll
+        for (int k = 0; k < D; ++k) { fa[k] *= w; fb[k] *= w; }
+#pragma unroll
+        for (int k = 0; k < P; ++k) { aaa[k] *= w; abb[k] *= w; }
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int j = 0; j < D; ++j) { aab[i][j] *= w; aba[j][i] = aab[i][j]; }
+    }
+    const double d = p.damping;
+    double lam[P], eta[D], S[P], en[D];
+    // to a: eliminate b
+#pragma unroll
+    for (int k = 0; k < P; ++k) S[k] = abb[k] + clb[k];
+#pragma unroll
+    for (int k = 0; k < D; ++k) en[k] = fb[k] + ceb[k];
+    lin_schur<D>(aaa, aab, S, fa, en, lam, eta);
+#pragma unroll
+    for (int k = 0; k < D; ++k) eta[k] = (1.0 - d) * eta[k] + d * oea[k];                   // gbp.py:368
+    if (live) {
+#pragma unroll
+        for (int k = 0; k < D; ++k) p.msg_a[k * F + f] = eta[k];
+#pragma unroll
+        for (int k = 0; k < P; ++k) p.msg_a[(D + k) * F + f] = lam[k];
+    }
+    stage_out(eta, lam, p.epos_a);
+    // to b: eliminate a (from the OLD message of b: both are committed together, gbp.py:371-373 -- cea / cla were
+    // formed before the store above)
+#pragma unroll
+    for (int k = 0; k < P; ++k) S[k] = aaa[k] + cla[k];
+#pragma unroll
+    for (int k = 0; k < D; ++k) en[k] = fa[k] + cea[k];
+    lin_schur<D>(abb, aba, S, fb, en, lam, eta);
+#pragma unroll
+    for (int k = 0; k < D; ++k) eta[k] = (1.0 - d) * eta[k] + d * oeb[k];
+    if (live) {
+#pragma unroll
+        for (int k = 0; k < D; ++k) p.msg_b[k * F + f] = eta[k];
+#pragma unroll
+        for (int k = 0; k < P; ++k) p.msg_b[(D + k) * F + f] = lam[k];
+    }
+    stage_out(eta, lam, p.epos_b);
+}
+
+}  // namespace gbp

@@ -35,6 +35,20 @@ def _host_factors(factors, index):
     return va, vb, fe, fl, fc, loss, thr, nvar
 
 
+class UntilResult:
+    """What LinearEngine.iterate_until returns: iters (the deciding sweep, or max_iters), converged, reason (GBP_LIN_STOP_*:
+    _capi.LIN_STOP_STEP, LIN_STOP_MAP, or LIN_STOP_NONE when max_iters ran out), and one value per sweep run: step, energy,
+    map_distance (the last two None when not asked for)."""
+    __slots__ = ('iters', 'converged', 'reason', 'step', 'energy', 'map_distance')
+
+    def __init__(self, iters, converged, reason, step, energy, map_distance):
+        self.iters, self.converged, self.reason = iters, converged, reason
+        self.step, self.energy, self.map_distance = step, energy, map_distance
+
+    def __repr__(self):
+        return f"UntilResult(iters={self.iters}, converged={self.converged}, reason={self.reason})"
+
+
 class LinearEngine:
     def __init__(self, var_a, var_b, factor_eta, factor_lam, prior_eta, prior_lam, factor_const=None, eta_damping=0.0, device=0):
         self._lib = _capi.load()
@@ -198,6 +212,27 @@ class LinearEngine:
     def iterate(self, n, robustify=False):
         """n sweeps; robustify=True: every sweep re-makes the weights first (synchronous_iteration(robustify=True) gbp.py:86-92)."""
         check((self._lib.gbp_lin_iterate_robust if robustify else self._lib.gbp_lin_iterate)(self._h, int(n)))
+
+    def iterate_until(self, max_iters, tol_step=0.0, tol_map=0.0, energy=False, map_distance=False, robustify=False, check_every=8):
+        """Up to max_iters sweeps in one call, the loop of ndim_posegraph.py:104-108 with the decision to stop taken on the device:
+        stop after the first sweep whose step max |mu_new - mu_old| <= tol_step, or whose distance from the last solve_map() <=
+        tol_map (0: off; tol_map needs map_distance=True).  energy / map_distance add what energy() / map_distance() would return
+        after every sweep.  The state afterwards is bit for bit that of iterate(result.iters, robustify), whatever check_every (how
+        often the host looks at the device's stop word) is.  Returns an UntilResult."""
+        want = (_capi.LIN_TRACE_ENERGY if energy else 0) | (_capi.LIN_TRACE_MAP if map_distance else 0)
+        o = _capi.LinUntilOpts(int(max_iters), int(check_every), int(bool(robustify)), want, float(tol_step), float(tol_map))
+        i = _capi.LinUntilInfo()
+        trace = np.full((max(int(max_iters), 1), 3), np.nan)
+        check(self._lib.gbp_lin_iterate_until(self._h, ct.byref(o), dptr(trace), ct.byref(i)))
+        rows = trace[:i.iters]
+        return UntilResult(i.iters, bool(i.converged), i.reason, rows[:, 0].copy(),
+                           rows[:, 1].copy() if energy else None, rows[:, 2].copy() if map_distance else None)
+
+    def alloc_count(self):
+        """The number of device allocations the handle owns (graph arrays and workspaces)."""
+        n = ct.c_int32()
+        check(self._lib.gbp_lin_get_alloc_count(self._h, ct.byref(n)))
+        return n.value
 
     # robust losses (Factor(loss=, mahalanobis_threshold=), Factor.robustify_loss gbp.py:296-332): one weight per factor
     def set_robust(self, loss, threshold=2.0, noise_var=None):

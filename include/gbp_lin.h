@@ -15,7 +15,8 @@
  * ndim_posegraph.py:86-88 produces.
  *
  * Beside the sweep: the batch MAP (the `mu` of FactorGraph.joint_distribution_cov) and exact marginal covariances (its `sigma`, for
- * chosen variables), both by block-Jacobi conjugate gradients on the block-sparse joint -- below.
+ * chosen variables), both by block-Jacobi conjugate gradients on the block-sparse joint; robust losses; growing and shrinking a live
+ * graph; and sweeps to convergence with the stop decided on the device (gbp_lin_iterate_until) -- below.
  */
 #ifndef GBP_LIN_H
 #define GBP_LIN_H
@@ -207,6 +208,55 @@ typedef struct {
     int32_t *var_map, *factor_map;                        /* out, host, N / F of BEFORE the call: new id or -1; either may be NULL */
 } gbp_lin_shrink_desc_t;
 int  gbp_lin_shrink(gbp_lin_t *h, const gbp_lin_shrink_desc_t *d);
+
+/* ---- iterating to convergence on the device: the loop of ndim_posegraph.py:104-108,
+ *        for i in range(n): graph.synchronous_iteration(); print(graph.energy(), norm(graph.get_means() - mu))
+ * (synchronous_iteration gbp.py:86-92, energy gbp.py:36-44, get_means gbp.py:146-153) in ONE call, without a host round trip per sweep ----
+ * Up to max_iters sweeps of gbp_lin_iterate (robustify 0) or gbp_lin_iterate_robust (robustify 1) are queued; after each one the device
+ * forms a trace row and decides whether to stop.  Row i (0-based, written for i < iters only) describes the state after sweep i + 1:
+ *   column 0  step      max over variables v and coordinates k of |mu_new[v][k] - mu_old[v][k]|, mu_old the belief mean the sweep
+ *                       overwrote.  Always computed, inside the belief stage (no second pass over the beliefs).  A maximum does not depend
+ *                       on the order it is taken in: bit-equal to the same expression over two gbp_lin_get_means downloads.
+ *   column 1  energy    what gbp_lin_energy would return after this sweep: the same per-factor terms (times w_f where losses are set),
+ *                       added in a fixed order on the device.  NaN unless GBP_LIN_TRACE_ENERGY is in `want`.
+ *   column 2  distance  what gbp_lin_map_distance would return after this sweep: |means - x|_2 against the iterate of the last
+ *                       gbp_lin_solve_map -- after robust sweeps still the distance from that solve, whatever the weights have become.
+ *                       NaN unless GBP_LIN_TRACE_MAP is in `want`.
+ * The stop rule: after the first sweep whose step <= tol_step (tol_step > 0), reason STEP; else after the first sweep whose distance <=
+ * tol_map (tol_map > 0), reason MAP; STEP is tested first when one sweep meets both.  The device sets a stop word in its memory, and every
+ * kernel of a later sweep already queued reads it at its head and returns.  The host reads the word only every check_every sweeps and
+ * after the last one, so
+ *   - info->iters is the deciding sweep, not a multiple of check_every;
+ *   - the handle's state after the call is bit for bit the state after gbp_lin_iterate(h, iters) (or gbp_lin_iterate_robust): both
+ *     messages, beliefs, means, weights and flags, for every check_every;
+ *   - max_iters running out is converged = 0, reason NONE, GBP_OK.
+ * No floating-point atomics: two identical calls on two identical handles give bit-identical traces.
+ * GBP_ESTATE: no beliefs yet; robustify without losses set; GBP_LIN_TRACE_MAP without a solve (also after gbp_lin_extend / gbp_lin_shrink,
+ * until the next solve).  GBP_EINVAL: opts NULL; max_iters < 0; check_every < 1; robustify not 0 or 1; unknown bits in want; a tolerance
+ * that is negative or not finite; tol_map > 0 without GBP_LIN_TRACE_MAP.  A refused call changes nothing.  max_iters == 0: GBP_OK, iters 0,
+ * converged 0, nothing written.  Without factors the energy is 0 and the step exactly 0 from the first sweep (tol_step > 0 converges at
+ * sweep 1); without variables the step is 0.  With robustify the call marks the solver's LDL^T and joint eta stale, as gbp_lin_robustify does.
+ * Workspace: per-block partials (sized by N and F: dropped by gbp_lin_extend / gbp_lin_shrink like the solver workspaces), the stop word,
+ * and a device trace buffer of max_iters rows (24 bytes each) that grows to the largest call seen; allocated on first use, freed with the
+ * handle.  max_iters has no other bound: a value whose trace buffer does not fit is GBP_ENOMEM, the graph's state and the buffers the
+ * handle already held unchanged.  gbp_lin_get_alloc_count: the number of device allocations the handle owns (every array of the graph
+ * and every workspace), for callers and tests that want to see that a repeated call allocates nothing. */
+#define GBP_LIN_TRACE_ENERGY 1   /* column 1: what gbp_lin_energy would return after this sweep              */
+#define GBP_LIN_TRACE_MAP    2   /* column 2: what gbp_lin_map_distance would return after this sweep        */
+#define GBP_LIN_STOP_NONE 0      /* max_iters ran out */
+#define GBP_LIN_STOP_STEP 1
+#define GBP_LIN_STOP_MAP  2
+typedef struct {
+    int32_t max_iters, check_every;  /* >= 0, >= 1                                                          */
+    int32_t robustify;               /* 0: sweeps of gbp_lin_iterate, 1: of gbp_lin_iterate_robust          */
+    int32_t want;                    /* mask of GBP_LIN_TRACE_*                                             */
+    double tol_step;                 /* > 0: stop after the first sweep whose step <= tol_step; 0: off      */
+    double tol_map;                  /* > 0: stop after the first sweep whose MAP distance <= tol_map; 0: off; needs TRACE_MAP */
+} gbp_lin_until_opts_t;
+typedef struct { int32_t iters, converged, reason, reserved; } gbp_lin_until_info_t;
+int  gbp_lin_iterate_until(gbp_lin_t *h, const gbp_lin_until_opts_t *opts,
+                           double *trace /* host, max_iters x 3, or NULL */, gbp_lin_until_info_t *info /* or NULL */);
+int  gbp_lin_get_alloc_count(gbp_lin_t *h, int32_t *count);
 
 #ifdef __cplusplus
 }

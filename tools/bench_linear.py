@@ -31,8 +31,11 @@ ap.add_argument('--extend', action='store_true',
 ap.add_argument('--shrink', action='store_true',
                 help='instead of the run above: on the 200k x 3 ring (k = 5, 1M factors) time one shrink retiring the 1000 lowest-numbered variables (folded) '
                      "against gbp_lin_create of the survivors' graph, alternating, and the sweeps of the shrunk handle against the created one; writes profiles/linear_shrink.json")
+ap.add_argument('--until', action='store_true',
+                help='instead of the run above: on the same two graphs time iterate_until(n) (tolerances off; no column, the energy column, both columns) '
+                     'against iterate(n) on the same handle and against the host loop iterate(1); energy(); map_distance(), alternating; writes profiles/linear_until.json')
 ap.add_argument('--parent-results', default=None,
-                help="--extend: a file of lines 'parent {json}' / 'here {json}', each the JSON line of a plain run of this tool from the parent "
+                help="--extend / --shrink / --until: a file of lines 'parent {json}' / 'here {json}', each the JSON line of a plain run of this tool from the parent "
                      "commit's tree or from this one (run alternating, in the same session); summarised per workload under sweeps_per_s_vs_parent")
 ap.add_argument('--repeats', type=int, default=5, help='--marginals / --robust / --extend: repeats per timing (the median is reported)')
 a = ap.parse_args()
@@ -362,6 +365,88 @@ def shrink_profile():
     print(json.dumps(out))
 
 
+def until_profile():
+    """Host clock around whole calls on ONE handle per graph, each ending in a stream synchronise, after a warm-up of every form (and a
+    solve_map, which the distance column needs); --repeats alternating rounds, medians reported, per sweep.  plain: iterate(steps) +
+    sync.  until: iterate_until(steps) with both tolerances off (so all `steps` sweeps run) and check_every = steps (one read of the stop
+    word), with no column, with the energy column, and with both.  host_loop: iterate(1); energy(); map_distance() from Python, `steps`
+    times, on this same handle and library -- the calls the parent commit offers for the same trace (their device code is unchanged; it
+    has no step column, which would add a get_means download per sweep); it was NOT timed on a build of the parent commit.
+    Counted, beside each ratio: a traced sweep reads the old mean (d doubles per variable) and writes one partial per belief block
+    (1 / VPW doubles per variable, VPW = 64 / (d + P)), and adds one kernel boundary (the finishing kernel) priced at 3.2 us; the energy
+    column adds one pass over the factors (Lambda_f d(2d+1), eta_f 2d, const 1, two means 2d doubles per factor) and one more boundary;
+    the distance column adds the MAP iterate (d doubles per variable) and one more partial."""
+    D, runs, boundary_ms = 3, [], 3.2e-3
+    P = D * (D + 1) // 2
+    for N, k in ((200_000, 5), (1_000_000, 1)):
+        g, fc = ring(N, D, k, np.random.RandomState(0))
+        F = g[0].shape[0]
+        e = LinearEngine(*g, factor_const=fc)
+        e.update_all_beliefs()
+        e.iterate(a.warmup); e.sync()
+        e.solve_map()
+        n = a.steps
+
+        def plain():
+            t = time.perf_counter(); e.iterate(n); e.sync()
+            return 1e3 * (time.perf_counter() - t) / n
+
+        def until(energy, dist):
+            t = time.perf_counter(); r = e.iterate_until(n, energy=energy, map_distance=dist, check_every=n); t = time.perf_counter() - t
+            assert r.iters == n and not r.converged
+            return 1e3 * t / n
+
+        def host_loop():
+            t = time.perf_counter()
+            for _ in range(n):
+                e.iterate(1); e.energy(); e.map_distance()
+            return 1e3 * (time.perf_counter() - t) / n
+        plain(); until(False, False); until(True, True); host_loop()
+        rec = {key: [] for key in ('plain', 'until', 'until_energy', 'until_both', 'host_loop')}
+        for _ in range(a.repeats):                          # alternating
+            rec['plain'].append(plain()); rec['until'].append(until(False, False)); rec['until_energy'].append(until(True, False))
+            rec['until_both'].append(until(True, True)); rec['host_loop'].append(host_loop())
+        med = {key: statistics.median(v) for key, v in rec.items()}
+        spread = {key: (max(v) - min(v)) / med[key] for key, v in rec.items()}
+        per_f = sweep_doubles(D, 1.0 / k, False)
+        vpw = 64 // (D + P)
+        extra_trace = (D + 1.0 / vpw) / k                   # doubles per factor
+        extra_energy = D * (2 * D + 1) + 2 * D + 1 + 2 * D
+        extra_dist = (D + 1.0 / vpw) / k
+        counted = lambda extra, boundaries: (per_f + extra) / per_f + boundaries * boundary_ms / med['plain']
+        runs.append({"vars": N, "dofs": D, "k": k, "factors": F, "ms_per_sweep": med, "spread": spread, "ms_all": rec,
+                     "ratio_until_over_plain": med['until'] / med['plain'], "ratio_counted": counted(extra_trace, 1),
+                     "ratio_until_energy_over_plain": med['until_energy'] / med['plain'], "ratio_energy_counted": counted(extra_trace + extra_energy, 2),
+                     "ratio_until_both_over_plain": med['until_both'] / med['plain'], "ratio_both_counted": counted(extra_trace + extra_energy + extra_dist, 2),
+                     "ratio_host_loop_over_until_both": med['host_loop'] / med['until_both'],
+                     "doubles_per_factor_plain": per_f, "extra_doubles_per_factor": {"trace": extra_trace, "energy": extra_energy, "distance": extra_dist},
+                     "kernel_boundary_ms_assumed": boundary_ms})
+        e.close()
+    vs_parent = None
+    if a.parent_results:
+        by = {}
+        for ln in open(a.parent_results):
+            who, js = ln.split(' ', 1)
+            r = json.loads(js)
+            by.setdefault(r['config']['workload'], {'parent': [], 'here': []})[who].append(r['value'])
+        vs_parent = [{"workload": w, "parent": v['parent'], "here": v['here'], "median_parent": statistics.median(v['parent']),
+                      "median_here": statistics.median(v['here']),
+                      "spread_parent": (max(v['parent']) - min(v['parent'])) / statistics.median(v['parent']),
+                      "spread_here": (max(v['here']) - min(v['here'])) / statistics.median(v['here'])} for w, v in by.items()]
+    out = {"what": "tools/bench_linear.py --until on one MI355X: ms per sweep of gbp_lin_iterate_until (tolerances off) against gbp_lin_iterate on the same "
+                   "handle and against the host loop it replaces, on the 200k x 3 ring (k = 5) and the 1M-variable chain (k = 1)",
+           "method": " ".join(until_profile.__doc__.split()), "repeats": a.repeats, "sweep_steps": a.steps, "runs": runs,
+           "sweeps_per_s_vs_parent": vs_parent}
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'profiles', 'linear_until.json')
+    with open(path, 'w') as fh:
+        json.dump(out, fh, indent=1)
+        fh.write('\n')
+    print(json.dumps(out))
+
+
+if a.until:
+    until_profile()
+    sys.exit(0)
 if a.shrink:
     shrink_profile()
     sys.exit(0)
