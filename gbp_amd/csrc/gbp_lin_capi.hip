@@ -1,8 +1,9 @@
 // gbp_lin_capi.hip -- linear pairwise GBP on gfx950 behind include/gbp_lin.h.
 //
 // The reference's generic path (gbp/gbp.py FactorGraph with nonlinear_factors=False, ndim_posegraph.py) for graphs
-// of two-variable factors over d-dimensional variables.  Two kernels per sweep, like the general BA sweep:
-//   k_lin_factor<D>   (gbp_lin_sweep.hpp) one lane per factor: both outgoing messages from the OLD incoming ones
+// of two-variable factors over d-dimensional variables.  Two kernels per sweep, like the general BA sweep, both in gbp_lin_sweep.hpp
+// (one source body per stage; this file launches the plain forms, gbp_lin_capi_until.hip the gated and traced ones):
+//   k_lin_factor<D>   one lane per factor: both outgoing messages from the OLD incoming ones
 //                     (Factor.compute_messages gbp.py:334-373): cavity of the other variable folded into its block,
 //                     that block eliminated by an unpivoted LDL^T (SPD: factor block + prior-backed cavity);
 //   k_lin_belief<D>   64/(d+P) variables per wave, one lane per belief entry: prior + messages in adj_factors order from
@@ -24,65 +25,6 @@
 #include <cstring>
 #include <new>
 #include <vector>
-
-namespace gbp {
-
-// 64/(D+P) variables per wave, one lane per (variable, belief entry): the variable's messages are one contiguous run of
-// vmsg (CSR edge order = adj_factors order), so the wave streams whole lines; the d x d solve is done by the entry-0 lane.
-template <int D>
-__global__ __launch_bounds__(64) void k_lin_belief(LinParams p)
-{
-    constexpr int P = LinDims<D>::P, REC = LinDims<D>::REC, R = D + P, VPW = 64 / R;
-    __shared__ double sh[VPW * R];
-    const int lane = threadIdx.x, j = lane / R, k = lane - j * R;
-    const int v = blockIdx.x * VPW + j;
-    const bool on = j < VPW && v < p.N;
-    if (on) {
-        double acc = p.prior[(size_t)v * R + k];
-        const int e1 = p.vptr[v + 1];
-        int e = p.vptr[v];
-        for (; e + 3 < e1; e += 4) {                              // four loads in flight, added in adj_factors order (gbp.py:182-188)
-            const double m0 = p.vmsg[(size_t)e * R + k], m1 = p.vmsg[(size_t)(e + 1) * R + k], m2 = p.vmsg[(size_t)(e + 2) * R + k],
-                         m3 = p.vmsg[(size_t)(e + 3) * R + k];
-            acc += m0; acc += m1; acc += m2; acc += m3;
-        }
-        for (; e < e1; ++e) acc += p.vmsg[(size_t)e * R + k];
-        p.bel[(size_t)v * REC + k] = acc;
-        sh[j * R + k] = acc;
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // one wave per block
-    if (on && k == 0) {
-        double eta[D], lam[P], mu[D];
-#pragma unroll
-        for (int i = 0; i < D; ++i) eta[i] = sh[j * R + i];
-#pragma unroll
-        for (int i = 0; i < P; ++i) lam[i] = sh[j * R + D + i];
-        spd_solve<D>(lam, eta, mu);                               // gbp.py:192-193
-#pragma unroll
-        for (int i = 0; i < D; ++i) p.bel[(size_t)v * REC + R + i] = mu[i];
-    }
-}
-
-// sum over factors of w_f 0.5 |h(mu) - z|^2 / sigma^2 for linear h (gbp.py:36-44, 251-265; w_f = sigma^2 / adaptive_gauss_noise_var, 1 on a
-// handle without losses): the per-factor term is lin_factor_energy (gbp_lin_robust.hpp), the residual form without cancellation.
-template <int D>
-__global__ __launch_bounds__(256) void k_lin_energy(LinParams p, double *out)
-{
-    __shared__ double red[256 / 64];
-    const int f = blockIdx.x * 256 + threadIdx.x;
-    double e = 0.0;
-    if (f < p.F) {
-        e = lin_factor_energy<D>(p, f);
-        if (p.w) e *= p.w[f];
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) e += __shfl_down(e, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = e;
-    __syncthreads();
-    if (threadIdx.x == 0) out[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-
-}  // namespace gbp
 
 static int lin_beliefs(gbp_lin *h)
 {

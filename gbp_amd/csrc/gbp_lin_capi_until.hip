@@ -1,12 +1,12 @@
 // gbp_lin_capi_until.hip -- gbp_lin_iterate_until of include/gbp_lin.h: the loop of ndim_posegraph.py:104-108 (synchronous_iteration
 // gbp.py:86-92, energy gbp.py:36-44, get_means gbp.py:146-153 against the MAP) in one call, the decision to stop taken on the device
-// (kernels and method: gbp_lin_until.hpp).
+// (method: gbp_lin_until.hpp; the stages are the kernels of gbp_lin_sweep.hpp and gbp_lin_robust.hpp in their gated and traced forms).
 //
 // The pattern is gbp_lin_solve_map's: sweeps are queued check_every at a time on the handle's stream, each followed by a one-block
 // finishing kernel that writes a trace row and, when a tolerance is met, a stop word in device memory; the host reads that word (8
 // bytes) only after each batch.  What was queued behind the deciding sweep returns at its head, so the state the call leaves is that of
 // gbp_lin_iterate(h, iters), whatever check_every was.  The rows are copied out once, at the end, and only the `iters` that were written.
-#include "gbp_lin_until.hpp"
+#include "gbp_lin_sweep.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -47,19 +47,17 @@ int until_workspace(gbp_lin *h, int max_iters)
 int until_sweep(gbp_lin *h, const gbp_lin_until_opts_t &o, const UntilRule &rule, int it)
 {
     const LinUntil &u = h->until;
-    LinGated g;
-    static_cast<LinParams &>(g) = h->p;
-    g.stop = u.stop;
-    const double *x = (o.want & GBP_LIN_TRACE_MAP) ? h->map.x : nullptr;
+    const LinGated g{h->p, u.stop};
+    const LinTraced t{h->p, u, (o.want & GBP_LIN_TRACE_MAP) ? h->map.x : nullptr};
     lin_dispatch(h->D, [&](auto d) {
         constexpr int DD = decltype(d)::value;
         if (h->p.F) {
-            if (o.robustify) hipLaunchKernelGGL((k_until_robustify<DD>), dim3((h->p.F + 255) / 256), dim3(256), 0, h->stream, h->p, h->rob, (const int *)u.stop);
+            if (o.robustify) hipLaunchKernelGGL((k_lin_robustify<DD, LinGated>), dim3((h->p.F + 255) / 256), dim3(256), 0, h->stream, g, h->rob);
             if (h->p.w) hipLaunchKernelGGL((k_lin_factor<DD, true, LinGated>), dim3((h->p.F + 63) / 64), dim3(64), 0, h->stream, g);
             else hipLaunchKernelGGL((k_lin_factor<DD, false, LinGated>), dim3((h->p.F + 63) / 64), dim3(64), 0, h->stream, g);
         }
-        if (h->p.N) hipLaunchKernelGGL((k_lin_belief_traced<DD>), dim3(u.nbel), dim3(64), 0, h->stream, h->p, u, x);
-        if (h->p.F && (o.want & GBP_LIN_TRACE_ENERGY)) hipLaunchKernelGGL((k_until_energy<DD>), dim3(u.nen), dim3(256), 0, h->stream, h->p, u);
+        if (h->p.N) hipLaunchKernelGGL((k_lin_belief<DD, LinTraced>), dim3(u.nbel), dim3(64), 0, h->stream, t);
+        if (h->p.F && (o.want & GBP_LIN_TRACE_ENERGY)) hipLaunchKernelGGL((k_lin_energy<DD, LinGated>), dim3(u.nen), dim3(256), 0, h->stream, g, u.en_part);
     });
     hipLaunchKernelGGL((k_until_finish<UNTIL_FIN>), dim3(1), dim3(UNTIL_FIN), 0, h->stream, u, rule, it);
     LHIPCHK(hipGetLastError());

@@ -1,17 +1,19 @@
 // gbp_lin_handle.hpp -- what the translation units of the linear engine (include/gbp_lin.h) share: the kernel parameter block, the
 // handle behind gbp_lin_t, the error / entry macros and the host helpers every entry point uses (the handle's one allocator among them).
 // What create, extend and shrink share on the host -- a generation of the graph's arrays and its commit -- is gbp_lin_generation.hpp.
-//   gbp_lin_capi.hip       create / destroy, the sweep (k_lin_factor, k_lin_belief), energy, getters
+//   gbp_lin_capi.hip       create / destroy, the plain sweep and energy (launches; the stage kernels are gbp_lin_sweep.hpp), getters
 //   gbp_lin_capi_map.hip   the batch MAP by block-Jacobi conjugate gradients (kernels in gbp_lin_map.hpp)
 //   gbp_lin_capi_marg.hip  exact marginal covariances by the same iteration on 8 columns at a time (kernels in gbp_lin_marg.hpp)
 //   gbp_lin_capi_robust.hip  robust losses: one weight per factor from the current belief means (kernels in gbp_lin_robust.hpp)
 //   gbp_lin_capi_extend.hip  growing a live graph: the layout rebuilt on the device (kernels in gbp_lin_extend.hpp)
 //   gbp_lin_capi_shrink.hip  shrinking a live graph: retired variables folded into priors (kernels in gbp_lin_shrink.hpp)
-//   gbp_lin_capi_until.hip   sweeps until a tolerance is met, decided on the device, with a per-sweep trace (kernels in gbp_lin_until.hpp;
-//                            the factor stage both sweeps share is gbp_lin_sweep.hpp)
+//   gbp_lin_capi_until.hip   sweeps until a tolerance is met, decided on the device, with a per-sweep trace: the gated and traced forms of
+//                            the same stage kernels (parameter blocks LinGated / LinTraced below), and what is the call's alone
+//                            (gbp_lin_until.hpp)
 #pragma once
 #include "../../include/gbp_ba.h"
 #include "../../include/gbp_lin.h"
+#include "gbp_math.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -81,6 +83,21 @@ struct LinUntil {
     int cap;                         // rows of `trace`: the largest max_iters seen
     int *stop;                       // [2]: GBP_LIN_STOP_* (0: go on), and the sweep that decided
 };
+
+// The parameter block selects the form of a stage kernel (gbp_lin_sweep.hpp, gbp_lin_robust.hpp).  LinParams: the plain form;
+// lin_stopped() is the constant false and the gate compiles away.  LinGated: a sweep queued by gbp_lin_iterate_until, which returns at
+// its head once stop[0] != 0 (an earlier sweep of the call met a tolerance).  LinTraced: the belief stage of such a sweep, gated and with
+// the trace of its block; x: the MAP iterate [N][D], or nullptr when the distance is not asked for.
+struct LinGated : LinParams {
+    const int *stop;
+};
+struct LinTraced : LinParams {
+    LinUntil u;
+    const double *x;
+};
+GBP_DEV bool lin_stopped(const LinParams &) { return false; }
+GBP_DEV bool lin_stopped(const LinGated &p) { return p.stop[0] != 0; }
+GBP_DEV bool lin_stopped(const LinTraced &p) { return p.u.stop[0] != 0; }
 
 }  // namespace gbp
 

@@ -14,7 +14,8 @@
 // before each robustify.
 //   lin_factor_energy<D>  the per-factor energy e_f in the cancellation-free residual form (a pivoted LDL^T of Lambda_f), shared by
 //                         k_lin_energy, k_lin_robustify and the host shim (tests/hostmath/lin_robust_shim.hip);
-//   k_lin_robustify<D>    one lane per factor: M^2 = 2 e_f, then w_f and the flag, plain vector stores.
+//   k_lin_robustify<D, PT>  one lane per factor: M^2 = 2 e_f, then w_f and the flag, plain vector stores; PT = LinGated
+//                         (gbp_lin_handle.hpp): gated on the stop word of gbp_lin_iterate_until.
 #pragma once
 #include "gbp_lin_handle.hpp"
 #include "gbp_math.hpp"
@@ -105,9 +106,10 @@ GBP_HD void lin_robustify_one(const LinParams &p, const LinRobust &r, int f)
     r.flag[f] = flag;
 }
 
-template <int D>
-__global__ __launch_bounds__(256) void k_lin_robustify(LinParams p, LinRobust r)
+template <int D, typename PT = LinParams>
+__global__ __launch_bounds__(256) void k_lin_robustify(PT p, LinRobust r)
 {
+    if (lin_stopped(p)) return;                           // PT = LinParams: never
     const int f = blockIdx.x * 256 + threadIdx.x;
     if (f < p.F) lin_robustify_one<D>(p, r, f);
 }

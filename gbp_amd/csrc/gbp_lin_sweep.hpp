@@ -1,21 +1,18 @@
-// gbp_lin_sweep.hpp -- the factor stage of a sweep of the linear engine (k_lin_factor<D, ROBUST> and its Schur step), in a header so
-// that two translation units can instantiate it: gbp_lin_capi.hip launches the plain forms (PT = LinParams), gbp_lin_capi_until.hip the
-// gated ones (PT = LinGated), which return at their head once gbp_lin_iterate_until's stop word is set.  For PT = LinParams
-// lin_stopped() is the constant false and the gate compiles away.
+// gbp_lin_sweep.hpp -- the stages of a sweep of the linear engine, one source body each (the robustify stage is gbp_lin_robust.hpp):
+//   k_lin_factor<D, ROBUST, PT>   one lane per factor: both outgoing messages from the OLD incoming ones, with its Schur step;
+//   k_lin_belief<D, PT>           64/(d+P) variables per wave: prior + messages in adj_factors order, mean by a d x d solve;
+//   k_lin_energy<D, PT>           the energy of the graph at the belief means, one partial per block.
+// The parameter block PT (gbp_lin_handle.hpp) selects the form, and two translation units instantiate them: gbp_lin_capi.hip launches the
+// plain forms (PT = LinParams), gbp_lin_capi_until.hip the gated ones (PT = LinGated; for the belief stage LinTraced, gated and traced),
+// which return at their head once gbp_lin_iterate_until's stop word is set.  For PT = LinParams lin_stopped() is the constant false and
+// the gate -- and with `if constexpr` the trace -- compiles away.
 #pragma once
-#include "gbp_lin_handle.hpp"
-#include "gbp_math.hpp"
+#include "gbp_lin_robust.hpp"
+#include "gbp_lin_until.hpp"
 
 #include <hip/hip_runtime.h>
 
 namespace gbp {
-
-// the kernel parameters of a sweep queued by gbp_lin_iterate_until: stop[0] != 0 once an earlier sweep of the call met a tolerance
-struct LinGated : LinParams {
-    const int *stop;
-};
-GBP_DEV bool lin_stopped(const LinParams &) { return false; }
-GBP_DEV bool lin_stopped(const LinGated &p) { return p.stop[0] != 0; }
 
 // Message to the KEPT variable from  [ A_kk  A_kn ; A_nk  A_nn ] , with the eliminated block S = A_nn + cavity already
 // formed (consumed):  Lambda = A_kk - A_kn S^-1 A_nk,  eta = e_k - A_kn S^-1 e_n   (gbp.py:353-367).
@@ -153,6 +150,84 @@ __global__ __launch_bounds__(64) void k_lin_factor(PT p)
         for (int k = 0; k < P; ++k) p.msg_b[(D + k) * F + f] = lam[k];
     }
     stage_out(eta, lam, p.epos_b);
+}
+
+// 64/(D+P) variables per wave, one lane per (variable, belief entry): the variable's messages are one contiguous run of
+// vmsg (CSR edge order = adj_factors order), so the wave streams whole lines; the d x d solve is done by the entry-0 lane.
+// PT = LinTraced adds the gate and the trace of the block: the entry-0 lane, which holds the new mean in registers, reads the old mean
+// from the record before it writes the new one, and the wave (one per block) reduces step and squared distance to one partial each.
+template <int D, typename PT = LinParams>
+__global__ __launch_bounds__(64) void k_lin_belief(PT p)
+{
+    constexpr bool TRACED = std::is_same<PT, LinTraced>::value;
+    if (lin_stopped(p)) return;                             // PT = LinParams: never
+    constexpr int P = LinDims<D>::P, REC = LinDims<D>::REC, R = D + P, VPW = 64 / R;
+    __shared__ double sh[VPW * R];
+    const int lane = threadIdx.x, j = lane / R, k = lane - j * R;
+    const int v = blockIdx.x * VPW + j;
+    const bool on = j < VPW && v < p.N;
+    if (on) {
+        double acc = p.prior[(size_t)v * R + k];
+        const int e1 = p.vptr[v + 1];
+        int e = p.vptr[v];
+        for (; e + 3 < e1; e += 4) {                              // four loads in flight, added in adj_factors order (gbp.py:182-188)
+            const double m0 = p.vmsg[(size_t)e * R + k], m1 = p.vmsg[(size_t)(e + 1) * R + k], m2 = p.vmsg[(size_t)(e + 2) * R + k],
+                         m3 = p.vmsg[(size_t)(e + 3) * R + k];
+            acc += m0; acc += m1; acc += m2; acc += m3;
+        }
+        for (; e < e1; ++e) acc += p.vmsg[(size_t)e * R + k];
+        p.bel[(size_t)v * REC + k] = acc;
+        sh[j * R + k] = acc;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // one wave per block
+    [[maybe_unused]] double step = 0.0, sq = 0.0;
+    if (on && k == 0) {
+        double eta[D], lam[P], mu[D];
+#pragma unroll
+        for (int i = 0; i < D; ++i) eta[i] = sh[j * R + i];
+#pragma unroll
+        for (int i = 0; i < P; ++i) lam[i] = sh[j * R + D + i];
+        spd_solve<D>(lam, eta, mu);                               // gbp.py:192-193
+        // The old mean, before the store.  The step is bit-equal to numpy's only while mu_new - mu_old is a subtraction of the ROUNDED
+        // mean that is stored below: were the last multiply of spd_solve fused into it (-ffp-contract=fast allows an fma), the step
+        // would be that of an unrounded mean.  The twin tests (tests/test_linear_until_gpu.py) compare it bit for bit for d = 1 .. 6.
+        if constexpr (TRACED) until_var<D>(mu, p.bel + (size_t)v * REC + R, p.x ? p.x + (size_t)v * D : nullptr, step, sq);
+#pragma unroll
+        for (int i = 0; i < D; ++i) p.bel[(size_t)v * REC + R + i] = mu[i];
+    }
+    if constexpr (TRACED) {
+        // the wave's partials: every other lane holds 0; lane 0 ends with the lanes combined in a fixed order
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            step = until_max(step, __shfl_down(step, off, 64));
+            sq += __shfl_down(sq, off, 64);
+        }
+        if (lane == 0) {
+            p.u.bel_part[blockIdx.x] = step;
+            if (p.x) p.u.bel_part[(size_t)p.u.nbel + blockIdx.x] = sq;
+        }
+    }
+}
+
+// sum over factors of w_f 0.5 |h(mu) - z|^2 / sigma^2 for linear h (gbp.py:36-44, 251-265; w_f = sigma^2 / adaptive_gauss_noise_var, 1 on a
+// handle without losses): the per-factor term is lin_factor_energy (gbp_lin_robust.hpp), the residual form without cancellation.
+// out: one partial per block -- the handle's for gbp_lin_energy, the call's own for the trace of gbp_lin_iterate_until.
+template <int D, typename PT = LinParams>
+__global__ __launch_bounds__(256) void k_lin_energy(PT p, double *out)
+{
+    if (lin_stopped(p)) return;                             // PT = LinParams: never
+    __shared__ double red[256 / 64];
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    double e = 0.0;
+    if (f < p.F) {
+        e = lin_factor_energy<D>(p, f);
+        if (p.w) e *= p.w[f];
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) e += __shfl_down(e, off, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = e;
+    __syncthreads();
+    if (threadIdx.x == 0) out[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
 }  // namespace gbp

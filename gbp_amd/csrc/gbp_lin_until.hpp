@@ -1,24 +1,20 @@
-// gbp_lin_until.hpp -- gbp_lin_iterate_until on gfx950: the loop of ndim_posegraph.py:104-108 (synchronous_iteration gbp.py:86-92, then
-// energy() gbp.py:36-44 and |get_means() - mu| gbp.py:146-153) with the decision "stop" taken on the device.
+// gbp_lin_until.hpp -- what belongs to gbp_lin_iterate_until alone on gfx950: the loop of ndim_posegraph.py:104-108 (synchronous_iteration
+// gbp.py:86-92, then energy() gbp.py:36-44 and |get_means() - mu| gbp.py:146-153) with the decision "stop" taken on the device.
 //
-// A sweep of the call is the sweep of gbp_lin_iterate (or gbp_lin_iterate_robust) with every kernel GATED -- it reads the call's stop
-// word at its head and returns once it is set, so the sweeps queued behind the deciding one change nothing -- and with the belief
-// stage TRACED, so that no second pass over the beliefs is needed:
-//   k_until_robustify<D>     k_lin_robustify, gated;
-//   k_lin_factor<D, R, LinGated>   the factor stage (gbp_lin_sweep.hpp), gated;
-//   k_lin_belief_traced<D>   k_lin_belief, gated; the entry-0 lane, which holds the new mean in registers, reads the old mean from the
-//                            record before it writes the new one: max_k |mu_new - mu_old| and, when asked, sum_k (mu_new - x)^2 against
-//                            the iterate of the last gbp_lin_solve_map.  The wave (one per block) reduces them to one partial each;
-//   k_until_energy<D>        only when asked: k_lin_energy's pass over the factors with partials of its own, gated;
+// A sweep of the call is the sweep of gbp_lin_iterate (or gbp_lin_iterate_robust): the SAME stage kernels (gbp_lin_sweep.hpp,
+// gbp_lin_robust.hpp), instantiated with the parameter blocks of gbp_lin_handle.hpp that gate them -- each reads the call's stop word at
+// its head and returns once it is set, so the sweeps queued behind the deciding one change nothing -- and, for the belief stage, trace
+// it, so that no second pass over the beliefs is needed.  There is one text of the belief, factor, energy and robustify arithmetic: the
+// state after the deciding sweep s is bit for bit that of gbp_lin_iterate(h, s) by construction.  What is here:
+//   until_var, until_max     what the traced belief stage adds per variable: max_k |mu_new - mu_old| and, when asked, sum_k (mu_new - x)^2
+//                            against the iterate of the last gbp_lin_solve_map;
 //   k_until_finish           one block: max of the step partials, fixed-order sums of the others (strided per thread, then a fixed
 //                            tree), row i of the device trace, and the stop word when an enabled tolerance is met.
-// The sums of the belief and factor arithmetic are those of k_lin_belief and k_lin_factor in the same order: the state after the
-// deciding sweep s is bit for bit that of gbp_lin_iterate(h, s).  A maximum does not depend on the order it is taken in, so the step
-// is exact; the two sums are added in a fixed order.  No floating-point atomics.
+// A maximum does not depend on the order it is taken in, so the step is exact; the two sums are added in a fixed order.  No
+// floating-point atomics.
 // The per-variable and finishing arithmetic are host/device routines (tests/hostmath/lin_until_shim.hip runs them on a CPU).
 #pragma once
-#include "gbp_lin_robust.hpp"
-#include "gbp_lin_sweep.hpp"
+#include "gbp_lin_handle.hpp"
 
 namespace gbp {
 
@@ -100,87 +96,7 @@ GBP_HD int until_row(const UntilRule &r, double step, double sq, double en, doub
     return GBP_LIN_STOP_NONE;
 }
 
-// ---- kernels -----------------------------------------------------------------------------------------------------------------------
-
-template <int D>
-__global__ __launch_bounds__(256) void k_until_robustify(LinParams p, LinRobust r, const int *stop)
-{
-    if (stop[0]) return;
-    const int f = blockIdx.x * 256 + threadIdx.x;
-    if (f < p.F) lin_robustify_one<D>(p, r, f);
-}
-
-// k_lin_belief (gbp_lin_capi.hip) with the same sums in the same order, and the trace of its block.  x: the MAP iterate [N][D], or
-// nullptr when the distance is not asked for.
-template <int D>
-__global__ __launch_bounds__(64) void k_lin_belief_traced(LinParams p, LinUntil u, const double *x)
-{
-    if (u.stop[0]) return;
-    constexpr int P = LinDims<D>::P, REC = LinDims<D>::REC, R = D + P, VPW = 64 / R;
-    __shared__ double sh[VPW * R];
-    const int lane = threadIdx.x, j = lane / R, k = lane - j * R;
-    const int v = blockIdx.x * VPW + j;
-    const bool on = j < VPW && v < p.N;
-    if (on) {
-        double acc = p.prior[(size_t)v * R + k];
-        const int e1 = p.vptr[v + 1];
-        int e = p.vptr[v];
-        for (; e + 3 < e1; e += 4) {                              // four loads in flight, added in adj_factors order (gbp.py:182-188)
-            const double m0 = p.vmsg[(size_t)e * R + k], m1 = p.vmsg[(size_t)(e + 1) * R + k], m2 = p.vmsg[(size_t)(e + 2) * R + k],
-                         m3 = p.vmsg[(size_t)(e + 3) * R + k];
-            acc += m0; acc += m1; acc += m2; acc += m3;
-        }
-        for (; e < e1; ++e) acc += p.vmsg[(size_t)e * R + k];
-        p.bel[(size_t)v * REC + k] = acc;
-        sh[j * R + k] = acc;
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // one wave per block
-    double step = 0.0, sq = 0.0;
-    if (on && k == 0) {
-        double eta[D], lam[P], mu[D];
-#pragma unroll
-        for (int i = 0; i < D; ++i) eta[i] = sh[j * R + i];
-#pragma unroll
-        for (int i = 0; i < P; ++i) lam[i] = sh[j * R + D + i];
-        spd_solve<D>(lam, eta, mu);                               // gbp.py:192-193
-        // The old mean, before the store.  The step is bit-equal to numpy's only while mu_new - mu_old is a subtraction of the ROUNDED
-        // mean that is stored below: were the last multiply of spd_solve fused into it (-ffp-contract=fast allows an fma), the step
-        // would be that of an unrounded mean.  The twin tests (tests/test_linear_until_gpu.py) compare it bit for bit for d = 1, 3, 6;
-        // they also keep this copy of k_lin_belief's sums in step with the original.
-        until_var<D>(mu, p.bel + (size_t)v * REC + R, x ? x + (size_t)v * D : nullptr, step, sq);
-#pragma unroll
-        for (int i = 0; i < D; ++i) p.bel[(size_t)v * REC + R + i] = mu[i];
-    }
-    // the wave's partials: every other lane holds 0; lane 0 ends with the lanes combined in a fixed order
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        step = until_max(step, __shfl_down(step, off, 64));
-        sq += __shfl_down(sq, off, 64);
-    }
-    if (lane == 0) {
-        u.bel_part[blockIdx.x] = step;
-        if (x) u.bel_part[(size_t)u.nbel + blockIdx.x] = sq;
-    }
-}
-
-// k_lin_energy (gbp_lin_capi.hip) into the call's own partials
-template <int D>
-__global__ __launch_bounds__(256) void k_until_energy(LinParams p, LinUntil u)
-{
-    if (u.stop[0]) return;
-    __shared__ double red[256 / 64];
-    const int f = blockIdx.x * 256 + threadIdx.x;
-    double e = 0.0;
-    if (f < p.F) {
-        e = lin_factor_energy<D>(p, f);
-        if (p.w) e *= p.w[f];
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) e += __shfl_down(e, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = e;
-    __syncthreads();
-    if (threadIdx.x == 0) u.en_part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
+// ---- the finishing kernel --------------------------------------------------------------------------------------------------------
 
 // one block after sweep `it` + 1 of the call: row `it` of the trace, and the stop word.  Without variables (factors) there are no
 // partials: the step (the energy) is 0.  T = UNTIL_FIN threads (a template, so that a host-only build of this header has no kernel).

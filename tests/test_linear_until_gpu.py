@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import golden
-from lin_until_cases import FIN_THREADS, MAX_S, STOP_MAP, STOP_NONE, STOP_STEP, TOL, TRACE_ENERGY, TRACE_MAP, graphs, map_of, oracle, run_model, usable_sweep
+from lin_until_cases import FIN_THREADS, MAX_S, STOP_MAP, STOP_NONE, STOP_STEP, TOL, TRACE_ENERGY, TRACE_MAP, displacement, graphs, map_of, oracle, run_model, usable_sweep
 
 pytestmark = pytest.mark.gpu
 
@@ -368,3 +368,44 @@ def test_running_out_of_sweeps_is_not_an_error(name, check_every):
     c.iterate(n)
     assert rc == 0 and (info.iters, info.converged, info.reason) == (n, 0, STOP_NONE)
     assert same(state(a), state(c)) and np.array_equal(trace[:n, 0], rows[:n, 0]) and np.all(trace[n:] == SENTINEL)
+
+
+# ---- 7. every d, and the wave and block edges of the gated and traced stages ----------------------------------------------------------
+
+def stage_cases():
+    """(d, N): for every d, N one short of two whole waves of the belief stage (64 // (d + d(d+1)/2) variables each), exactly two, and
+    one over; and d = 1 with N = 131, whose F = 259 factors cross the 64-factor wave of the factor stage (a tail of 3) and the
+    256-factor block of the energy and robustify stages."""
+    out = []
+    for d in range(1, 7):
+        vpw = 64 // (d + d * (d + 1) // 2)
+        out += [(d, 2 * vpw - 1), (d, 2 * vpw), (d, 2 * vpw + 1)]
+    return out + [(1, 131)]
+
+
+def skip_chain(d, N):
+    """lin_until_cases.displacement on the chain with skips: factors (i, i + 1) and (i, i + 2), three of the measurements outliers."""
+    rs = np.random.RandomState(100 * d + N)
+    return displacement(f'chain_d{d}_n{N}', np.concatenate([np.arange(N - 1), np.arange(N - 2)]), np.concatenate([np.arange(1, N), np.arange(2, N)]),
+                        rs.rand(N, d) * 10, 0.5, 7 * d + N, outliers=3)
+
+
+@pytest.mark.parametrize('robust', [False, True])
+@pytest.mark.parametrize('d,N', stage_cases())
+def test_every_d_at_the_wave_and_block_edges_matches_the_plain_sweeps_on_a_twin(d, N, robust):
+    """The gated and traced forms of every stage against the plain ones, for every d the engine is instantiated for: A makes four
+    sweeps in one call with both extra columns, B four calls of one plain sweep each."""
+    g = skip_chain(d, N)
+    assert len(g['va']) == 2 * N - 3 and N <= 131
+    a, b = engine(g, robust), engine(g, robust)
+    a.solve_map(); b.solve_map()
+    rc, trace, info = raw(a, 4, 8, int(robust), TRACE_ENERGY | TRACE_MAP)
+    rows = host_loop(b, 4, robust)
+    assert rc == 0 and info.iters == 4 and info.reason == STOP_NONE
+    assert same(state(a), state(b))
+    assert np.array_equal(trace[:, 0], rows[:, 0])
+    for i in range(4):
+        assert close(trace[i, 1], rows[i, 1]), f"sweep {i + 1}: energy {trace[i, 1]!r} vs {rows[i, 1]!r}"
+        assert close(trace[i, 2], rows[i, 2]), f"sweep {i + 1}: distance {trace[i, 2]!r} vs {rows[i, 2]!r}"
+    if robust:
+        assert a.weights()[1].any() and np.any(a.weights()[0] != 1.0)      # the outliers did their work: weights other than 1
