@@ -172,6 +172,10 @@ SIGNATURES = {
     'gbp_lin_shrink': (ct.c_int, [ct.c_void_p, ct.c_void_p]),
     'gbp_lin_iterate_until': (ct.c_int, [ct.c_void_p, ct.c_void_p, _dp, ct.c_void_p]),
     'gbp_lin_get_alloc_count': (ct.c_int, [ct.c_void_p, _ip]),
+    'gbp_lin_set_nonlinear': (ct.c_int, [ct.c_void_p, ct.c_void_p]),
+    'gbp_lin_relinearise': (ct.c_int, [ct.c_void_p, _ip]),
+    'gbp_lin_iterate_nonlinear': (ct.c_int, [ct.c_void_p, ct.c_int32, _ip]),
+    'gbp_lin_get_linearisation': (ct.c_int, [ct.c_void_p, _dp, _ip, _dp]),
     'gbp_ba_get_lmk_order': (ct.c_int, [ct.c_void_p, _ip]),
     'gbp_ba_fused_max_cams': (ct.c_int, []),
     'gbp_ba_plan_info': (ct.c_int, [ct.c_void_p, _ip, ct.c_int32]),
@@ -228,6 +232,13 @@ class LinUntilInfo(ct.Structure):
     _fields_ = [('iters', ct.c_int32), ('converged', ct.c_int32), ('reason', ct.c_int32), ('reserved', ct.c_int32)]
 
 
+class LinNonlinear(ct.Structure):
+    """gbp_lin_nonlinear_desc_t (include/gbp_lin.h)."""
+    _fields_ = [('model', ct.c_int32), ('num_undamped_iters', ct.c_int32), ('min_linear_iters', ct.c_int32), ('reserved', ct.c_int32),
+                ('beta', ct.c_double), ('measurement', _dp), ('sqrt_info', _dp)]
+
+
+LIN_MODEL_SE2_BETWEEN = 1                           # GBP_LIN_MODEL_* (include/gbp_lin.h)
 LIN_TRACE_ENERGY, LIN_TRACE_MAP = 1, 2              # GBP_LIN_TRACE_* (include/gbp_lin.h)
 LIN_STOP_NONE, LIN_STOP_STEP, LIN_STOP_MAP = 0, 1, 2   # GBP_LIN_STOP_*
 LIN_MARG_COLS = 8

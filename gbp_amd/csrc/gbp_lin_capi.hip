@@ -171,7 +171,8 @@ int gbp_lin_energy(gbp_lin_t *h, double *out)
     if (!h->has_beliefs) return set_error(GBP_ESTATE, "beliefs have not been computed yet");
     double e = 0.0;
     if (h->p.F) {
-        lin_dispatch(h->D, [&](auto d) {
+        if (h->nonlinear) LCHK(lin_nonlin_energy(h, h->d_red));    // through the nonlinear h at the current means (gbp.py:251-265)
+        else lin_dispatch(h->D, [&](auto d) {
             hipLaunchKernelGGL((k_lin_energy<decltype(d)::value>), dim3(h->red_blocks), dim3(256), 0, h->stream, h->p, h->d_red);
         });
         LHIPCHK(hipGetLastError());

@@ -182,6 +182,7 @@ int gbp_lin_get_sizes(gbp_lin_t *h, int32_t *n_vars, int32_t *n_factors)
 int gbp_lin_extend(gbp_lin_t *h, const gbp_lin_extend_desc_t *d)
 {
     LENTER(h);
+    LIN_REFUSE_NONLINEAR(h, "gbp_lin_extend");
     if (!d) return set_error(GBP_EINVAL, "NULL descriptor");
     LCHK(ext_validate(h, d));
     const int dN = d->n_new_vars, dF = d->n_new_factors;

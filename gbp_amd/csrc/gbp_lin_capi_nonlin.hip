@@ -1,0 +1,159 @@
+// gbp_lin_capi_nonlin.hip -- the nonlinear entry points of include/gbp_lin.h: FactorGraph(nonlinear_factors=True) (gbp.py:30-34),
+// relinearise_factors (gbp.py:64-80), the per-factor damping of compute_all_messages (gbp.py:46-54) and
+// synchronous_iteration(local_relin=True) (gbp.py:86-92) for the SE(2) relative-pose factor (kernels and model: gbp_lin_nonlin.hpp).
+//
+// A nonlinear handle keeps (eta_f, Lambda_f) where a linear one does -- LinParams::feta / flam -- so the plain sweep, the joint behind the
+// batch MAP and the marginals read the factor "at the current linearisation point" (gbp.py:96-97) without knowing.  What is added per
+// factor: measurement and square-root information, the linearisation point, iters_since_relin and the factor's damping.  A sweep is
+// three kernels queued on the handle's stream (k_lin_relin, k_lin_factor<3, false, LinRelin>, k_lin_belief): no host round trip; the
+// only atomics are integer adds of the per-sweep counts.  Every call that may relinearise clears map_ready, as a change of robust
+// weights does.
+#include "gbp_lin_nonlin.hpp"
+#include "gbp_lin_sweep.hpp"
+
+#include <cmath>
+
+using namespace gbp;
+
+namespace {
+
+int nl_check_state(gbp_lin *h)
+{
+    if (!h->nonlinear) return set_error(GBP_ESTATE, "the handle has no nonlinear factors: call gbp_lin_set_nonlinear first");
+    return GBP_OK;
+}
+
+// a counts buffer of at least n slots
+int nl_counts(gbp_lin *h, int n)
+{
+    LinNonlin &nl = h->nl;
+    if (n > nl.cap) {
+        int *c = nullptr;
+        LCHK(lin_alloc(h, &c, (size_t)n));
+        lin_free(h, nl.counts);                             // no call is in flight: every call that counts ends in a synchronisation
+        nl.counts = c;
+        nl.cap = n;
+    }
+    return GBP_OK;
+}
+
+// the relinearise stage (mode: gbp_lin_nonlin.hpp), counted into `count` (nullptr: not counted)
+void nl_relin(gbp_lin *h, int mode, int *count)
+{
+    if (!h->p.F) return;
+    hipLaunchKernelGGL((k_lin_relin<GBP_LIN_MODEL_SE2_BETWEEN>), dim3((h->p.F + 255) / 256), dim3(256), 0, h->stream, h->p, h->nl, mode, count);
+}
+
+}  // namespace
+
+namespace gbp {
+int lin_nonlin_energy(gbp_lin *h, double *out)
+{
+    hipLaunchKernelGGL((k_lin_energy_nl<GBP_LIN_MODEL_SE2_BETWEEN>), dim3((h->p.F + 255) / 256), dim3(256), 0, h->stream, h->p, h->nl, out);
+    return GBP_OK;
+}
+}  // namespace gbp
+
+extern "C" {
+
+int gbp_lin_set_nonlinear(gbp_lin_t *h, const gbp_lin_nonlinear_desc_t *d)
+{
+    LENTER(h);
+    if (!d) return set_error(GBP_EINVAL, "NULL descriptor");
+    const int F = h->p.F;
+    if (d->model != GBP_LIN_MODEL_SE2_BETWEEN) return set_error(GBP_EINVAL, "unknown model %d", d->model);
+    if (h->D != NL_D) return set_error(GBP_EINVAL, "the SE(2) relative-pose factor needs dofs == 3, the handle has %d", h->D);
+    if (d->num_undamped_iters < 0 || d->min_linear_iters < 0) return set_error(GBP_EINVAL, "num_undamped_iters and min_linear_iters must not be negative");
+    if (!(d->beta >= 0.0)) return set_error(GBP_EINVAL, "beta must not be negative (+inf: never relinearise)");
+    if (F && (!d->measurement || !d->sqrt_info)) return set_error(GBP_EINVAL, "NULL array in the descriptor");
+    for (size_t i = 0; i < (size_t)F * NL_M; ++i) {
+        if (!(d->sqrt_info[i] > 0.0) || !std::isfinite(d->sqrt_info[i])) return set_error(GBP_EINVAL, "factor %d: sqrt_info must be positive and finite", (int)(i / NL_M));
+        if (!std::isfinite(d->measurement[i])) return set_error(GBP_EINVAL, "factor %d: the measurement must be finite", (int)(i / NL_M));
+    }
+    if (h->p.w) return set_error(GBP_ESTATE, "losses are set: robust nonlinear factors are not supported");
+    if (h->nonlinear) return set_error(GBP_ESTATE, "the handle already has nonlinear factors");
+
+    std::vector<double> z((size_t)NL_M * F), s((size_t)NL_M * F);     // SoA, stride F
+    for (int f = 0; f < F; ++f)
+        for (int k = 0; k < NL_M; ++k) { z[(size_t)k * F + f] = d->measurement[(size_t)f * NL_M + k]; s[(size_t)k * F + f] = d->sqrt_info[(size_t)f * NL_M + k]; }
+    LinNonlin nl{};
+    double *dz = nullptr, *ds = nullptr;
+    LCHK(lin_alloc(h, &dz, z.size())); LCHK(lin_alloc(h, &ds, s.size()));
+    LCHK(lin_alloc(h, &nl.linpoint, (size_t)2 * NL_D * F)); LCHK(lin_alloc(h, &nl.iters, (size_t)F)); LCHK(lin_alloc(h, &nl.fdamp, (size_t)F));
+    LCHK(lin_alloc(h, &nl.counts, 1));
+    nl.meas = dz; nl.sinfo = ds; nl.cap = 1;
+    nl.feta = const_cast<double *>(h->p.feta); nl.flam = const_cast<double *>(h->p.flam);
+    nl.beta = d->beta; nl.num_undamped = d->num_undamped_iters; nl.min_linear = d->min_linear_iters; nl.model = d->model;
+    if (F) {
+        LHIPCHK(hipMemcpyAsync(dz, z.data(), z.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        LHIPCHK(hipMemcpyAsync(ds, s.data(), s.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    }
+    h->nl = nl;
+    if (!h->has_beliefs) LCHK(gbp_lin_update_beliefs(h));  // belief = prior (+ whatever messages the handle holds)
+    nl_relin(h, NL_INIT, nullptr);                         // compute_all_factors gbp.py:60-62
+    LHIPCHK(hipGetLastError());
+    LHIPCHK(hipStreamSynchronize(h->stream));              // z and s are temporaries
+    h->nonlinear = true;
+    h->map_ready = false;
+    return GBP_OK;
+}
+
+int gbp_lin_relinearise(gbp_lin_t *h, int32_t *n_relinearised)
+{
+    LENTER(h);
+    LCHK(nl_check_state(h));
+    LHIPCHK(hipMemsetAsync(h->nl.counts, 0, sizeof(int), h->stream));
+    nl_relin(h, NL_ALONE, h->nl.counts);
+    LHIPCHK(hipGetLastError());
+    h->map_ready = false;                                   // the joint is that of the new linearisation point
+    if (n_relinearised) {
+        LHIPCHK(hipMemcpyAsync(n_relinearised, h->nl.counts, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        LHIPCHK(hipStreamSynchronize(h->stream));
+    }
+    return GBP_OK;
+}
+
+int gbp_lin_iterate_nonlinear(gbp_lin_t *h, int32_t n_iters, int32_t *relin_counts)
+{
+    LENTER(h);
+    if (n_iters < 0) return set_error(GBP_EINVAL, "negative iteration count");
+    LCHK(nl_check_state(h));
+    if (!n_iters) return GBP_OK;
+    LCHK(nl_counts(h, n_iters));
+    const LinNonlin &nl = h->nl;
+    LHIPCHK(hipMemsetAsync(nl.counts, 0, (size_t)n_iters * sizeof(int), h->stream));
+    h->map_ready = false;                                   // the joint is that of the new linearisation point
+    const LinRelin r{h->p, nl.fdamp};
+    for (int it = 0; it < n_iters; ++it) {
+        nl_relin(h, NL_SWEEP, nl.counts + it);
+        if (h->p.F) hipLaunchKernelGGL((k_lin_factor<NL_D, false, LinRelin>), dim3((h->p.F + 63) / 64), dim3(64), 0, h->stream, r);
+        LCHK(gbp_lin_update_beliefs(h));
+    }
+    LHIPCHK(hipGetLastError());
+    if (relin_counts) {
+        LHIPCHK(hipMemcpyAsync(relin_counts, nl.counts, (size_t)n_iters * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        LHIPCHK(hipStreamSynchronize(h->stream));
+    }
+    return GBP_OK;
+}
+
+int gbp_lin_get_linearisation(gbp_lin_t *h, double *linpoint, int32_t *iters_since_relin, double *eta_damping)
+{
+    LENTER(h);
+    LCHK(nl_check_state(h));
+    const size_t F = (size_t)h->p.F;
+    std::vector<double> lp;
+    if (F) {
+        if (linpoint) {
+            lp.resize(2 * NL_D * F);
+            LHIPCHK(hipMemcpyAsync(lp.data(), h->nl.linpoint, lp.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        }
+        if (iters_since_relin) LHIPCHK(hipMemcpyAsync(iters_since_relin, h->nl.iters, F * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        if (eta_damping) LHIPCHK(hipMemcpyAsync(eta_damping, h->nl.fdamp, F * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    }
+    LHIPCHK(hipStreamSynchronize(h->stream));
+    if (linpoint) for (size_t f = 0; f < F; ++f) for (int k = 0; k < 2 * NL_D; ++k) linpoint[f * 2 * NL_D + k] = lp[(size_t)k * F + f];
+    return GBP_OK;
+}
+
+}  // extern "C"

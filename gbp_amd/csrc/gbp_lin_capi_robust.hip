@@ -58,6 +58,7 @@ extern "C" {
 int gbp_lin_set_robust(gbp_lin_t *h, const int32_t *loss, const double *threshold, const double *noise_var)
 {
     LENTER(h);
+    LIN_REFUSE_NONLINEAR(h, "gbp_lin_set_robust");
     const int F = h->p.F;
     if (!loss) {                                            // clear: back to the plain path
         LHIPCHK(hipStreamSynchronize(h->stream));
@@ -91,6 +92,7 @@ int gbp_lin_set_robust(gbp_lin_t *h, const int32_t *loss, const double *threshol
 int gbp_lin_robustify(gbp_lin_t *h)
 {
     LENTER(h);
+    LIN_REFUSE_NONLINEAR(h, "gbp_lin_robustify");
     LCHK(rob_check_state(h));
     return rob_robustify(h);
 }
@@ -98,6 +100,7 @@ int gbp_lin_robustify(gbp_lin_t *h)
 int gbp_lin_iterate_robust(gbp_lin_t *h, int32_t n_iters)
 {
     LENTER(h);
+    LIN_REFUSE_NONLINEAR(h, "gbp_lin_iterate_robust");
     if (n_iters < 0) return set_error(GBP_EINVAL, "negative iteration count");
     LCHK(rob_check_state(h));
     for (int it = 0; it < n_iters; ++it) {

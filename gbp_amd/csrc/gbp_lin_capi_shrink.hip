@@ -134,6 +134,7 @@ extern "C" {
 int gbp_lin_shrink(gbp_lin_t *h, const gbp_lin_shrink_desc_t *d)
 {
     LENTER(h);
+    LIN_REFUSE_NONLINEAR(h, "gbp_lin_shrink");
     if (!d) return set_error(GBP_EINVAL, "NULL descriptor");
     LCHK(shr_validate(h, d));
     if (!d->n_retire_vars && !d->n_drop_factors) {          // nothing leaves: the maps are the identity

@@ -71,6 +71,7 @@ extern "C" {
 int gbp_lin_iterate_until(gbp_lin_t *h, const gbp_lin_until_opts_t *opts, double *trace, gbp_lin_until_info_t *info)
 {
     LENTER(h);
+    LIN_REFUSE_NONLINEAR(h, "gbp_lin_iterate_until");
     if (!opts) return set_error(GBP_EINVAL, "opts is NULL");
     const gbp_lin_until_opts_t o = *opts;
     if (o.max_iters < 0) return set_error(GBP_EINVAL, "negative max_iters");

@@ -10,6 +10,8 @@
 //   gbp_lin_capi_until.hip   sweeps until a tolerance is met, decided on the device, with a per-sweep trace: the gated and traced forms of
 //                            the same stage kernels (parameter blocks LinGated / LinTraced below), and what is the call's alone
 //                            (gbp_lin_until.hpp)
+//   gbp_lin_capi_nonlin.hip  nonlinear pairwise factors relinearised on the device (kernels in gbp_lin_nonlin.hpp): the relinearise stage,
+//                            the factor stage with per-factor damping (parameter block LinRelin below), the model-aware energy
 #pragma once
 #include "../../include/gbp_ba.h"
 #include "../../include/gbp_lin.h"
@@ -84,6 +86,22 @@ struct LinUntil {
     int *stop;                       // [2]: GBP_LIN_STOP_* (0: go on), and the sweep that decided
 };
 
+// Nonlinear factors (gbp_lin_nonlin.hpp): device memory owned by gbp_lin::allocs, allocated by gbp_lin_set_nonlinear.  Everything
+// per-factor is SoA with stride F like the rest of the handle.  feta / flam are the handle's own factor arrays (LinParams::feta / flam),
+// writable: a nonlinear handle keeps its generation (gbp_lin_extend / gbp_lin_shrink are refused), so they stay valid.
+struct LinNonlin {
+    const double *meas, *sinfo;      // [3][F] measurement z, square-root information s
+    double *linpoint;                // [6][F] Factor.linpoint gbp.py:231 = [xa; xb]
+    int *iters;                      // [F] Factor.iters_since_relin gbp.py:249
+    double *fdamp;                   // [F] Factor.eta_damping gbp.py:248
+    double *feta, *flam;             // what the relinearise stage rewrites
+    int *counts;                     // [cap] factors relinearised per sweep of the call in progress
+    int cap;                         // the largest n_iters seen (at least 1)
+    double beta;                     // FactorGraph.beta gbp.py:32
+    int num_undamped, min_linear;    // gbp.py:33-34
+    int model;                       // GBP_LIN_MODEL_*
+};
+
 // The parameter block selects the form of a stage kernel (gbp_lin_sweep.hpp, gbp_lin_robust.hpp).  LinParams: the plain form;
 // lin_stopped() is the constant false and the gate compiles away.  LinGated: a sweep queued by gbp_lin_iterate_until, which returns at
 // its head once stop[0] != 0 (an earlier sweep of the call met a tolerance).  LinTraced: the belief stage of such a sweep, gated and with
@@ -95,6 +113,12 @@ struct LinTraced : LinParams {
     LinUntil u;
     const double *x;
 };
+// LinRelin: the factor stage of a sweep of gbp_lin_iterate_nonlinear, where every factor has a damping of its own (gbp.py:50-52).
+struct LinRelin : LinParams {
+    const double *fdamp;         // [F] Factor.eta_damping gbp.py:248
+};
+GBP_DEV double lin_damping(const LinParams &p, int) { return p.damping; }
+GBP_DEV double lin_damping(const LinRelin &p, int f) { return p.fdamp[f]; }
 GBP_DEV bool lin_stopped(const LinParams &) { return false; }
 GBP_DEV bool lin_stopped(const LinGated &p) { return p.stop[0] != 0; }
 GBP_DEV bool lin_stopped(const LinTraced &p) { return p.u.stop[0] != 0; }
@@ -121,6 +145,8 @@ struct gbp_lin {
     LinRobust rob{};                 // gbp_lin_capi_robust.hip
     bool rob_alloc = false;          // rob's arrays exist; losses are set while p.w != nullptr
     LinUntil until{};                // gbp_lin_capi_until.hip
+    LinNonlin nl{};                  // gbp_lin_capi_nonlin.hip
+    bool nonlinear = false;          // gbp_lin_set_nonlinear was called: (eta_f, Lambda_f) are those of nl.linpoint
 };
 
 #define LHIPCHK(expr)                                                                                       \
@@ -140,7 +166,14 @@ struct gbp_lin {
 namespace gbp {
 int lin_map_prepare(gbp_lin *h);                    // gbp_lin_capi_map.hip: LinMap's workspace (once per handle), LDL^T and joint eta (per set of weights)
 int lin_sweep(gbp_lin *h);                          // gbp_lin_capi.hip: one synchronous iteration at the weights as they stand, queued on the stream
+int lin_nonlin_energy(gbp_lin *h, double *out);     // gbp_lin_capi_nonlin.hip: one partial per block of 256 factors into `out`, queued on the stream
 }
+
+// the entry points that a nonlinear handle refuses (include/gbp_lin.h): decided before anything changes
+#define LIN_REFUSE_NONLINEAR(h, what)                                                                                       \
+    do {                                                                                                                    \
+        if ((h)->nonlinear) return set_error(GBP_ESTATE, what " is not available on a handle with nonlinear factors");      \
+    } while (0)
 
 // n elements of device memory (at least one), owned by the handle: gbp_lin_destroy frees whatever `allocs` still lists
 template <typename T>

@@ -1,0 +1,167 @@
+// gbp_lin_nonlin.hpp -- nonlinear pairwise factors of the linear engine on gfx950, relinearised on the device: FactorGraph(
+// nonlinear_factors=True) with relinearise_factors (gbp.py:64-80), the per-factor damping of compute_all_messages (gbp.py:46-54) and
+// Factor.compute_factor at a moving linearisation point (gbp.py:267-294).  include/gbp_lin.h states the semantics.
+//
+// The model is a template parameter of what evaluates it; there is one so far, GBP_LIN_MODEL_SE2_BETWEEN: x = (tx, ty, theta), and with
+// c = cos theta_a, s_ = sin theta_a, dx = xb - xa, dy = yb - ya
+//   h = diag(s) [ c dx + s_ dy ;  -s_ dx + c dy ;  theta_b - theta_a ]
+//   J = diag(s) [ -c  -s_  (-s_ dx + c dy) |  c   s_  0 ;   s_ -c  (-c dx - s_ dy) | -s_  c  0 ;   0  0  -1 | 0  0  1 ]
+//   Lambda_f = J^T J,  eta_f = J^T (J x0 + diag(s) z - h(x0))                                      (gbp.py:280-289, noise variance 1)
+// Angles are never wrapped: the reference does not wrap, and the caller keeps theta continuous.
+//   nonlin_h<MODEL>, nonlin_factor<MODEL>   the model: h at a point; eta_f and packed-upper Lambda_f at a linearisation point
+//   k_lin_relin<MODEL>     one lane per factor: the test of gbp.py:75, the factor re-made where it passes, iters, and the damping
+//                          switch of gbp.py:50-51; the relinearised factors of a wave are counted by a popcount and ONE integer atomic add
+//   k_lin_energy_nl<MODEL> sum_f 0.5 |h(mu) - diag(s) z|^2 at the belief means, in the block / partials shape of k_lin_energy
+// The factor stage of such a sweep is k_lin_factor<3, false, LinRelin> (gbp_lin_sweep.hpp), instantiated in gbp_lin_capi_nonlin.hip.
+// The model routines are host/device, so a host program can run them.
+#pragma once
+#include "gbp_lin_handle.hpp"
+#include "gbp_math.hpp"
+
+namespace gbp {
+
+constexpr int NL_D = 3;                                   // dofs of a variable of every model so far
+constexpr int NL_M = 3;                                   // rows of a measurement
+
+// how k_lin_relin is run
+constexpr int NL_SWEEP = 0;                               // the stage of a sweep: test, iters, damping switch
+constexpr int NL_ALONE = 1;                               // relinearise_factors alone (gbp.py:64-80): no damping switch
+constexpr int NL_INIT = 2;                                // compute_all_factors (gbp.py:60-62): every factor, iters = 1, damping = 0
+
+template <int MODEL> struct NonlinModel;
+
+template <> struct NonlinModel<GBP_LIN_MODEL_SE2_BETWEEN> {
+    // h(x) whitened, and the two entries of J that depend on the translation; c, sn = cos, sin of theta_a
+    static GBP_HD void h(const double (&x)[6], const double (&s)[3], double c, double sn, double (&out)[3])
+    {
+        const double dx = x[3] - x[0], dy = x[4] - x[1];
+        out[0] = s[0] * (c * dx + sn * dy);
+        out[1] = s[1] * (-sn * dx + c * dy);
+        out[2] = s[2] * (x[5] - x[2]);
+    }
+    static GBP_HD void jac(const double (&x)[6], const double (&s)[3], double c, double sn, double (&J)[3][6])
+    {
+        const double dx = x[3] - x[0], dy = x[4] - x[1];
+        J[0][0] = -s[0] * c;  J[0][1] = -s[0] * sn; J[0][2] = s[0] * (-sn * dx + c * dy); J[0][3] = s[0] * c;   J[0][4] = s[0] * sn; J[0][5] = 0.0;
+        J[1][0] = s[1] * sn;  J[1][1] = -s[1] * c;  J[1][2] = s[1] * (-c * dx - sn * dy); J[1][3] = -s[1] * sn; J[1][4] = s[1] * c;  J[1][5] = 0.0;
+        J[2][0] = 0.0;        J[2][1] = 0.0;        J[2][2] = -s[2];                      J[2][3] = 0.0;        J[2][4] = 0.0;       J[2][5] = s[2];
+    }
+};
+
+// 0.5 |h(x) - diag(s) z|^2 (Factor.energy gbp.py:261-265 with noise variance 1)
+template <int MODEL>
+GBP_HD double nonlin_energy(const double (&x)[6], const double (&z)[3], const double (&s)[3])
+{
+    double sn, c, h[3], e = 0.0;
+    sincos(x[2], &sn, &c);
+    NonlinModel<MODEL>::h(x, s, c, sn, h);
+#pragma unroll
+    for (int k = 0; k < NL_M; ++k) { const double r = h[k] - s[k] * z[k]; e += r * r; }
+    return 0.5 * e;
+}
+
+// Factor.compute_factor at linpoint x (gbp.py:280-289): eta_f [6], Lambda_f packed upper [21] (the layout k_lin_factor reads)
+template <int MODEL>
+GBP_HD void nonlin_factor(const double (&x)[6], const double (&z)[3], const double (&s)[3], double (&eta)[6], double (&lam)[Sym<6>::size])
+{
+    double sn, c, h[3], J[3][6], b[3];
+    sincos(x[2], &sn, &c);                                  // once: h and J share it
+    NonlinModel<MODEL>::h(x, s, c, sn, h);
+    NonlinModel<MODEL>::jac(x, s, c, sn, J);
+#pragma unroll
+    for (int k = 0; k < NL_M; ++k) {                        // J x0 + diag(s) z - h(x0)
+        double v = s[k] * z[k] - h[k];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) v += J[k][i] * x[i];
+        b[k] = v;
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        double e = 0.0;
+#pragma unroll
+        for (int k = 0; k < NL_M; ++k) e += J[k][i] * b[k];
+        eta[i] = e;
+#pragma unroll
+        for (int j = i; j < 6; ++j) {
+            double v = 0.0;
+#pragma unroll
+            for (int k = 0; k < NL_M; ++k) v += J[k][i] * J[k][j];
+            lam[Sym<6>::at(i, j)] = v;
+        }
+    }
+}
+
+// One lane per factor.  A lane that does not relinearise writes iters only (and its damping in the sweep in which that switches); a
+// relinearising lane writes the 6 + 21 doubles of the factor, the 6 of the linpoint, iters and its damping.  Lanes past F neither load nor
+// store.  `count`: the slot of this sweep (nullptr for NL_INIT): one integer atomic add per wave that relinearised anything.
+template <int MODEL>
+__global__ __launch_bounds__(256) void k_lin_relin(LinParams p, LinNonlin n, int mode, int *count)
+{
+    constexpr int D = NL_D, P = LinDims<D>::P, REC = LinDims<D>::REC;
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    const bool live = f < p.F;
+    const size_t F = (size_t)p.F;
+    bool relin = false;
+    if (live) {
+        const double *ma = p.bel + (size_t)p.va[f] * REC + D + P, *mb = p.bel + (size_t)p.vb[f] * REC + D + P;
+        double x[6];
+#pragma unroll
+        for (int k = 0; k < D; ++k) { x[k] = ma[k]; x[D + k] = mb[k]; }
+        int it = 1;
+        if (mode == NL_INIT) relin = true;
+        else {
+            it = n.iters[f];
+            double d2 = 0.0;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) { const double d = n.linpoint[k * F + f] - x[k]; d2 += d * d; }
+            relin = sqrt(d2) > n.beta && it >= n.min_linear;                      // gbp.py:75
+            it = relin ? 0 : it + 1;                                               // gbp.py:77, 80
+        }
+        n.iters[f] = it;
+        if (relin) {
+            double z[3], s[3], eta[6], lam[Sym<6>::size];
+#pragma unroll
+            for (int k = 0; k < NL_M; ++k) { z[k] = n.meas[k * F + f]; s[k] = n.sinfo[k * F + f]; }
+            nonlin_factor<MODEL>(x, z, s, eta, lam);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) { n.feta[k * F + f] = eta[k]; n.linpoint[k * F + f] = x[k]; }
+#pragma unroll
+            for (int k = 0; k < Sym<6>::size; ++k) n.flam[(size_t)k * F + f] = lam[k];
+        }
+        // gbp.py:78, then the switch of gbp.py:50-51 on the iters just written (0 after a relinearisation: fires when num_undamped == 0)
+        if (mode == NL_SWEEP && it == n.num_undamped) n.fdamp[f] = p.damping;
+        else if (relin) n.fdamp[f] = 0.0;
+    }
+    if (count) {
+        const unsigned long long who = __ballot(relin);
+        if ((threadIdx.x & 63) == 0 && who) atomicAdd(count, __popcll(who));
+    }
+}
+
+// sum_f 0.5 |h(mu) - diag(s) z|^2 at the current belief means (gbp.py:36-44, 251-265): one partial per block, the lanes of a wave and
+// the four waves of a block added in a fixed order, exactly the shape of k_lin_energy (gbp_lin_sweep.hpp)
+template <int MODEL>
+__global__ __launch_bounds__(256) void k_lin_energy_nl(LinParams p, LinNonlin n, double *out)
+{
+    constexpr int D = NL_D, P = LinDims<D>::P, REC = LinDims<D>::REC;
+    __shared__ double red[256 / 64];
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    const size_t F = (size_t)p.F;
+    double e = 0.0;
+    if (f < p.F) {
+        const double *ma = p.bel + (size_t)p.va[f] * REC + D + P, *mb = p.bel + (size_t)p.vb[f] * REC + D + P;
+        double x[6], z[3], s[3];
+#pragma unroll
+        for (int k = 0; k < D; ++k) { x[k] = ma[k]; x[D + k] = mb[k]; }
+#pragma unroll
+        for (int k = 0; k < NL_M; ++k) { z[k] = n.meas[k * F + f]; s[k] = n.sinfo[k * F + f]; }
+        e = nonlin_energy<MODEL>(x, z, s);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) e += __shfl_down(e, off, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = e;
+    __syncthreads();
+    if (threadIdx.x == 0) out[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+
+}  // namespace gbp

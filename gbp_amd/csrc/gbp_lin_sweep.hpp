@@ -5,7 +5,8 @@
 // The parameter block PT (gbp_lin_handle.hpp) selects the form, and two translation units instantiate them: gbp_lin_capi.hip launches the
 // plain forms (PT = LinParams), gbp_lin_capi_until.hip the gated ones (PT = LinGated; for the belief stage LinTraced, gated and traced),
 // which return at their head once gbp_lin_iterate_until's stop word is set.  For PT = LinParams lin_stopped() is the constant false and
-// the gate -- and with `if constexpr` the trace -- compiles away.
+// the gate -- and with `if constexpr` the trace -- compiles away.  gbp_lin_capi_nonlin.hip instantiates the factor stage once more with
+// PT = LinRelin, where lin_damping() reads the factor's own damping instead of the graph's.
 #pragma once
 #include "gbp_lin_robust.hpp"
 #include "gbp_lin_until.hpp"
@@ -117,7 +118,7 @@ __global__ __launch_bounds__(64) void k_lin_factor(PT p)
 #pragma unroll
             for (int j = 0; j < D; ++j) { aab[i][j] *= w; aba[j][i] = aab[i][j]; }
     }
-    const double d = p.damping;
+    const double d = lin_damping(p, f);                     // PT = LinRelin: the factor's own (gbp.py:52), else the graph's (gbp.py:54)
     double lam[P], eta[D], S[P], en[D];
     // to a: eliminate b
 #pragma unroll

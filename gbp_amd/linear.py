@@ -206,12 +206,56 @@ class LinearEngine:
     def update_all_beliefs(self):
         check(self._lib.gbp_lin_update_beliefs(self._h))
 
-    def synchronous_iteration(self, robustify=False):
-        self.iterate(1, robustify)
+    def synchronous_iteration(self, robustify=False, relinearise=False):
+        self.iterate(1, robustify, relinearise)
 
-    def iterate(self, n, robustify=False):
-        """n sweeps; robustify=True: every sweep re-makes the weights first (synchronous_iteration(robustify=True) gbp.py:86-92)."""
+    def iterate(self, n, robustify=False, relinearise=False):
+        """n sweeps; robustify=True: every sweep re-makes the weights first (synchronous_iteration(robustify=True) gbp.py:86-92).
+        relinearise=True (a handle of se2_pose_graph): n x synchronous_iteration(local_relin=True) -- every sweep relinearises the
+        factors whose belief means left their linearisation point by more than beta, and every factor has its own damping
+        (gbp.py:46-54, 64-80); returns the number of factors relinearised in each sweep, (n,) int32, counted on the device."""
+        if relinearise:
+            if robustify:
+                raise ValueError("robust nonlinear factors are not supported")
+            counts = np.zeros(max(int(n), 1), dtype=np.int32)
+            check(self._lib.gbp_lin_iterate_nonlinear(self._h, int(n), iptr(counts)))
+            return counts[:max(int(n), 0)]
         check((self._lib.gbp_lin_iterate_robust if robustify else self._lib.gbp_lin_iterate)(self._h, int(n)))
+
+    # nonlinear pose graphs: FactorGraph(nonlinear_factors=True) (gbp.py:30-34) for the SE(2) relative-pose factor
+    @classmethod
+    def se2_pose_graph(cls, var_a, var_b, measurement, sqrt_info, prior_eta, prior_lam, beta, num_undamped_iters, min_linear_iters,
+                       eta_damping=0.0, device=0):
+        """A planar pose graph on variables (tx, ty, theta): factor f joins var_a[f] and var_b[f] with measurement[f] (the pose of b
+        in the frame of a) and sqrt_info[f] > 0 per component.  The factors are linearised on the device at the prior means
+        (compute_all_factors gbp.py:60-62); iterate(n, relinearise=True) then relinearises them by the reference's local schedule
+        (beta, min_linear_iters gbp.py:64-80; num_undamped_iters and eta_damping gbp.py:46-54).  Angles are never wrapped: keep
+        theta continuous along the trajectory."""
+        var_a = i32(var_a).reshape(-1)
+        F = var_a.shape[0]
+        eng = cls(var_a, var_b, np.zeros((F, 6)), np.zeros((F, 6, 6)), prior_eta, prior_lam, eta_damping=eta_damping, device=device)
+        if eng.D != 3:
+            raise ValueError("an SE(2) pose has 3 dofs")
+        eng.set_nonlinear(measurement, sqrt_info, beta, num_undamped_iters, min_linear_iters)
+        return eng
+
+    def set_nonlinear(self, measurement, sqrt_info, beta, num_undamped_iters, min_linear_iters, model=_capi.LIN_MODEL_SE2_BETWEEN):
+        z = f64(np.asarray(measurement, dtype=np.float64).reshape(self.F, 3))
+        s = f64(np.ascontiguousarray(np.broadcast_to(np.asarray(sqrt_info, dtype=np.float64), (self.F, 3))))
+        d = _capi.LinNonlinear(int(model), int(num_undamped_iters), int(min_linear_iters), 0, float(beta), dptr(z), dptr(s))
+        check(self._lib.gbp_lin_set_nonlinear(self._h, ct.byref(d)))
+
+    def relinearise(self):
+        """relinearise_factors (gbp.py:64-80) alone; returns the number of factors relinearised."""
+        n = ct.c_int32()
+        check(self._lib.gbp_lin_relinearise(self._h, ct.byref(n)))
+        return n.value
+
+    def linearisation(self):
+        """(linpoint (F, 6) = [xa; xb], iters_since_relin (F,) int32, eta_damping (F,)) of every factor (gbp.py:231, 248-249)."""
+        lp, it, dm = np.zeros((max(self.F, 1), 6)), np.zeros(max(self.F, 1), dtype=np.int32), np.zeros(max(self.F, 1))
+        check(self._lib.gbp_lin_get_linearisation(self._h, dptr(lp), iptr(it), dptr(dm)))
+        return lp[:self.F], it[:self.F], dm[:self.F]
 
     def iterate_until(self, max_iters, tol_step=0.0, tol_map=0.0, energy=False, map_distance=False, robustify=False, check_every=8):
         """Up to max_iters sweeps in one call, the loop of ndim_posegraph.py:104-108 with the decision to stop taken on the device:

@@ -16,7 +16,8 @@
  *
  * Beside the sweep: the batch MAP (the `mu` of FactorGraph.joint_distribution_cov) and exact marginal covariances (its `sigma`, for
  * chosen variables), both by block-Jacobi conjugate gradients on the block-sparse joint; robust losses; growing and shrinking a live
- * graph; and sweeps to convergence with the stop decided on the device (gbp_lin_iterate_until) -- below.
+ * graph; sweeps to convergence with the stop decided on the device (gbp_lin_iterate_until); and one NONLINEAR factor family, the SE(2)
+ * relative-pose factor, relinearised on the device by the reference's local schedule (gbp_lin_set_nonlinear) -- below.
  */
 #ifndef GBP_LIN_H
 #define GBP_LIN_H
@@ -257,6 +258,74 @@ typedef struct { int32_t iters, converged, reason, reserved; } gbp_lin_until_inf
 int  gbp_lin_iterate_until(gbp_lin_t *h, const gbp_lin_until_opts_t *opts,
                            double *trace /* host, max_iters x 3, or NULL */, gbp_lin_until_info_t *info /* or NULL */);
 int  gbp_lin_get_alloc_count(gbp_lin_t *h, int32_t *count);
+
+/* ---- nonlinear pairwise factors, relinearised on the device: FactorGraph(nonlinear_factors=True) (gbp.py:30-34) with relinearise_factors
+ * (gbp.py:64-80), the per-factor damping that a relinearisation switches off and num_undamped_iters sweeps later restores (gbp.py:46-54),
+ * and Factor.compute_factor at a moving linearisation point (gbp.py:267-294) -- without a host round trip per sweep ----
+ * One factor family so far, GBP_LIN_MODEL_SE2_BETWEEN: the planar relative-pose ("between") factor on variables x = (tx, ty, theta),
+ * d = 3.  A factor joins a and b and has a measurement z in R^3 and positive square-root information s in R^3, one per component (the
+ * reference knows a scalar noise std only: this is its arithmetic with std 1 and a whitened meas_fn / jac_fn).  With c = cos theta_a,
+ * s_ = sin theta_a, dx = xb - xa, dy = yb - ya:
+ *   h(xa, xb) = diag(s) [ c dx + s_ dy ;  -s_ dx + c dy ;  theta_b - theta_a ]                       (Factor.meas_fn gbp.py:237)
+ *   J = diag(s) [ -c  -s_  (-s_ dx + c dy) |  c   s_  0 ]                                            (Factor.jac_fn gbp.py:238)
+ *               [  s_ -c   (-c dx - s_ dy) | -s_  c   0 ]
+ *               [  0   0        -1         |  0   0   1 ]
+ *   Lambda_f = J^T J,  eta_f = J^T (J x0 + diag(s) z - h(x0))  at the linearisation point x0         (gbp.py:280-289, noise variance 1)
+ * ANGLES ARE NOT WRAPPED anywhere -- not in h, not in the distance of the relinearisation test, not in the beliefs -- because the
+ * reference does not wrap: the caller keeps theta continuous along the trajectory (a pose 1.5 turns on has theta = 3 pi + ...).
+ *
+ * gbp_lin_set_nonlinear (Factor(meas_fn=, jac_fn=) gbp.py:207-208, 237-239; compute_all_factors gbp.py:60-62, 273-276; the per-factor
+ * state gbp.py:248-249): legal on a handle with dofs == 3, without losses set, and not already nonlinear; GBP_EINVAL for a NULL
+ * descriptor or array (with F > 0), an unknown model, dofs != 3, a negative num_undamped_iters / min_linear_iters, beta negative or NaN
+ * (+inf is legal: never relinearise), a sqrt_info that is not positive and finite or a measurement that is not finite; GBP_ESTATE with
+ * losses set or on a handle that is already nonlinear; all decided before anything changes.  The eta_f, Lambda_f given at create are
+ * ignored and overwritten, factor_const is not used.  If the handle has no beliefs the belief stage runs first (belief = prior); then
+ * every factor is computed at linpoint = its adjacent belief means, iters_since_relin = 1 and the per-factor damping = 0.  Messages are
+ * left as they are.
+ *
+ * gbp_lin_iterate_nonlinear: n x synchronous_iteration(local_relin=True, robustify=False) (gbp.py:86-92), three kernels per sweep queued
+ * on the handle's stream:
+ *   relinearise (gbp.py:64-80)  per factor dist = |linpoint - [mu_a; mu_b]|_2; if dist > beta && iters_since_relin >= min_linear_iters:
+ *                               eta_f, Lambda_f and the linpoint re-made at the means, iters = 0, the factor's damping = 0; else iters += 1.
+ *                               Then the switch of gbp.py:50-51: a factor whose iters == num_undamped_iters takes the graph's eta_damping.
+ *                               Kept as the reference has it: iters starts at 1 and is incremented BEFORE the test, so a factor that has
+ *                               never relinearised never meets num_undamped_iters <= 1, and with num_undamped_iters == 0 the switch fires
+ *                               only in the very sweep a factor relinearises (iters == 0 there).
+ *   factor (gbp.py:52)          the messages, each factor with ITS damping;
+ *   belief (gbp.py:56-58)       the existing stage.
+ * relin_counts[i] (host, n_iters, or NULL): the number of factors relinearised in sweep i, counted on the device -- integer adds, which
+ * do not depend on their order -- and downloaded once after the call.  The device buffer of the counts grows to the largest n_iters
+ * seen, like the trace buffer of gbp_lin_iterate_until.  n_iters < 0: GBP_EINVAL.
+ * gbp_lin_relinearise: relinearise_factors (gbp.py:64-80) alone -- the test, the re-made factors, iters; not the damping switch, which
+ * belongs to compute_all_messages.  n_relinearised may be NULL.
+ * gbp_lin_get_linearisation: Factor.linpoint (gbp.py:231, F x 6 = [xa; xb]), Factor.iters_since_relin and Factor.eta_damping
+ * (gbp.py:248-249); any of the three may be NULL.
+ * On a handle that is not nonlinear the three return GBP_ESTATE.
+ *
+ * The older entry points on a nonlinear handle:
+ *   gbp_lin_iterate          synchronous_iteration(local_relin=False): no relinearisation, the graph-level damping (gbp.py:54), iters untouched;
+ *   gbp_lin_energy           sum_f 0.5 |h(mu) - diag(s) z|^2 at the CURRENT belief means through the nonlinear h (gbp.py:36-44, 251-265),
+ *                            per-block partials added in a fixed order as before;
+ *   gbp_lin_joint_matvec / joint_eta / solve_map / solve_marginals   the joint "at the current linearisation point" (gbp.py:96-97):
+ *                            eta_f, Lambda_f live where the solvers read them.  Every call that may relinearise marks the solver's
+ *                            LDL^T and joint eta stale, as a change of robust weights does; a solve after it is one Gauss-Newton step;
+ *   gbp_lin_set_robust, gbp_lin_robustify, gbp_lin_iterate_robust, gbp_lin_iterate_until, gbp_lin_extend, gbp_lin_shrink
+ *                            GBP_ESTATE with a message; nothing changes.
+ * No floating-point atomics: two identical call sequences on two handles are bit-identical, counts included. */
+#define GBP_LIN_MODEL_SE2_BETWEEN 1
+typedef struct {
+    int32_t model;                      /* GBP_LIN_MODEL_*                                                     */
+    int32_t num_undamped_iters;         /* FactorGraph.num_undamped_iters gbp.py:33, >= 0                      */
+    int32_t min_linear_iters;           /* FactorGraph.min_linear_iters gbp.py:34, >= 0                        */
+    int32_t reserved;
+    double beta;                        /* FactorGraph.beta gbp.py:32, >= 0; +inf = never relinearise          */
+    const double *measurement;          /* F x 3   Factor.measurement gbp.py:233 (not whitened)                */
+    const double *sqrt_info;            /* F x 3, positive and finite                                          */
+} gbp_lin_nonlinear_desc_t;
+int  gbp_lin_set_nonlinear(gbp_lin_t *h, const gbp_lin_nonlinear_desc_t *d);    /* compute_all_factors gbp.py:60-62 */
+int  gbp_lin_relinearise(gbp_lin_t *h, int32_t *n_relinearised /* or NULL */);  /* relinearise_factors gbp.py:64-80 */
+int  gbp_lin_iterate_nonlinear(gbp_lin_t *h, int32_t n_iters, int32_t *relin_counts /* host, n_iters, or NULL */);   /* n x synchronous_iteration(local_relin=True) gbp.py:86-92 */
+int  gbp_lin_get_linearisation(gbp_lin_t *h, double *linpoint /* F x 6 */, int32_t *iters_since_relin /* F */, double *eta_damping /* F */);   /* Factor.linpoint gbp.py:231, iters_since_relin / eta_damping gbp.py:248-249; any may be NULL */
 
 #ifdef __cplusplus
 }

@@ -34,8 +34,12 @@ ap.add_argument('--shrink', action='store_true',
 ap.add_argument('--until', action='store_true',
                 help='instead of the run above: on the same two graphs time iterate_until(n) (tolerances off; no column, the energy column, both columns) '
                      'against iterate(n) on the same handle and against the host loop iterate(1); energy(); map_distance(), alternating; writes profiles/linear_until.json')
+ap.add_argument('--nonlinear', action='store_true',
+                help='instead of the run above: the same two graphs re-posed as SE(2) pose graphs; time iterate(n, relinearise=True) with beta = +inf and with '
+                     'beta = 0 against iterate(n) on the same handle, and one host relinearisation + gbp_lin_create against iterate(1, relinearise=True); '
+                     'writes profiles/linear_nonlinear.json')
 ap.add_argument('--parent-results', default=None,
-                help="--extend / --shrink / --until: a file of lines 'parent {json}' / 'here {json}', each the JSON line of a plain run of this tool from the parent "
+                help="--extend / --shrink / --until / --nonlinear: a file of lines 'parent {json}' / 'here {json}', each the JSON line of a plain run of this tool from the parent "
                      "commit's tree or from this one (run alternating, in the same session); summarised per workload under sweeps_per_s_vs_parent")
 ap.add_argument('--repeats', type=int, default=5, help='--marginals / --robust / --extend: repeats per timing (the median is reported)')
 a = ap.parse_args()
@@ -444,6 +448,124 @@ def until_profile():
     print(json.dumps(out))
 
 
+def se2_graph(N, k, rs):
+    """N poses on a circle of radius N / 20 (about 0.3 between neighbours), headings unwrapped over one turn, each joined to its next k
+    neighbours (the closing ones measure minus a turn of heading: nothing is wrapped); sqrt information (10, 10, 20), noise to match;
+    priors sigma (1, 1, 0.5) at truth + N(0, (0.1, 0.1, 0.03))."""
+    th = np.arange(N) * 2 * np.pi / N
+    R = N / 20.0
+    truth = np.stack([R * np.cos(th), R * np.sin(th), th + np.pi / 2], 1)
+    va = np.repeat(np.arange(N), k)
+    vb = (va + np.tile(np.arange(1, k + 1), N)) % N
+    s = np.tile(np.array([10.0, 10.0, 20.0]), (va.shape[0], 1))
+    z = se2_h(np.concatenate([truth[va], truth[vb]], 1), np.ones_like(s)) + rs.normal(0, 1, s.shape) / s
+    pl = np.ascontiguousarray(np.broadcast_to(np.diag([1.0, 1.0, 4.0]), (N, 3, 3)))
+    pe = np.einsum('nij,nj->ni', pl, truth + rs.normal(0, 1, (N, 3)) * np.array([0.1, 0.1, 0.03]))
+    return va.astype(np.int32), vb.astype(np.int32), z, s, pe, pl
+
+
+def se2_h(x, s):
+    c, sn = np.cos(x[:, 2]), np.sin(x[:, 2])
+    dx, dy = x[:, 3] - x[:, 0], x[:, 4] - x[:, 1]
+    return s * np.stack([c * dx + sn * dy, -sn * dx + c * dy, x[:, 5] - x[:, 2]], 1)
+
+
+def se2_host_factors(x, z, s):
+    """What a caller does today: eta_f, Lambda_f of every factor at x (F, 6), vectorised numpy (gbp.py:280-289)."""
+    c, sn = np.cos(x[:, 2]), np.sin(x[:, 2])
+    dx, dy = x[:, 3] - x[:, 0], x[:, 4] - x[:, 1]
+    o, l = np.zeros_like(c), np.ones_like(c)
+    J = s[:, :, None] * np.stack([np.stack([-c, -sn, -sn * dx + c * dy, c, sn, o], 1), np.stack([sn, -c, -c * dx - sn * dy, -sn, c, o], 1),
+                                  np.stack([o, o, -l, o, o, l], 1)], 1)
+    b = np.einsum('fki,fi->fk', J, x) + s * z - se2_h(x, s)
+    return np.einsum('fki,fk->fi', J, b), np.einsum('fki,fkj->fij', J, J)
+
+
+def nonlinear_profile():
+    """Host clock around whole calls, each ending in a stream synchronise, after a warm-up of every form; --repeats alternating rounds of
+    --steps sweeps, medians reported per sweep, spread = (max - min) / median.  (a) on ONE handle with beta = +inf: iterate(n) against
+    iterate(n, relinearise=True), where the relinearise stage runs and relinearises nothing.  (b) a second handle with beta = 0 and
+    min_linear_iters = 0, where every factor relinearises in every sweep.  (c) what a caller has without this path: the means downloaded,
+    every factor re-made on the host in vectorised numpy, gbp_lin_create of the graph and the belief stage -- against
+    iterate(1, relinearise=True) on the handle of (b); the host figure loses every message besides.
+    Counted beside (a): per factor the stage gathers two means (6 doubles), reads the linpoint (6) and iters (0.5), writes iters (0.5), and
+    the factor stage reads the factor's damping (1): 14 doubles on top of the plain sweep's count, plus one kernel boundary priced at
+    3.2 us.  (b) adds the measurement and square-root information read (6) and eta_f, Lambda_f and the linpoint written (33).  The counts
+    are of algorithmic bytes, not of what the caches fetch (gathers fetch whole lines): an excess of the measured ratio over the counted
+    one is UNEXPLAINED here -- no counters were collected."""
+    D, runs, boundary_ms = 3, [], 3.2e-3
+    for N, k in ((200_000, 5), (1_000_000, 1)):
+        va, vb, z, s, pe, pl = se2_graph(N, k, np.random.RandomState(0))
+        F = va.shape[0]
+        e = LinearEngine.se2_pose_graph(va, vb, z, s, pe, pl, float('inf'), 4, 2, eta_damping=0.4)
+        e0 = LinearEngine.se2_pose_graph(va, vb, z, s, pe, pl, 0.0, 4, 0, eta_damping=0.4)
+        n = a.steps
+
+        def plain():
+            t = time.perf_counter(); e.iterate(n); e.sync()
+            return 1e3 * (time.perf_counter() - t) / n
+
+        def relin(h):
+            t = time.perf_counter(); c = h.iterate(n, relinearise=True); t = time.perf_counter() - t
+            return 1e3 * t / n, c
+
+        def one_device():
+            t = time.perf_counter(); e0.iterate(1, relinearise=True); e0.sync()
+            return 1e3 * (time.perf_counter() - t)
+
+        def one_host():
+            t = time.perf_counter()
+            mu = e0.get_means().reshape(N, 3)
+            fe, fl = se2_host_factors(np.concatenate([mu[va], mu[vb]], 1), z, s)
+            h = LinearEngine(va, vb, fe, fl, pe, pl, eta_damping=0.4)
+            h.update_all_beliefs(); h.sync()
+            t = 1e3 * (time.perf_counter() - t)
+            h.close()
+            return t
+        e.iterate(a.warmup); e.sync(); relin(e); relin(e0); one_device(); one_host()
+        rec = {key: [] for key in ('plain', 'relin_none', 'relin_all', 'one_device', 'one_host')}
+        least = F
+        for _ in range(a.repeats):                          # alternating
+            rec['plain'].append(plain())
+            t, c = relin(e); assert not c.any(); rec['relin_none'].append(t)
+            t, c = relin(e0); least = min(least, int(c.min())); rec['relin_all'].append(t)
+            rec['one_device'].append(one_device()); rec['one_host'].append(one_host())
+        med = {key: statistics.median(v) for key, v in rec.items()}
+        spread = {key: (max(v) - min(v)) / med[key] for key, v in rec.items()}
+        per_f = sweep_doubles(D, 1.0 / k, False)
+        runs.append({"vars": N, "dofs": D, "k": k, "factors": F, "ms_per_sweep": med, "spread": spread, "ms_all": rec,
+                     "ratio_relin_none_over_plain": med['relin_none'] / med['plain'], "ratio_none_counted": (per_f + 14) / per_f + boundary_ms / med['plain'],
+                     "ratio_relin_all_over_plain": med['relin_all'] / med['plain'], "ratio_all_counted": (per_f + 14 + 39) / per_f + boundary_ms / med['plain'],
+                     "ratio_host_over_device_one_relinearising_sweep": med['one_host'] / med['one_device'],
+                     "doubles_per_factor_plain": per_f, "kernel_boundary_ms_assumed": boundary_ms, "counters_collected": False,
+                     "fewest_relinearised_in_a_beta_0_sweep": least,
+                     "energy_after": {"beta_inf": e.energy(), "beta_0": e0.energy()}})
+        e.close(); e0.close()
+    vs_parent = None
+    if a.parent_results:
+        by = {}
+        for ln in open(a.parent_results):
+            who, js = ln.split(' ', 1)
+            r = json.loads(js)
+            by.setdefault(r['config']['workload'], {'parent': [], 'here': []})[who].append(r['value'])
+        vs_parent = [{"workload": w, "parent": v['parent'], "here": v['here'], "median_parent": statistics.median(v['parent']),
+                      "median_here": statistics.median(v['here']),
+                      "spread_parent": (max(v['parent']) - min(v['parent'])) / statistics.median(v['parent']),
+                      "spread_here": (max(v['here']) - min(v['here'])) / statistics.median(v['here'])} for w, v in by.items()]
+    out = {"what": "tools/bench_linear.py --nonlinear on one MI355X: ms per sweep of gbp_lin_iterate_nonlinear against gbp_lin_iterate on the same handle, and "
+                   "against a host relinearisation + gbp_lin_create, on the 200k x 3 ring (k = 5) and the 1M-variable chain (k = 1) re-posed as SE(2)",
+           "method": " ".join(nonlinear_profile.__doc__.split()), "repeats": a.repeats, "sweep_steps": a.steps, "runs": runs,
+           "sweeps_per_s_vs_parent": vs_parent}
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'profiles', 'linear_nonlinear.json')
+    with open(path, 'w') as fh:
+        json.dump(out, fh, indent=1)
+        fh.write('\n')
+    print(json.dumps(out))
+
+
+if a.nonlinear:
+    nonlinear_profile()
+    sys.exit(0)
 if a.until:
     until_profile()
     sys.exit(0)
