@@ -153,17 +153,10 @@ int gbp_ba_extend(gbp_ba_t *h, const gbp_ba_ext_t *e, int32_t *old_to_new)
 {
     ENTER(h);
     if (!e) return fail(GBP_EINVAL, "null argument");
-    if (h->xch_fn || h->comm || h->peer.mailbox || h->peer.connected)
-        return fail(GBP_ESTATE, "a sharded handle (communicator, exchange callback or peer mailbox) cannot grow");
-    if (!h->has_beliefs) return fail(GBP_ESTATE, "the handle has no beliefs yet (gbp_ba_update_beliefs first)");
-    const int dC = e->n_new_cams, dL = e->n_new_lmks, dF = e->n_new_factors;
-    if (dC < 0 || dL < 0 || dF < 0) return fail(GBP_EINVAL, "negative size");
-    if (e->flags & ~GBP_FLAG_DEVICE_INPUT) return fail(GBP_EINVAL, "unknown flags 0x%x (only GBP_FLAG_DEVICE_INPUT)", e->flags);
-    if ((dC && !e->cam_means) || (dL && !e->lmk_means)) return fail(GBP_EINVAL, "null initial means");
-    if (dF && (!e->meas || !e->cam_idx || !e->lmk_idx)) return fail(GBP_EINVAL, "null observation arrays");
+    CHK(live_and_whole(h, "grow"));
+    CHK(sound_batch(h->p, e));
     const Params &op = h->p;
-    if ((int64_t)op.C + dC > INT32_MAX || (int64_t)op.L + dL > INT32_MAX || (int64_t)op.F + dF > INT32_MAX) return fail(GBP_EINVAL, "sizes exceed int32");
-    if (op.C + dC >= (1 << (32 - META_LMK_BITS))) return fail(GBP_EINVAL, "more than %d cameras are not supported", (1 << (32 - META_LMK_BITS)) - 1);
+    const int dC = e->n_new_cams, dL = e->n_new_lmks, dF = e->n_new_factors;
     if (!(e->flags & GBP_FLAG_DEVICE_INPUT)) {            // host ids: checked here, before anything is allocated
         for (int i = 0; i < dF; ++i)
             if (e->cam_idx[i] < 0 || e->cam_idx[i] >= op.C + dC || e->lmk_idx[i] < 0 || e->lmk_idx[i] >= op.L + dL)

@@ -424,15 +424,6 @@ int list_words(const char *what, int32_t count, const int32_t *ids, int limit, s
     return GBP_OK;
 }
 
-// what every call asks of the handle before it looks at its arguments
-int live_and_whole(const gbp_ba *h, const char *to_do)
-{
-    if (h->xch_fn || h->comm || h->peer.mailbox || h->peer.connected)
-        return fail(GBP_ESTATE, "a sharded handle (communicator, exchange callback or peer mailbox) cannot %s", to_do);
-    if (!h->has_beliefs) return fail(GBP_ESTATE, "the handle has no beliefs yet (gbp_ba_update_beliefs first)");
-    return GBP_OK;
-}
-
 // The engine: the lists are checked, the result is built beside the handle (window_into), the scratch goes; on success the maps go out
 // (sizes from BEFORE the call, NULL to skip) and the result becomes the handle, on failure the half-built graph goes and the handle is
 // what it was.  The caller has checked its own arguments and answered a step that changes nothing.
@@ -499,15 +490,9 @@ int gbp_ba_window_step(gbp_ba_t *h, const gbp_ba_window_t *step, const gbp_ba_wi
     if (step->lmk_mode != GBP_RETIRE_FOLD && step->lmk_mode != GBP_RETIRE_DROP)
         return fail(GBP_EINVAL, "mode %d is neither GBP_RETIRE_FOLD nor GBP_RETIRE_DROP", step->lmk_mode);
     const gbp_ba_ext_t *e = step->batch ? step->batch : &no_batch;
-    const int dC = e->n_new_cams, dL = e->n_new_lmks, dF = e->n_new_factors;
-    if (dC < 0 || dL < 0 || dF < 0) return fail(GBP_EINVAL, "negative size");
-    if (e->flags & ~GBP_FLAG_DEVICE_INPUT) return fail(GBP_EINVAL, "unknown flags 0x%x (only GBP_FLAG_DEVICE_INPUT)", e->flags);
-    if ((dC && !e->cam_means) || (dL && !e->lmk_means)) return fail(GBP_EINVAL, "null initial means");
-    if (dF && (!e->meas || !e->cam_idx || !e->lmk_idx)) return fail(GBP_EINVAL, "null observation arrays");
+    CHK(sound_batch(h->p, e));
     const Params &op = h->p;
-    if ((int64_t)op.C + dC > INT32_MAX || (int64_t)op.L + dL > INT32_MAX || (int64_t)op.F + dF > INT32_MAX ||
-        (int64_t)op.C + dC + (int64_t)op.L + dL + (int64_t)op.F + dF >= INT32_MAX)
-        return fail(GBP_EINVAL, "sizes exceed int32");
+    const int dC = e->n_new_cams, dL = e->n_new_lmks, dF = e->n_new_factors;
     const gbp_ba_window_maps_t maps = out ? *out : gbp_ba_window_maps_t{};
     if (!step->n_cull && !step->n_retire_cams && !step->n_retire_lmks && !dC && !dL && !dF) {      // an empty step: nothing changes
         graft_identity_maps(op, maps.cam_old_to_new, maps.lmk_old_to_new, maps.factor_old_to_new);

@@ -2,8 +2,9 @@
 // gbp_ba_window_step, gbp_ba_cull, gbp_ba_retire and gbp_ba_retire_landmarks (gbp_capi_window.hip).  Both build the new graph BESIDE the
 // handle by the create path (gbp::build_graph), move the state of the factors and variables that live on into the new layout, and swap
 // the new graph in only when everything has succeeded.  Here: the per-slot and per-variable moves (device), the arrays a rebuild
-// assembles for the create path (Survivors), and on the host the staging of inputs and scratch, the settings the new graph inherits, the
-// counters it carries, the swap itself and the maps of a call that changes nothing.
+// assembles for the create path (Survivors), and on the host what every call asks of the handle and of a batch before it starts
+// (live_and_whole, sound_batch), the staging of inputs and scratch, the settings the new graph inherits, the counters it carries, the
+// swap itself and the maps of a call that changes nothing.
 #pragma once
 #include "gbp_handle.hpp"
 
@@ -65,6 +66,31 @@ GBP_DEV void transplant_lmk(const Params &n, const Params &o, int nl, int ol)
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
+// what every call that rebuilds a handle asks of it before it looks at its arguments
+inline int live_and_whole(const gbp_ba *h, const char *to_do)
+{
+    if (h->xch_fn || h->comm || h->peer.mailbox || h->peer.connected)
+        return fail(GBP_ESTATE, "a sharded handle (communicator, exchange callback or peer mailbox) cannot %s", to_do);
+    if (!h->has_beliefs) return fail(GBP_ESTATE, "the handle has no beliefs yet (gbp_ba_update_beliefs first)");
+    return GBP_OK;
+}
+
+// what every call that brings a batch asks of it before its ids are looked at: sizes, flags, arrays, a union that an int can index
+// ([C + dC | L + dL | F + dF | 1]: the window engine does) and whose cameras fit the meta word
+inline int sound_batch(const Params &op, const gbp_ba_ext_t *e)
+{
+    const int dC = e->n_new_cams, dL = e->n_new_lmks, dF = e->n_new_factors;
+    if (dC < 0 || dL < 0 || dF < 0) return fail(GBP_EINVAL, "negative size");
+    if (e->flags & ~GBP_FLAG_DEVICE_INPUT) return fail(GBP_EINVAL, "unknown flags 0x%x (only GBP_FLAG_DEVICE_INPUT)", e->flags);
+    if ((dC && !e->cam_means) || (dL && !e->lmk_means)) return fail(GBP_EINVAL, "null initial means");
+    if (dF && (!e->meas || !e->cam_idx || !e->lmk_idx)) return fail(GBP_EINVAL, "null observation arrays");
+    if ((int64_t)op.C + dC > INT32_MAX || (int64_t)op.L + dL > INT32_MAX || (int64_t)op.F + dF > INT32_MAX ||
+        (int64_t)op.C + dC + (int64_t)op.L + dL + (int64_t)op.F + dF >= INT32_MAX)
+        return fail(GBP_EINVAL, "sizes exceed int32");
+    if (op.C + dC >= (1 << (32 - META_LMK_BITS))) return fail(GBP_EINVAL, "more than %d cameras are not supported", (1 << (32 - META_LMK_BITS)) - 1);
+    return GBP_OK;
+}
+
 template <typename T>
 inline int graft_stage(gbp_ba *h, const T *src, size_t n, bool on_device, std::vector<void *> &scratch, const T **out)
 {

@@ -189,41 +189,34 @@ class BAEngine:
         check(self._lib.gbp_ba_rebuild_count(self._h, ct.byref(v)))
         return v.value
 
-    # ---- shrinking (include/gbp_ba.h: gbp_ba_retire) ----------------------------------------------
+    # ---- shrinking (include/gbp_ba.h: gbp_ba_retire, gbp_ba_cull, gbp_ba_retire_landmarks) ----------
+    def _shrink(self, fn, ids, *extra):
+        """One of the three calls that take a list of ids (and `extra` arguments behind it) and return the three maps."""
+        ids = i32(np.asarray(ids, dtype=np.int64).reshape(-1))
+        cm, lm, fm = np.empty(self.C, np.int32), np.empty(self.L, np.int32), np.empty(self.F, np.int32)
+        check(fn(self._h, ids.size, iptr(ids) if ids.size else None, *extra, iptr(cm), iptr(lm), iptr(fm)))
+        self.C, self.L, self.F = int((cm >= 0).sum()), int((lm >= 0).sum()), int((fm >= 0).sum())
+        return cm, lm, fm
+
     def retire(self, cam_ids):
         """Retire cameras (the old keyframes of a fixed-lag window): their factors' messages to the landmarks are folded into the landmarks'
         priors, the cameras, their factors and every landmark left without a factor are removed and the survivors are renumbered compactly
         with all their solver state.  Returns (cam_map, lmk_map, factor_map): int32, one entry per OLD camera / landmark / factor, its new
         id or -1 when it is gone."""
-        ids = i32(np.asarray(cam_ids, dtype=np.int64).reshape(-1))
-        cm, lm, fm = np.empty(self.C, np.int32), np.empty(self.L, np.int32), np.empty(self.F, np.int32)
-        check(self._lib.gbp_ba_retire(self._h, ids.size, iptr(ids) if ids.size else None, iptr(cm), iptr(lm), iptr(fm)))
-        self.C, self.L, self.F = int((cm >= 0).sum()), int((lm >= 0).sum()), int((fm >= 0).sum())
-        return cm, lm, fm
+        return self._shrink(self._lib.gbp_ba_retire, cam_ids)
 
-    # ---- culling (include/gbp_ba.h: gbp_ba_cull) --------------------------------------------------
     def cull(self, factor_ids):
         """Remove single observations (factor ids in reference order): both messages of every listed factor are discarded -- nothing is
         folded into any prior, an outlier's information vanishes -- cameras and landmarks left without a factor are removed and the
         survivors are renumbered compactly with all their solver state.  Returns (cam_map, lmk_map, factor_map) as retire does."""
-        ids = i32(np.asarray(factor_ids, dtype=np.int64).reshape(-1))
-        cm, lm, fm = np.empty(self.C, np.int32), np.empty(self.L, np.int32), np.empty(self.F, np.int32)
-        check(self._lib.gbp_ba_cull(self._h, ids.size, iptr(ids) if ids.size else None, iptr(cm), iptr(lm), iptr(fm)))
-        self.C, self.L, self.F = int((cm >= 0).sum()), int((lm >= 0).sum()), int((fm >= 0).sum())
-        return cm, lm, fm
+        return self._shrink(self._lib.gbp_ba_cull, factor_ids)
 
-    # ---- letting go of landmarks (include/gbp_ba.h: gbp_ba_retire_landmarks) -----------------------
     def retire_landmarks(self, lmk_ids, fold=True):
         """Retire landmarks by name (ids in the caller's numbering).  fold=True (the landmarks were good): their factors' messages to the
         cameras are folded into the cameras' priors; fold=False (the landmarks were bad): the messages are discarded, as cull of exactly
         those factors does.  The landmarks, their factors and every camera and landmark left without a factor are removed and the survivors
         are renumbered compactly with all their solver state.  Returns (cam_map, lmk_map, factor_map) as retire does."""
-        ids = i32(np.asarray(lmk_ids, dtype=np.int64).reshape(-1))
-        cm, lm, fm = np.empty(self.C, np.int32), np.empty(self.L, np.int32), np.empty(self.F, np.int32)
-        mode = _capi.RETIRE_FOLD if fold else _capi.RETIRE_DROP
-        check(self._lib.gbp_ba_retire_landmarks(self._h, ids.size, iptr(ids) if ids.size else None, mode, iptr(cm), iptr(lm), iptr(fm)))
-        self.C, self.L, self.F = int((cm >= 0).sum()), int((lm >= 0).sum()), int((fm >= 0).sum())
-        return cm, lm, fm
+        return self._shrink(self._lib.gbp_ba_retire_landmarks, lmk_ids, _capi.RETIRE_FOLD if fold else _capi.RETIRE_DROP)
 
     def cull_outliers(self, nstds):
         """Cull every factor whose residual at the current belief means exceeds nstds standard deviations (||r|| / gauss_noise_std >

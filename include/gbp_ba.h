@@ -121,7 +121,9 @@ int gbp_ba_sync(gbp_ba_t *h);
  * Errors leave the handle untouched (the union is built beside it and swapped in at the end): GBP_ESTATE for a handle with a
  * communicator, an exchange callback or a peer mailbox (sharded growth is not supported) or without beliefs yet; GBP_EINVAL for ids
  * out of range, negative counts, NULL arrays with a non-zero count or sizes gbp_ba_create would reject; GBP_ENOMEM when the union
- * does not fit -- peak device memory is the old handle's plus the union's.  old_to_new (NULL to skip) receives F_old entries. */
+ * does not fit -- peak device memory is the old handle's plus the union's.  old_to_new (NULL to skip) receives F_old entries.
+ * One check of a batch serves this call and gbp_ba_window_step: beside the three single int32 limits, (C+dC) + (L+dL) + (F+dF) must
+ * stay below INT32_MAX and C+dC below 2^24 (GBP_EINVAL; no handle that fits a device comes near either). */
 typedef struct gbp_ba_ext {
     int32_t n_new_cams, n_new_lmks, n_new_factors;   /* dC, dL, dF (any may be 0) */
     int32_t flags;                                   /* GBP_FLAG_DEVICE_INPUT allowed (the five arrays below are then device pointers) */

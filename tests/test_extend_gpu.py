@@ -481,3 +481,211 @@ def test_compat_graph_grows(lib):
         assert list(f.adj_vIDs) == [int(fac['cam'][i]), len(g.cam_nodes) + int(fac['lmk'][i])]
     np.testing.assert_array_equal(g.cam_nodes[11].mu, e.means()[0][11])
     g.synchronous_iteration()
+
+
+# ---- 9. where a rebuild that lets nothing go and one that can let things go could part ---------------------------------------------------
+# (window_host.base_case()'s 16-camera base; default and landmark-reordered handles, the sweep forced fused and forced general)
+HANDLES = pytest.mark.parametrize('reorder,fused', [(False, True), (False, False), (True, True), (True, False)])
+CAM_LAMBDA, LMK_LAMBDA = np.array([2.0, 5.0]), np.array([1.0, 1.5, 3.0])
+
+
+@pytest.fixture(scope='module')
+def case():
+    from window_host import base_case
+    return base_case()
+
+
+def _host_messages(nb):
+    fs = nb.graph.factors
+    return (np.array([f.messages[0].eta for f in fs]), np.array([f.messages[0].lam for f in fs]),
+            np.array([f.messages[1].eta for f in fs]), np.array([f.messages[1].lam for f in fs]))
+
+
+def _host_grown(problem, batch, sweeps, **prior_kw):
+    """The reference's object graph after `sweeps` sweeps and one extend: (old_to_new, beliefs, messages)."""
+    nb = make_numpy_ba(problem, loss='huber')
+    nb.generate_priors_var(W)
+    nb.update_all_beliefs()
+    nb.iterate(sweeps)
+    o2n = host_extend(nb, batch, **prior_kw)
+    return o2n, nb.beliefs(), _host_messages(nb)
+
+
+@pytest.fixture(scope='module')
+def host_bare_new(case):
+    from extend_cases import bare_new_batch
+    b = bare_new_batch(case.base)
+    return b, _host_grown(case.base, b, 3, cam_prior_lambda=CAM_LAMBDA, lmk_prior_lambda=LMK_LAMBDA)
+
+
+@HANDLES
+def test_new_variables_without_a_factor_stay(lib, case, host_bare_new, reorder, fused):
+    """Two new cameras and three new landmarks, camera C + 1 and landmark L + 2 named by no factor of the batch (scalars for the priors:
+    the rule gives such a variable Lambda = 0): both are in the union, with prior lambda I, lambda mu and a belief that is the prior."""
+    b, (o2n_h, bel_h, msg_h) = host_bare_new
+    e = _engine(case.base, loss='huber', fused=fused, reorder_landmarks=reorder)
+    e.iterate(3)
+    C, L, F = e.C, e.L, e.F
+    o2n = _ext(e, b, cam_prior_lambda=CAM_LAMBDA, lmk_prior_lambda=LMK_LAMBDA)
+    np.testing.assert_array_equal(o2n, o2n_h)
+    assert (e.C, e.L, e.F) == (C + 2, L + 3, F + b['meas'].shape[0]) and e.check_layout() == 0
+    ce, cl, le, ll = e.priors()
+    cm, lm = e.means()
+    # lambda I is exact, lambda mu one product (1 ulp), the mean one solve with lambda I
+    np.testing.assert_array_equal(cl[C + 1], CAM_LAMBDA[1] * np.eye(6))
+    np.testing.assert_array_equal(ll[L + 2], LMK_LAMBDA[2] * np.eye(3))
+    np.testing.assert_allclose(ce[C + 1], CAM_LAMBDA[1] * b['cam_means'][1], rtol=1e-15, atol=0)
+    np.testing.assert_allclose(le[L + 2], LMK_LAMBDA[2] * b['lmk_means'][2], rtol=1e-15, atol=0)
+    np.testing.assert_allclose(cm[C + 1], b['cam_means'][1], rtol=1e-12, atol=0)
+    np.testing.assert_allclose(lm[L + 2], b['lmk_means'][2], rtol=1e-12, atol=0)
+    bel = e.beliefs()
+    for k, (pri, v) in enumerate(((ce, C + 1), (cl, C + 1), (le, L + 2), (ll, L + 2))):
+        np.testing.assert_allclose(bel[k][v], pri[v], rtol=1e-12, atol=1e-15)
+    worst = max([rel_err_rows(a, h) for a, h in zip(bel, bel_h)] + [rel_err_rows(a, h) for a, h in zip(e.messages(), msg_h)])
+    print(f'bare new variables (reorder={reorder}, fused={fused}): worst belief / message gap to the host graph {worst:.3e}')
+    assert worst < 1e-7, worst
+    e.iterate(3)
+    assert all(np.isfinite(x).all() for x in e.beliefs())
+    e.close()
+
+
+@HANDLES
+@pytest.mark.parametrize('named', [True, False])
+def test_an_old_camera_without_a_factor_stays(lib, case, reorder, fused, named):
+    """window_host.bare_camera_problem(): camera 8 has no factor (its prior set by hand, as tools/rebuild_digest.py does).  Extend by
+    base_case()'s batch -- which brings late observations of camera 8 (named) -- and by that batch without them: the camera keeps its
+    id and its prior, and its belief is its prior (a new factor's messages are zero)."""
+    from window_host import bare_camera_problem
+    from gbp_amd.engine import BAEngine
+    p, bare = bare_camera_problem(), 8
+    e = BAEngine.from_problem(p, loss='huber', fused=fused, reorder_landmarks=reorder)
+    e.generate_priors_var(W)
+    pr = e.priors()
+    lam = pr[1][:, 0, 0].max()
+    pr[1][bare], pr[0][bare] = lam * np.eye(6), lam * p.cam_means[bare]
+    e.set_priors(*pr)
+    e.update_all_beliefs()
+    e.iterate(3)
+    b = case.batch
+    assert (b['cam_idx'] == bare).any()
+    if not named:
+        ok = b['cam_idx'] != bare
+        b = dict(b, meas=b['meas'][ok], cam_idx=b['cam_idx'][ok], lmk_idx=b['lmk_idx'][ok])
+    before, C, L, F = _state(e), e.C, e.L, e.F
+    o2n = _ext(e, b, prior_weaker_factor=W)
+    assert (e.C, e.L, e.F) == (C + 2, L + b['lmk_means'].shape[0], F + b['meas'].shape[0]) and e.check_layout() == 0
+    assert ((e.factors(dense=False)['cam'] == bare).sum() > 0) == named
+    after = _state(e)
+    for k in range(4):
+        assert _bitwise(after['msg'][k][o2n], before['msg'][k])
+    for k, n in zip(range(4), (C, C, L, L)):
+        assert _bitwise(after['pri'][k][:n], before['pri'][k])
+    for k in range(2):
+        assert _bitwise(after['pri'][k][bare], pr[k][bare])
+        np.testing.assert_allclose(after['bel'][k][bare], pr[k][bare], rtol=1e-12, atol=1e-15)
+    np.testing.assert_allclose(e.means()[0][bare], p.cam_means[bare], rtol=1e-12, atol=0)
+    e.iterate(3)
+    assert all(np.isfinite(x).all() for x in e.beliefs())
+    e.close()
+
+
+@HANDLES
+def test_late_factors_of_old_cameras_move_old_ids(lib, case, reorder, fused):
+    """No new variable, new factors between old ones only, one of camera 0's: every old factor behind camera 0's moves up
+    (include/gbp_ba.h: old + the new factors of a lower camera), and carries its messages and linearisation point bit for bit."""
+    from extend_cases import old_only_batch
+    b = old_only_batch(case.base)
+    e = _engine(case.base, loss='huber', fused=fused, reorder_landmarks=reorder)
+    e.iterate(4)
+    before, C, L, F = _state(e), e.C, e.L, e.F
+    o2n = _ext(e, b, prior_weaker_factor=W)
+    assert (e.C, e.L, e.F) == (C, L, F + b['meas'].shape[0])
+    below = np.cumsum(np.bincount(b['cam_idx'], minlength=C))           # new factors of cameras <= c
+    cam = before['fac']['cam']
+    expect = np.arange(F) + np.where(cam > 0, below[np.maximum(cam, 1) - 1], 0)
+    np.testing.assert_array_equal(o2n, expect)
+    assert (o2n != np.arange(F)).sum() == (cam > 0).sum() > 0
+    after = _state(e)
+    for k in range(4):
+        assert _bitwise(after['msg'][k][o2n], before['msg'][k])
+        assert _bitwise(after['pri'][k], before['pri'][k])
+    for key in ('linpoint', 'z', 'cam', 'lmk'):
+        assert _bitwise(after['fac'][key][o2n], before['fac'][key])
+    for key in ('iters_since_relin', 'eta_damping', 'adaptive_var', 'robust_flag'):
+        assert _bitwise(after['rs'][key][o2n], before['rs'][key])
+    e.close()
+
+
+@HANDLES
+def test_the_smallest_graphs_grow(lib, reorder, fused):
+    """One camera, one landmark, one factor grows by one more of each (the new camera sees the old landmark, the new landmark nothing)."""
+    from extend_cases import smallest_case
+    base, b, _ = smallest_case()
+    lam = np.array([2.0])
+    e = _engine(base, fused=fused, reorder_landmarks=reorder)
+    e.iterate(2)
+    nb = make_numpy_ba(base)
+    nb.generate_priors_var(W)
+    nb.update_all_beliefs()
+    nb.iterate(2)
+    n0 = e.rebuild_count()
+    o2n = _ext(e, b, prior_weaker_factor=W, lmk_prior_lambda=lam)
+    np.testing.assert_array_equal(o2n, host_extend(nb, b, prior_weaker_factor=W, lmk_prior_lambda=lam))
+    np.testing.assert_array_equal(o2n, [0])
+    assert (e.C, e.L, e.F) == (2, 2, 2) and e.rebuild_count() == n0 + 1 and e.check_layout() == 0
+    worst = max([rel_err_rows(a, h) for a, h in zip(e.beliefs(), nb.beliefs())] + [rel_err_rows(a, h) for a, h in zip(e.messages(), _host_messages(nb))])
+    assert worst < 1e-7, worst
+    np.testing.assert_array_equal(e.priors()[3][1], 2.0 * np.eye(3))
+    e.iterate(3)
+    assert all(np.isfinite(x).all() for x in e.beliefs())
+    e.close()
+
+
+@pytest.mark.parametrize('fused', [True, False])
+def test_bad_id_in_a_device_batch_leaves_a_reordered_handle_untouched(lib, case, fused):
+    import torch
+    a, twin = (_engine(case.base, loss='huber', fused=fused, reorder_landmarks=True) for _ in range(2))
+    for e in (a, twin):
+        e.iterate(3)
+    b = case.batch
+    bad = dict(b, lmk_idx=b['lmk_idx'].copy())
+    bad['lmk_idx'][3] = a.L + b['lmk_means'].shape[0]        # one past the union's landmarks
+    t = {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in bad.items()}
+    torch.cuda.synchronize()
+    with pytest.raises(lib.GbpError) as ei:
+        a.extend(t['cam_means'].data_ptr(), t['lmk_means'].data_ptr(), t['meas'].data_ptr(), t['cam_idx'].data_ptr(), t['lmk_idx'].data_ptr(),
+                 device_pointers=(b['cam_means'].shape[0], b['lmk_means'].shape[0], b['meas'].shape[0]))
+    assert ei.value.code == -1
+    assert (a.C, a.L, a.F) == (twin.C, twin.L, twin.F)
+    a.iterate(3)
+    twin.iterate(3)
+    assert _bitwise(a.save_state(), twin.save_state())
+    for x, y in zip(a.beliefs(), twin.beliefs()):
+        assert _bitwise(x, y)
+    a.close()
+    twin.close()
+
+
+@HANDLES
+def test_a_handle_created_without_a_factor_grows(lib, reorder, fused):
+    """One camera and one landmark with no observation (priors by hand: the rule has nothing to go by) take smallest_case()'s batch."""
+    from extend_cases import smallest_case
+    from gbp_amd.engine import BAEngine
+    _, b, bare = smallest_case()
+    lam = np.array([2.0])
+    e = BAEngine.from_problem(bare, fused=fused, reorder_landmarks=reorder)
+    assert (e.C, e.L, e.F) == (1, 1, 0)
+    e.set_priors(3.0 * bare.cam_means, 3.0 * np.eye(6)[None], 4.0 * bare.lmk_means, 4.0 * np.eye(3)[None])
+    e.update_all_beliefs()
+    pr = e.priors()
+    o2n = _ext(e, b, prior_weaker_factor=W, lmk_prior_lambda=lam)
+    assert o2n.size == 0 and (e.C, e.L, e.F) == (2, 2, 1) and e.check_layout() == 0
+    fac = e.factors(dense=False)
+    assert (int(fac['cam'][0]), int(fac['lmk'][0])) == (1, 0) and _bitwise(fac['z'][0], b['meas'][0])
+    after = e.priors()
+    for k in range(4):
+        assert _bitwise(after[k][0], pr[k][0])
+    np.testing.assert_array_equal(after[3][1], 2.0 * np.eye(3))
+    e.iterate(3)
+    assert all(np.isfinite(x).all() for x in e.beliefs())
+    e.close()

@@ -3,9 +3,10 @@
 
 Prints one JSON object per scenario (--out PATH: also written there, one per line): the maps the call returned, save_state() directly
 after it and save_state() after three more sweeps.  The graph, the batch and the lists are tests/window_host.py's base_case(); the calls:
-cull, retire, retire_landmarks (fold / drop), the full window_step, extend; each on a default handle (loss='huber', 6 sweeps), on a
-handle created with landmark reordering, and on one whose dense remainder is on (num_undamped_iters=0, 9 sweeps); and retire([0]) on
-bare_camera_problem(), where a camera has no factor."""
+cull, retire, retire_landmarks (fold / drop), the full window_step, extend, and extend by tests/extend_cases.py's batches (extend_bare_new:
+new variables no batch factor names, priors from scalars; extend_old_only: late factors of old cameras and no new variable); each on a
+default handle (loss='huber', 6 sweeps), on a handle created with landmark reordering, and on one whose dense remainder is on
+(num_undamped_iters=0, 9 sweeps); and retire([0]) and extend on bare_camera_problem(), where a camera has no factor."""
 import hashlib
 import json
 import os
@@ -25,8 +26,11 @@ def sha(a):
 def main():
     from gbp_amd import _capi
     from gbp_amd.engine import BAEngine
+    from extend_cases import bare_new_batch, old_only_batch
     from window_host import bare_camera_problem, base_case
     c = base_case()
+    five = lambda b: (b['cam_means'], b['lmk_means'], b['meas'], b['cam_idx'], b['lmk_idx'])
+    bare_new, old_only = five(bare_new_batch(c.base)), five(old_only_batch(c.base))
     bt = (c.batch['cam_means'], c.batch['lmk_means'], c.batch['meas'], c.batch['cam_idx'], c.batch['lmk_idx'])
     calls = {
         'cull': lambda e: e.cull(c.cull),
@@ -35,6 +39,8 @@ def main():
         'retire_landmarks_drop': lambda e: e.retire_landmarks(c.lmks, fold=False),
         'window_step': lambda e: e.window_step(cull=c.cull, retire=c.retire, retire_landmarks=c.lmks, batch=bt, prior_weaker_factor=W),
         'extend': lambda e: (e.extend(*bt, prior_weaker_factor=W),),
+        'extend_bare_new': lambda e: (e.extend(*bare_new, cam_prior_lambda=[2.0, 5.0], lmk_prior_lambda=[1.0, 1.5, 3.0]),),
+        'extend_old_only': lambda e: (e.extend(*old_only, prior_weaker_factor=W),),
     }
     handles = {'default': (dict(loss='huber'), 6), 'reordered': (dict(loss='huber', reorder_landmarks=True), 6),
                'dense_remainder': (dict(num_undamped_iters=0), 9)}
@@ -64,6 +70,7 @@ def main():
         for cname, call in calls.items():
             lines.append(record(f'{hname}/{cname}', live(c.base, kw, sweeps), call))
     lines.append(record('bare_camera/retire', live(bare_camera_problem(), dict(loss='huber'), 6, bare=8), lambda e: e.retire([0])))
+    lines.append(record('bare_camera/extend', live(bare_camera_problem(), dict(loss='huber'), 6, bare=8), calls['extend']))
     print('\n'.join(lines))
     if '--out' in sys.argv:
         with open(sys.argv[sys.argv.index('--out') + 1], 'w') as f:
