@@ -176,6 +176,8 @@ SIGNATURES = {
     'gbp_lin_relinearise': (ct.c_int, [ct.c_void_p, _ip]),
     'gbp_lin_iterate_nonlinear': (ct.c_int, [ct.c_void_p, ct.c_int32, _ip]),
     'gbp_lin_get_linearisation': (ct.c_int, [ct.c_void_p, _dp, _ip, _dp]),
+    'gbp_lin_extend_nonlinear': (ct.c_int, [ct.c_void_p, ct.c_void_p]),
+    'gbp_lin_shrink_nonlinear': (ct.c_int, [ct.c_void_p, ct.c_void_p]),
     'gbp_ba_get_lmk_order': (ct.c_int, [ct.c_void_p, _ip]),
     'gbp_ba_fused_max_cams': (ct.c_int, []),
     'gbp_ba_plan_info': (ct.c_int, [ct.c_void_p, _ip, ct.c_int32]),
@@ -236,6 +238,12 @@ class LinNonlinear(ct.Structure):
     """gbp_lin_nonlinear_desc_t (include/gbp_lin.h)."""
     _fields_ = [('model', ct.c_int32), ('num_undamped_iters', ct.c_int32), ('min_linear_iters', ct.c_int32), ('reserved', ct.c_int32),
                 ('beta', ct.c_double), ('measurement', _dp), ('sqrt_info', _dp)]
+
+
+class LinExtNonlinear(ct.Structure):
+    """gbp_lin_extend_nonlinear_desc_t (include/gbp_lin.h)."""
+    _fields_ = [('n_new_vars', ct.c_int32), ('n_new_factors', ct.c_int32), ('var_a', _ip), ('var_b', _ip),
+                ('measurement', _dp), ('sqrt_info', _dp), ('prior_eta', _dp), ('prior_lam', _dp)]
 
 
 LIN_MODEL_SE2_BETWEEN = 1                           # GBP_LIN_MODEL_* (include/gbp_lin.h)

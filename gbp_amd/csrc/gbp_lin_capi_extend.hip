@@ -7,6 +7,10 @@
 // new generation (lin_gen_commit, gbp_lin_generation.hpp) and, where the handle had beliefs, run the belief stage over all variables.
 // A failure before the commit frees what was allocated and leaves the handle as it was.  Host work and host <-> device traffic are
 // proportional to dN and dF; no existing array crosses to the host.
+//
+// gbp_lin_extend_nonlinear is the same call on a handle of gbp_lin_set_nonlinear: the same build with zero eta_f, Lambda_f for the new
+// factors and the five per-factor arrays of LinNonlin re-strided with the rest, the same commit, the belief stage, and then
+// compute_factor (gbp.py:267-294) over the new factors alone (lin_nonlin_linearise, gbp_lin_capi_nonlin.hip).
 #include "gbp_lin_extend.hpp"
 #include "gbp_lin_generation.hpp"
 
@@ -26,7 +30,7 @@ namespace {
 // every path, a failure in the middle of ext_build included
 struct ExtHost {
     std::vector<int> a, b, loss;
-    std::vector<double> feta, flam, fconst, prior, thr, nvar;
+    std::vector<double> feta, flam, fconst, prior, thr, nvar, meas, sinfo;
 };
 
 template <typename T>
@@ -48,8 +52,10 @@ void ext_restride(gbp_lin *h, const T *src, const T *tail, T *dst, int rows, int
 
 int ext_blocks(size_t n) { return (int)((n + EXT_BLOCK - 1) / EXT_BLOCK); }
 
-// everything up to and including the synchronisation after which nothing can fail: the new arrays, built on the device
-int ext_build(gbp_lin *h, const gbp_lin_extend_desc_t *d, bool robust, LinScratch &mem, ExtHost &host, LinGen &n)
+// everything up to and including the synchronisation after which nothing can fail: the new arrays, built on the device.  nl: the
+// descriptor of gbp_lin_extend_nonlinear, whose sizes, ends and priors `d` repeats; its factors arrive as measurements, eta_f and
+// Lambda_f start at zero (the linearise pass after the commit writes them) and so does const_f where the handle has one
+int ext_build(gbp_lin *h, const gbp_lin_extend_desc_t *d, const gbp_lin_extend_nonlinear_desc_t *nl, bool robust, LinScratch &mem, ExtHost &host, LinGen &n)
 {
     const LinParams &p = h->p;
     const int D = h->D, D2 = 2 * D, P = D * (D + 1) / 2, P2 = D * (2 * D + 1), R = D + P, REC = D + P + D;
@@ -59,9 +65,19 @@ int ext_build(gbp_lin *h, const gbp_lin_extend_desc_t *d, bool robust, LinScratc
     std::vector<int> &ha = host.a, &hb = host.b, &hloss = host.loss;
     std::vector<double> &hfeta = host.feta, &hflam = host.flam, &hfconst = host.fconst, &hprior = host.prior, &hthr = host.thr, &hnvar = host.nvar;
     ha.assign(d->var_a, d->var_a + dF); hb.assign(d->var_b, d->var_b + dF);
-    hfeta.resize((size_t)D2 * dF); hflam.resize((size_t)P2 * dF); hprior.resize((size_t)dN * R);
-    lin_pack_factors(D, dF, d->factor_eta, d->factor_lam, hfeta.data(), hflam.data());
-    if (h->has_const) hfconst.assign(d->factor_const, d->factor_const + dF);
+    hprior.resize((size_t)dN * R);
+    if (!nl) {
+        hfeta.resize((size_t)D2 * dF); hflam.resize((size_t)P2 * dF);
+        lin_pack_factors(D, dF, d->factor_eta, d->factor_lam, hfeta.data(), hflam.data());
+        if (h->has_const) hfconst.assign(d->factor_const, d->factor_const + dF);
+    } else {                                                // SoA rows [3][dF], as gbp_lin_set_nonlinear packs the whole
+        host.meas.resize((size_t)NL_M * dF); host.sinfo.resize((size_t)NL_M * dF);
+        for (int f = 0; f < dF; ++f)
+            for (int k = 0; k < NL_M; ++k) {
+                host.meas[(size_t)k * dF + f] = nl->measurement[(size_t)f * NL_M + k];
+                host.sinfo[(size_t)k * dF + f] = nl->sqrt_info[(size_t)f * NL_M + k];
+            }
+    }
     lin_pack_priors(D, dN, d->prior_eta, d->prior_lam, hprior.data());
     if (robust && d->loss && dF) {
         hloss.assign(d->loss, d->loss + dF);
@@ -72,14 +88,16 @@ int ext_build(gbp_lin *h, const gbp_lin_extend_desc_t *d, bool robust, LinScratc
         }
     }
     const int *ta = nullptr, *tb = nullptr, *tloss = nullptr;
-    const double *tfeta = nullptr, *tflam = nullptr, *tfconst = nullptr, *tthr = nullptr, *tnvar = nullptr;
+    const double *tfeta = nullptr, *tflam = nullptr, *tfconst = nullptr, *tthr = nullptr, *tnvar = nullptr, *tmeas = nullptr, *tsinfo = nullptr;
     LCHK(ext_upload(h, mem, &ta, ha)); LCHK(ext_upload(h, mem, &tb, hb));
-    LCHK(ext_upload(h, mem, &tfeta, hfeta)); LCHK(ext_upload(h, mem, &tflam, hflam));
-    if (h->has_const) LCHK(ext_upload(h, mem, &tfconst, hfconst));
+    if (!nl) {
+        LCHK(ext_upload(h, mem, &tfeta, hfeta)); LCHK(ext_upload(h, mem, &tflam, hflam));
+        if (h->has_const) LCHK(ext_upload(h, mem, &tfconst, hfconst));
+    } else { LCHK(ext_upload(h, mem, &tmeas, host.meas)); LCHK(ext_upload(h, mem, &tsinfo, host.sinfo)); }
     if (!hloss.empty()) { LCHK(ext_upload(h, mem, &tloss, hloss)); LCHK(ext_upload(h, mem, &tthr, hthr)); LCHK(ext_upload(h, mem, &tnvar, hnvar)); }
 
     // ---- every allocation of the call, before the first kernel ----
-    LCHK(lin_gen_alloc(h, mem, n, N1, F1, robust, true));     // d_red grows when ceil(F / 256) does
+    LCHK(lin_gen_alloc(h, mem, n, N1, F1, robust, true, nl != nullptr));     // d_red grows when ceil(F / 256) does
     int *keys = nullptr, *vals = nullptr, *keys_s = nullptr, *vals_s = nullptr, *enew = nullptr;
     void *sort_tmp = nullptr;
     int bits = 1;
@@ -103,6 +121,12 @@ int ext_build(gbp_lin *h, const gbp_lin_extend_desc_t *d, bool robust, LinScratc
         ext_restride<double>(h, old ? h->rob.nvar : nullptr, tnvar, n.nvar, 1, F, dF, 1.0);
         ext_restride<double>(h, old ? h->rob.w : nullptr, nullptr, n.w, 1, F, dF, 1.0);
         ext_restride<int>(h, old ? h->rob.flag : nullptr, nullptr, n.flag, 1, F, dF, 0);
+    }
+    if (nl) {
+        // the old factors' rows as they are; the new factors' linpoint, iters and damping hold a fill until the linearise pass
+        ext_restride<double>(h, h->nl.meas, tmeas, n.meas, NL_M, F, dF, 0.0); ext_restride<double>(h, h->nl.sinfo, tsinfo, n.sinfo, NL_M, F, dF, 1.0);
+        ext_restride<double>(h, h->nl.linpoint, nullptr, n.linpoint, 2 * NL_D, F, dF, 0.0);
+        ext_restride<int>(h, h->nl.iters, nullptr, n.iters, 1, F, dF, 1); ext_restride<double>(h, h->nl.fdamp, nullptr, n.fdamp, 1, F, dF, 0.0);
     }
     LHIPCHK(hipGetLastError());
     // ---- variable-strided records: the old ones as they are, the new priors behind them; new belief records start at zero ----
@@ -141,15 +165,16 @@ int ext_build(gbp_lin *h, const gbp_lin_extend_desc_t *d, bool robust, LinScratc
     return GBP_OK;
 }
 
-int ext_validate(gbp_lin *h, const gbp_lin_extend_desc_t *d)
+// nl: the call is gbp_lin_extend_nonlinear, whose factors arrive as measurements (checked by its entry point), not as eta_f, Lambda_f
+int ext_validate(gbp_lin *h, const gbp_lin_extend_desc_t *d, bool nl)
 {
     const int N = h->p.N, F = h->p.F, dN = d->n_new_vars, dF = d->n_new_factors;
     if (dN < 0 || dF < 0) return set_error(GBP_EINVAL, "negative size");
     if ((long long)N + dN > INT_MAX - 1) return set_error(GBP_EINVAL, "%d + %d variables do not fit int32", N, dN);
     if (2LL * ((long long)F + dF) > INT_MAX) return set_error(GBP_EINVAL, "%d + %d factors: 2 F must fit int32 (an adjacency entry is factor << 1 | side)", F, dF);
-    if ((dF && (!d->var_a || !d->var_b || !d->factor_eta || !d->factor_lam)) || (dN && (!d->prior_eta || !d->prior_lam)))
+    if ((dF && (!d->var_a || !d->var_b || (!nl && (!d->factor_eta || !d->factor_lam)))) || (dN && (!d->prior_eta || !d->prior_lam)))
         return set_error(GBP_EINVAL, "NULL array in the descriptor");
-    if (dF && h->has_const != (d->factor_const != nullptr))
+    if (!nl && dF && h->has_const != (d->factor_const != nullptr))
         return set_error(GBP_EINVAL, h->has_const ? "the handle was created with factor_const: the new factors need theirs"
                                                   : "the handle was created without factor_const: the new factors cannot have one");
     const int N1 = N + dN;
@@ -164,6 +189,25 @@ int ext_validate(gbp_lin *h, const gbp_lin_extend_desc_t *d)
         if ((any || !h->p.w) && !h->has_const)
             return set_error(GBP_EINVAL, "a loss needs the factors' constants: the handle was created with factor_const == NULL");
     }
+    return GBP_OK;
+}
+
+// what both entry points do once the descriptor is known to be good
+int ext_run(gbp_lin *h, const gbp_lin_extend_desc_t *d, const gbp_lin_extend_nonlinear_desc_t *nl, bool robust)
+{
+    LHIPCHK(hipStreamSynchronize(h->stream));
+    LinScratch mem;
+    ExtHost host;                                           // read by the stream until the synchronisation in ext_build, or the one below
+    LinGen n;
+    const int rc = ext_build(h, d, nl, robust, mem, host, n);
+    if (rc != GBP_OK) {                                     // the handle's arrays were only read: it goes on as it was
+        (void)hipStreamSynchronize(h->stream);              // before `mem` frees what the stream may still be writing
+        return rc;
+    }
+    lin_gen_commit(h, mem, n);
+    // beliefs of the grown graph (update_all_beliefs gbp.py:56-58): old variables add the same messages in the same order plus zeros,
+    // new ones hold their prior
+    if (h->has_beliefs) return gbp_lin_update_beliefs(h);
     return GBP_OK;
 }
 
@@ -184,25 +228,31 @@ int gbp_lin_extend(gbp_lin_t *h, const gbp_lin_extend_desc_t *d)
     LENTER(h);
     LIN_REFUSE_NONLINEAR(h, "gbp_lin_extend");
     if (!d) return set_error(GBP_EINVAL, "NULL descriptor");
-    LCHK(ext_validate(h, d));
-    const int dN = d->n_new_vars, dF = d->n_new_factors;
-    if (!dN && !dF) return GBP_OK;
+    LCHK(ext_validate(h, d, false));
+    if (!d->n_new_vars && !d->n_new_factors) return GBP_OK;
     // losses are on after the call if they are now, or if the new factors bring some
-    const bool robust = h->p.w != nullptr || (d->loss && dF);
-    LHIPCHK(hipStreamSynchronize(h->stream));
-    LinScratch mem;
-    ExtHost host;                                           // read by the stream until the synchronisation in ext_build, or the one below
-    LinGen n;
-    const int rc = ext_build(h, d, robust, mem, host, n);
-    if (rc != GBP_OK) {                                     // the handle's arrays were only read: it goes on as it was
-        (void)hipStreamSynchronize(h->stream);              // before `mem` frees what the stream may still be writing
-        return rc;
+    return ext_run(h, d, nullptr, h->p.w != nullptr || (d->loss && d->n_new_factors));
+}
+
+int gbp_lin_extend_nonlinear(gbp_lin_t *h, const gbp_lin_extend_nonlinear_desc_t *nl)
+{
+    LENTER(h);
+    if (!h->nonlinear) return set_error(GBP_ESTATE, "the handle has no nonlinear factors: call gbp_lin_set_nonlinear first, or gbp_lin_extend");
+    if (!nl) return set_error(GBP_EINVAL, "NULL descriptor");
+    gbp_lin_extend_desc_t d{};                              // sizes, ends and priors: the rules of gbp_lin_extend
+    d.n_new_vars = nl->n_new_vars; d.n_new_factors = nl->n_new_factors;
+    d.var_a = nl->var_a; d.var_b = nl->var_b; d.prior_eta = nl->prior_eta; d.prior_lam = nl->prior_lam;
+    LCHK(ext_validate(h, &d, true));
+    const int F = h->p.F, dF = nl->n_new_factors;
+    if (dF && (!nl->measurement || !nl->sqrt_info)) return set_error(GBP_EINVAL, "NULL array in the descriptor");
+    for (size_t i = 0; i < (size_t)dF * NL_M; ++i) {        // the rules of gbp_lin_set_nonlinear
+        if (!(nl->sqrt_info[i] > 0.0) || !std::isfinite(nl->sqrt_info[i])) return set_error(GBP_EINVAL, "new factor %d: sqrt_info must be positive and finite", (int)(i / NL_M));
+        if (!std::isfinite(nl->measurement[i])) return set_error(GBP_EINVAL, "new factor %d: the measurement must be finite", (int)(i / NL_M));
     }
-    lin_gen_commit(h, mem, n);
-    // beliefs of the grown graph (update_all_beliefs gbp.py:56-58): old variables add the same messages in the same order plus zeros,
-    // new ones hold their prior
-    if (h->has_beliefs) return gbp_lin_update_beliefs(h);
-    return GBP_OK;
+    if (!nl->n_new_vars && !dF) return GBP_OK;
+    LCHK(ext_run(h, &d, nl, false));                        // ends with the belief stage: a nonlinear handle has beliefs
+    // compute_factor on the new factors only (gbp.py:267-294), at the belief means as that stage left them; the joint is stale already
+    return lin_nonlin_linearise(h, F, F + dF);
 }
 
 }  // extern "C"

@@ -49,7 +49,19 @@ void nl_relin(gbp_lin *h, int mode, int *count)
 namespace gbp {
 int lin_nonlin_energy(gbp_lin *h, double *out)
 {
-    hipLaunchKernelGGL((k_lin_energy_nl<GBP_LIN_MODEL_SE2_BETWEEN>), dim3((h->p.F + 255) / 256), dim3(256), 0, h->stream, h->p, h->nl, out);
+    // over red_blocks blocks, as k_lin_energy: the caller adds up red_blocks partials, and after a shrink that is more than
+    // ceil(F / 256) (d_red stays with the handle) -- a block past F writes 0 over what an energy at the larger F left there
+    hipLaunchKernelGGL((k_lin_energy_nl<GBP_LIN_MODEL_SE2_BETWEEN>), dim3(h->red_blocks), dim3(256), 0, h->stream, h->p, h->nl, out);
+    return GBP_OK;
+}
+
+// compute_factor (gbp.py:267-294) on the factors [f0, f1) alone, at their adjacent belief means as the handle holds them: eta_f,
+// Lambda_f, linpoint, iters = 1, damping = 0 -- the lane code of compute_all_factors, over a launch sized by the range
+int lin_nonlin_linearise(gbp_lin *h, int f0, int f1)
+{
+    if (f1 <= f0) return GBP_OK;
+    hipLaunchKernelGGL((k_lin_relin_range<GBP_LIN_MODEL_SE2_BETWEEN>), dim3((f1 - f0 + 255) / 256), dim3(256), 0, h->stream, h->p, h->nl, NL_INIT, f0, f1);
+    LHIPCHK(hipGetLastError());
     return GBP_OK;
 }
 }  // namespace gbp

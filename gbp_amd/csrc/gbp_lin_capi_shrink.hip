@@ -8,6 +8,10 @@
 // gbp_lin_generation.hpp) and, where the handle had beliefs, run the belief stage over the survivors.  A failure before the commit
 // frees what was allocated and leaves the handle as it was.  Host work and host <-> device traffic are proportional to the two lists,
 // plus the maps where the caller asks for them; no existing array crosses to the host.
+//
+// gbp_lin_shrink_nonlinear is the same call on a handle of gbp_lin_set_nonlinear: the five per-factor arrays of LinNonlin are gathered
+// through the same list of survivors.  Nothing relinearises; a folded message is the one its factor computed at its last
+// linearisation point and is frozen in the prior from then on.
 #include "gbp_lin_shrink.hpp"
 #include "gbp_lin_generation.hpp"
 
@@ -79,10 +83,10 @@ int shr_build(gbp_lin *h, const gbp_lin_shrink_desc_t *d, bool robust, LinScratc
         return set_error(GBP_EHIP, "the scan of the keep flags gave %d variables, %d factors, %d edges from %d - %d and %d - %d", N1, F1, hs[2], N, nr, F, nd);
 
     // ---- every allocation of the new generation, before the first kernel that builds it ----
-    // d_red stays: it holds ceil(F / 256) >= max(1, ceil(F' / 256)) partials, and the energy's launch goes by red_blocks
+    // d_red stays: it holds ceil(F / 256) >= max(1, ceil(F' / 256)) partials, and the energy's launch goes by red_blocks (the nonlinear one too: lin_nonlin_energy)
     int *maps = nullptr, *surv_v = nullptr, *surv_f = nullptr;          // maps: [N | F] of before the call
     LCHK(mem.get(&maps, (size_t)N + F, false)); LCHK(mem.get(&surv_v, (size_t)N1, false)); LCHK(mem.get(&surv_f, (size_t)F1, false));
-    LCHK(lin_gen_alloc(h, mem, n, N1, F1, robust, false));
+    LCHK(lin_gen_alloc(h, mem, n, N1, F1, robust, false, h->nonlinear));
 
     // ---- the maps and the lists of survivors ----
     const int *ckeep = keep, *cpos = pos, *csurv = surv_f, *cmaps = maps;
@@ -99,6 +103,11 @@ int shr_build(gbp_lin *h, const gbp_lin_shrink_desc_t *d, bool robust, LinScratc
         shr_gather<int>(h, h->rob.loss, csurv, n.loss, 1, F, F1); shr_gather<double>(h, h->rob.thr, csurv, n.thr, 1, F, F1);
         shr_gather<double>(h, h->rob.nvar, csurv, n.nvar, 1, F, F1); shr_gather<double>(h, h->rob.w, csurv, n.w, 1, F, F1);
         shr_gather<int>(h, h->rob.flag, csurv, n.flag, 1, F, F1);
+    }
+    if (h->nonlinear) {
+        shr_gather<double>(h, h->nl.meas, csurv, n.meas, NL_M, F, F1); shr_gather<double>(h, h->nl.sinfo, csurv, n.sinfo, NL_M, F, F1);
+        shr_gather<double>(h, h->nl.linpoint, csurv, n.linpoint, 2 * NL_D, F, F1);
+        shr_gather<int>(h, h->nl.iters, csurv, n.iters, 1, F, F1); shr_gather<double>(h, h->nl.fdamp, csurv, n.fdamp, 1, F, F1);
     }
     LHIPCHK(hipGetLastError());
     // ---- the CSR of the survivors, the rows of vmsg with it ----
@@ -127,14 +136,9 @@ int shr_validate(gbp_lin *h, const gbp_lin_shrink_desc_t *d)
     return GBP_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int gbp_lin_shrink(gbp_lin_t *h, const gbp_lin_shrink_desc_t *d)
+// what both entry points do on a handle they accept
+int shr_run(gbp_lin *h, const gbp_lin_shrink_desc_t *d)
 {
-    LENTER(h);
-    LIN_REFUSE_NONLINEAR(h, "gbp_lin_shrink");
     if (!d) return set_error(GBP_EINVAL, "NULL descriptor");
     LCHK(shr_validate(h, d));
     if (!d->n_retire_vars && !d->n_drop_factors) {          // nothing leaves: the maps are the identity
@@ -155,6 +159,24 @@ int gbp_lin_shrink(gbp_lin_t *h, const gbp_lin_shrink_desc_t *d)
     // beliefs of the shrunk graph (update_all_beliefs gbp.py:56-58): the folded prior, then the surviving messages in adjacency order
     if (h->has_beliefs) return gbp_lin_update_beliefs(h);
     return GBP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gbp_lin_shrink(gbp_lin_t *h, const gbp_lin_shrink_desc_t *d)
+{
+    LENTER(h);
+    LIN_REFUSE_NONLINEAR(h, "gbp_lin_shrink");
+    return shr_run(h, d);
+}
+
+int gbp_lin_shrink_nonlinear(gbp_lin_t *h, const gbp_lin_shrink_desc_t *d)
+{
+    LENTER(h);
+    if (!h->nonlinear) return set_error(GBP_ESTATE, "the handle has no nonlinear factors: call gbp_lin_set_nonlinear first, or gbp_lin_shrink");
+    return shr_run(h, d);
 }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
-// gbp_lin_generation.hpp -- host code only: what gbp_lin_create, gbp_lin_extend and gbp_lin_shrink share.  Each of them builds a complete
+// gbp_lin_generation.hpp -- host code only: what gbp_lin_create, gbp_lin_extend and gbp_lin_shrink (and the two calls that grow and
+// shrink a nonlinear handle, gbp_lin_extend_nonlinear / gbp_lin_shrink_nonlinear) share.  Each of them builds a complete
 // new GENERATION of the handle's graph arrays while the old one is only read, synchronises, and commits:
 //   LinScratch       the device memory of one call: `keep` becomes the handle's at the commit, `temp` goes with the call
 //   LinGen           the arrays of one generation; lin_gen_alloc is the one place that says which they are and how large each is
@@ -29,7 +30,7 @@ struct LinScratch {
     static void release(std::vector<void *> &v) { for (void *q : v) (void)hipFree(q); v.clear(); }
 };
 
-// the arrays that replace the handle's (LinParams and LinRobust say what each holds)
+// the arrays that replace the handle's (LinParams, LinRobust and LinNonlin say what each holds)
 struct LinGen {
     int N = 0, F = 0;
     int *va = nullptr, *vb = nullptr, *vptr = nullptr, *vadj = nullptr, *epos_a = nullptr, *epos_b = nullptr;
@@ -39,11 +40,14 @@ struct LinGen {
     bool robust = false;                            // losses are set after the commit: the five arrays below exist
     int *loss = nullptr, *flag = nullptr;
     double *thr = nullptr, *nvar = nullptr, *w = nullptr;
+    bool nonlinear = false;                         // the handle is nonlinear: the five per-factor arrays below exist
+    double *meas = nullptr, *sinfo = nullptr, *linpoint = nullptr, *fdamp = nullptr;
+    int *iters = nullptr;
 };
 
 // Every array of a generation of N1 variables and F1 factors, nothing written yet.  grow_red: a larger d_red where ceil(F1 / 256)
-// exceeds what the handle has (a new handle has none).
-inline int lin_gen_alloc(gbp_lin *h, LinScratch &mem, LinGen &g, int N1, int F1, bool robust, bool grow_red)
+// exceeds what the handle has (a new handle has none).  nonlinear: the per-factor arrays of LinNonlin too (a nonlinear handle has d = 3).
+inline int lin_gen_alloc(gbp_lin *h, LinScratch &mem, LinGen &g, int N1, int F1, bool robust, bool grow_red, bool nonlinear = false)
 {
     const size_t D = (size_t)h->D, P = D * (D + 1) / 2, P2 = D * (2 * D + 1), R = D + P, REC = D + P + D, N = (size_t)N1, F = (size_t)F1;
     g.N = N1; g.F = F1; g.robust = robust;
@@ -62,6 +66,11 @@ inline int lin_gen_alloc(gbp_lin *h, LinScratch &mem, LinGen &g, int N1, int F1,
     if (robust) {
         LCHK(mem.get(&g.loss, F, true)); LCHK(mem.get(&g.thr, F, true)); LCHK(mem.get(&g.nvar, F, true));
         LCHK(mem.get(&g.w, F, true)); LCHK(mem.get(&g.flag, F, true));
+    }
+    g.nonlinear = nonlinear;
+    if (nonlinear) {
+        LCHK(mem.get(&g.meas, NL_M * F, true)); LCHK(mem.get(&g.sinfo, NL_M * F, true)); LCHK(mem.get(&g.linpoint, 2 * NL_D * F, true));
+        LCHK(mem.get(&g.iters, F, true)); LCHK(mem.get(&g.fdamp, F, true));
     }
     return GBP_OK;
 }
@@ -94,7 +103,9 @@ inline void lin_drop_solvers(gbp_lin *h)
 
 // The swap, after the synchronisation that ends the build of `g`: nothing here can fail.  The arrays that are replaced are freed and
 // taken out of `allocs` (a handle rebuilt a thousand times holds one generation) -- the robust ones of a handle whose losses were
-// cleared too: they are stale and not carried -- and the call's `temp` with them; `keep` becomes the handle's.
+// cleared too: they are stale and not carried -- and the call's `temp` with them; `keep` becomes the handle's.  A nonlinear handle's
+// five per-factor arrays go the same way, and LinNonlin::feta / flam -- what the relinearise stage writes -- are re-pointed at the new
+// generation's factor arrays: the old ones are freed here.  The per-sweep counts buffer does not depend on F and stays.
 inline void lin_gen_commit(gbp_lin *h, LinScratch &mem, const LinGen &g)
 {
     LinScratch::release(mem.temp);
@@ -105,6 +116,8 @@ inline void lin_gen_commit(gbp_lin *h, LinScratch &mem, const LinGen &g)
         lin_free(h, q);
     if (h->rob_alloc)
         for (const void *q : {(const void *)h->rob.loss, (const void *)h->rob.thr, (const void *)h->rob.nvar, (const void *)h->rob.w, (const void *)h->rob.flag}) lin_free(h, q);
+    if (g.nonlinear)
+        for (const void *q : {(const void *)h->nl.meas, (const void *)h->nl.sinfo, (const void *)h->nl.linpoint, (const void *)h->nl.iters, (const void *)h->nl.fdamp}) lin_free(h, q);
     lin_drop_solvers(h);
     if (g.d_red) { lin_free(h, h->d_red); h->d_red = g.d_red; h->red_blocks = g.red_blocks; }
     h->allocs.insert(h->allocs.end(), mem.keep.begin(), mem.keep.end());
@@ -115,6 +128,11 @@ inline void lin_gen_commit(gbp_lin *h, LinScratch &mem, const LinGen &g)
     p.w = g.robust ? g.w : nullptr;
     h->rob = g.robust ? LinRobust{g.loss, g.thr, g.nvar, g.w, g.flag} : LinRobust{};
     h->rob_alloc = g.robust;
+    if (g.nonlinear) {
+        LinNonlin &nl = h->nl;
+        nl.meas = g.meas; nl.sinfo = g.sinfo; nl.linpoint = g.linpoint; nl.iters = g.iters; nl.fdamp = g.fdamp;
+        nl.feta = g.feta; nl.flam = g.flam;
+    }
 }
 
 // ---- host routines without a HIP call (tests/hostmath/lin_pack_shim.hip runs them on a CPU) ----

@@ -11,7 +11,8 @@
 //                            the same stage kernels (parameter blocks LinGated / LinTraced below), and what is the call's alone
 //                            (gbp_lin_until.hpp)
 //   gbp_lin_capi_nonlin.hip  nonlinear pairwise factors relinearised on the device (kernels in gbp_lin_nonlin.hpp): the relinearise stage,
-//                            the factor stage with per-factor damping (parameter block LinRelin below), the model-aware energy
+//                            the factor stage with per-factor damping (parameter block LinRelin below), the model-aware energy; growing and
+//                            shrinking such a handle are gbp_lin_extend_nonlinear / gbp_lin_shrink_nonlinear in the extend / shrink units
 #pragma once
 #include "../../include/gbp_ba.h"
 #include "../../include/gbp_lin.h"
@@ -87,8 +88,11 @@ struct LinUntil {
 };
 
 // Nonlinear factors (gbp_lin_nonlin.hpp): device memory owned by gbp_lin::allocs, allocated by gbp_lin_set_nonlinear.  Everything
-// per-factor is SoA with stride F like the rest of the handle.  feta / flam are the handle's own factor arrays (LinParams::feta / flam),
-// writable: a nonlinear handle keeps its generation (gbp_lin_extend / gbp_lin_shrink are refused), so they stay valid.
+// per-factor is SoA with stride F like the rest of the handle, and travels with a generation: gbp_lin_extend_nonlinear /
+// gbp_lin_shrink_nonlinear rebuild the five per-factor arrays with the graph's, and lin_gen_commit (gbp_lin_generation.hpp) installs
+// them.  feta / flam are the handle's own factor arrays (LinParams::feta / flam), writable; the same commit re-points them.
+constexpr int NL_D = 3;                                   // dofs of a variable of every model so far
+constexpr int NL_M = 3;                                   // rows of a measurement
 struct LinNonlin {
     const double *meas, *sinfo;      // [3][F] measurement z, square-root information s
     double *linpoint;                // [6][F] Factor.linpoint gbp.py:231 = [xa; xb]
@@ -166,7 +170,8 @@ struct gbp_lin {
 namespace gbp {
 int lin_map_prepare(gbp_lin *h);                    // gbp_lin_capi_map.hip: LinMap's workspace (once per handle), LDL^T and joint eta (per set of weights)
 int lin_sweep(gbp_lin *h);                          // gbp_lin_capi.hip: one synchronous iteration at the weights as they stand, queued on the stream
-int lin_nonlin_energy(gbp_lin *h, double *out);     // gbp_lin_capi_nonlin.hip: one partial per block of 256 factors into `out`, queued on the stream
+int lin_nonlin_energy(gbp_lin *h, double *out);     // gbp_lin_capi_nonlin.hip: red_blocks partials (one per block of 256 factors, 0 past F) into `out` = d_red, queued on the stream
+int lin_nonlin_linearise(gbp_lin *h, int f0, int f1);   // gbp_lin_capi_nonlin.hip: compute_factor on the factors [f0, f1) at their belief means, queued
 }
 
 // the entry points that a nonlinear handle refuses (include/gbp_lin.h): decided before anything changes

@@ -9,8 +9,10 @@
 //   Lambda_f = J^T J,  eta_f = J^T (J x0 + diag(s) z - h(x0))                                      (gbp.py:280-289, noise variance 1)
 // Angles are never wrapped: the reference does not wrap, and the caller keeps theta continuous.
 //   nonlin_h<MODEL>, nonlin_factor<MODEL>   the model: h at a point; eta_f and packed-upper Lambda_f at a linearisation point
-//   k_lin_relin<MODEL>     one lane per factor: the test of gbp.py:75, the factor re-made where it passes, iters, and the damping
-//                          switch of gbp.py:50-51; the relinearised factors of a wave are counted by a popcount and ONE integer atomic add
+//   lin_relin_one<MODEL>   one lane, one factor: the test of gbp.py:75, the factor re-made where it passes, iters, and the damping
+//                          switch of gbp.py:50-51
+//   k_lin_relin<MODEL>     that over every factor; the relinearised factors of a wave are counted by a popcount and ONE integer atomic add
+//   k_lin_relin_range<MODEL>  that over a range of factors (the ones gbp_lin_extend_nonlinear appended), uncounted
 //   k_lin_energy_nl<MODEL> sum_f 0.5 |h(mu) - diag(s) z|^2 at the belief means, in the block / partials shape of k_lin_energy
 // The factor stage of such a sweep is k_lin_factor<3, false, LinRelin> (gbp_lin_sweep.hpp), instantiated in gbp_lin_capi_nonlin.hip.
 // The model routines are host/device, so a host program can run them.
@@ -19,9 +21,6 @@
 #include "gbp_math.hpp"
 
 namespace gbp {
-
-constexpr int NL_D = 3;                                   // dofs of a variable of every model so far
-constexpr int NL_M = 3;                                   // rows of a measurement
 
 // how k_lin_relin is run
 constexpr int NL_SWEEP = 0;                               // the stage of a sweep: test, iters, damping switch
@@ -91,15 +90,14 @@ GBP_HD void nonlin_factor(const double (&x)[6], const double (&z)[3], const doub
     }
 }
 
-// One lane per factor.  A lane that does not relinearise writes iters only (and its damping in the sweep in which that switches); a
-// relinearising lane writes the 6 + 21 doubles of the factor, the 6 of the linpoint, iters and its damping.  Lanes past F neither load nor
-// store.  `count`: the slot of this sweep (nullptr for NL_INIT): one integer atomic add per wave that relinearised anything.
+// The relinearise stage for factor f, one lane: shared by the two kernels below so that a factor linearised over a range comes out bit
+// for bit as one linearised with the whole graph.  A lane that does not relinearise writes iters only (and its damping in the sweep in
+// which that switches); a relinearising lane writes the 6 + 21 doubles of the factor, the 6 of the linpoint, iters and its damping.  A
+// lane that is not `live` neither loads nor stores.  Returns whether the factor was relinearised.
 template <int MODEL>
-__global__ __launch_bounds__(256) void k_lin_relin(LinParams p, LinNonlin n, int mode, int *count)
+GBP_DEV bool lin_relin_one(const LinParams &p, const LinNonlin &n, int mode, int f, bool live)
 {
     constexpr int D = NL_D, P = LinDims<D>::P, REC = LinDims<D>::REC;
-    const int f = blockIdx.x * 256 + threadIdx.x;
-    const bool live = f < p.F;
     const size_t F = (size_t)p.F;
     bool relin = false;
     if (live) {
@@ -132,10 +130,30 @@ __global__ __launch_bounds__(256) void k_lin_relin(LinParams p, LinNonlin n, int
         if (mode == NL_SWEEP && it == n.num_undamped) n.fdamp[f] = p.damping;
         else if (relin) n.fdamp[f] = 0.0;
     }
+    return relin;
+}
+
+// One lane per factor of the graph.  Lanes past F neither load nor store.  `count`: the slot of this sweep (nullptr for NL_INIT): one
+// integer atomic add per wave that relinearised anything.
+template <int MODEL>
+__global__ __launch_bounds__(256) void k_lin_relin(LinParams p, LinNonlin n, int mode, int *count)
+{
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    const bool relin = lin_relin_one<MODEL>(p, n, mode, f, f < p.F);
     if (count) {
         const unsigned long long who = __ballot(relin);
         if ((threadIdx.x & 63) == 0 && who) atomicAdd(count, __popcll(who));
     }
+}
+
+// The same stage over the factors [f0, f1) only, one lane per factor of the RANGE: what gbp_lin_extend_nonlinear runs in mode NL_INIT
+// on the factors it appended (compute_factor on the new factors, gbp.py:267-294).  Work and traffic go by f1 - f0, not by F; lanes
+// outside the range neither load nor store; no atomics.  `mode` stays a run-time argument so that the lane's code is k_lin_relin's.
+template <int MODEL>
+__global__ __launch_bounds__(256) void k_lin_relin_range(LinParams p, LinNonlin n, int mode, int f0, int f1)
+{
+    const int f = f0 + blockIdx.x * 256 + threadIdx.x;
+    (void)lin_relin_one<MODEL>(p, n, mode, f, f < f1);
 }
 
 // sum_f 0.5 |h(mu) - diag(s) z|^2 at the current belief means (gbp.py:36-44, 251-265): one partial per block, the lanes of a wave and

@@ -69,6 +69,7 @@ class LinearEngine:
         d.prior_eta, d.prior_lam = dptr(prior_eta), dptr(prior_lam)
         d.eta_damping = float(eta_damping)
         self._h = ct.c_void_p()
+        self._nonlinear = False                              # set_nonlinear was called: the handle grows by extend_se2, shrinks by gbp_lin_shrink_nonlinear
         check(self._lib.gbp_lin_create(ct.byref(self._h), ct.byref(d)))
 
     @classmethod
@@ -144,7 +145,9 @@ class LinearEngine:
         """Retire variables and drop factors on the device.  A factor leaves if it is listed or has a retired end; with fold=True a
         leaving factor that is not listed and has one surviving end adds its stored message to that end's prior (GBP's own
         marginalisation), otherwise its messages are dropped.  Survivors are renumbered monotonically and keep their messages; beliefs,
-        where the handle had them, are re-made; solve_map / marginals results are dropped until the next solve.
+        where the handle had them, are re-made; solve_map / marginals results are dropped until the next solve.  On an engine of
+        se2_pose_graph every survivor also keeps its linearisation point, iters_since_relin and damping, nothing relinearises, and a
+        folded message is the one its factor computed at its last linearisation point, frozen in the prior from then on.
         Returns (var_map, factor_map): int32 arrays over the ids of before the call, the new id or -1."""
         rv, df = i32(np.asarray(retire_vars, dtype=np.int64).reshape(-1)), i32(np.asarray(drop_factors, dtype=np.int64).reshape(-1))
         vmap, fmap = np.empty(max(self.N, 1), dtype=np.int32), np.empty(max(self.F, 1), dtype=np.int32)
@@ -153,7 +156,7 @@ class LinearEngine:
         d.n_drop_factors, d.drop_factors = df.shape[0], iptr(df)
         d.fold = int(fold)
         d.var_map, d.factor_map = iptr(vmap), iptr(fmap)
-        check(self._lib.gbp_lin_shrink(self._h, ct.byref(d)))
+        check((self._lib.gbp_lin_shrink_nonlinear if self._nonlinear else self._lib.gbp_lin_shrink)(self._h, ct.byref(d)))
         vmap, fmap = vmap[:self.N], fmap[:self.F]
         self.N, self.F = self.sizes()
         return vmap, fmap
@@ -244,6 +247,27 @@ class LinearEngine:
         s = f64(np.ascontiguousarray(np.broadcast_to(np.asarray(sqrt_info, dtype=np.float64), (self.F, 3))))
         d = _capi.LinNonlinear(int(model), int(num_undamped_iters), int(min_linear_iters), 0, float(beta), dptr(z), dptr(s))
         check(self._lib.gbp_lin_set_nonlinear(self._h, ct.byref(d)))
+        self._nonlinear = True
+
+    def extend_se2(self, var_a, var_b, measurement, sqrt_info, prior_eta=None, prior_lam=None):
+        """Append dN poses (their priors: ids N .. N + dN - 1; put the odometry prediction there) and dF relative-pose factors (ids
+        F .. F + dF - 1, joining any poses old or new) to an engine of se2_pose_graph, on the device.  Every old factor keeps its
+        messages, linearisation point, iters_since_relin and damping; nothing relinearises.  The new factors are linearised at their
+        adjacent belief means as they are after the belief update of the grown graph (a new pose's belief is its prior), with zero
+        messages, iters_since_relin 1 and damping 0 (compute_factor gbp.py:267-294, 248-249).  solve_map / marginals results are dropped
+        until the next solve.  `extend` stays refused on such an engine: it takes eta_f, Lambda_f, which the engine owns."""
+        var_a, var_b = i32(var_a).reshape(-1), i32(var_b).reshape(-1)
+        dF = var_a.shape[0]
+        if var_b.shape[0] != dF:
+            raise ValueError("var_a / var_b length mismatch")
+        z = f64(np.asarray(measurement, dtype=np.float64).reshape(dF, 3))
+        s = f64(np.ascontiguousarray(np.broadcast_to(np.asarray(sqrt_info, dtype=np.float64), (dF, 3))))
+        dN = 0 if prior_eta is None else f64(prior_eta).reshape(-1, self.D).shape[0]
+        pe = f64(np.zeros((0, self.D)) if prior_eta is None else prior_eta, (dN, self.D))
+        pl = f64(np.zeros((0, self.D, self.D)) if prior_lam is None else prior_lam, (dN, self.D, self.D))
+        d = _capi.LinExtNonlinear(dN, dF, iptr(var_a), iptr(var_b), dptr(z), dptr(s), dptr(pe), dptr(pl))
+        check(self._lib.gbp_lin_extend_nonlinear(self._h, ct.byref(d)))
+        self.N, self.F = self.N + dN, self.F + dF
 
     def relinearise(self):
         """relinearise_factors (gbp.py:64-80) alone; returns the number of factors relinearised."""

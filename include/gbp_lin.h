@@ -17,7 +17,8 @@
  * Beside the sweep: the batch MAP (the `mu` of FactorGraph.joint_distribution_cov) and exact marginal covariances (its `sigma`, for
  * chosen variables), both by block-Jacobi conjugate gradients on the block-sparse joint; robust losses; growing and shrinking a live
  * graph; sweeps to convergence with the stop decided on the device (gbp_lin_iterate_until); and one NONLINEAR factor family, the SE(2)
- * relative-pose factor, relinearised on the device by the reference's local schedule (gbp_lin_set_nonlinear) -- below.
+ * relative-pose factor, relinearised on the device by the reference's local schedule (gbp_lin_set_nonlinear), on a handle that grows
+ * and shrinks too (gbp_lin_extend_nonlinear / gbp_lin_shrink_nonlinear) -- below.
  */
 #ifndef GBP_LIN_H
 #define GBP_LIN_H
@@ -310,7 +311,8 @@ int  gbp_lin_get_alloc_count(gbp_lin_t *h, int32_t *count);
  *                            eta_f, Lambda_f live where the solvers read them.  Every call that may relinearise marks the solver's
  *                            LDL^T and joint eta stale, as a change of robust weights does; a solve after it is one Gauss-Newton step;
  *   gbp_lin_set_robust, gbp_lin_robustify, gbp_lin_iterate_robust, gbp_lin_iterate_until, gbp_lin_extend, gbp_lin_shrink
- *                            GBP_ESTATE with a message; nothing changes.
+ *                            GBP_ESTATE with a message; nothing changes.  (gbp_lin_extend takes eta_f, Lambda_f, which a nonlinear
+ *                            handle owns: such a handle grows and shrinks through the two calls below.)
  * No floating-point atomics: two identical call sequences on two handles are bit-identical, counts included. */
 #define GBP_LIN_MODEL_SE2_BETWEEN 1
 typedef struct {
@@ -326,6 +328,41 @@ int  gbp_lin_set_nonlinear(gbp_lin_t *h, const gbp_lin_nonlinear_desc_t *d);    
 int  gbp_lin_relinearise(gbp_lin_t *h, int32_t *n_relinearised /* or NULL */);  /* relinearise_factors gbp.py:64-80 */
 int  gbp_lin_iterate_nonlinear(gbp_lin_t *h, int32_t n_iters, int32_t *relin_counts /* host, n_iters, or NULL */);   /* n x synchronous_iteration(local_relin=True) gbp.py:86-92 */
 int  gbp_lin_get_linearisation(gbp_lin_t *h, double *linpoint /* F x 6 */, int32_t *iters_since_relin /* F */, double *eta_damping /* F */);   /* Factor.linpoint gbp.py:231, iters_since_relin / eta_damping gbp.py:248-249; any may be NULL */
+
+/* ---- growing and shrinking a live NONLINEAR handle: a fixed-lag smoother for SE(2) pose graphs ----
+ * Both calls return GBP_ESTATE on a handle without nonlinear factors, validate completely before anything changes, leave the handle
+ * bit-identical on any failure before the commit (GBP_EINVAL, GBP_ENOMEM), drop the solver workspaces and mark the joint stale as
+ * gbp_lin_extend / gbp_lin_shrink do, and leave the handle holding ONE generation of arrays: gbp_lin_get_alloc_count does not grow
+ * with repeated calls.  beta, num_undamped_iters, min_linear_iters and the graph's eta_damping stay the handle's.  No atomics.
+ * After the commit only a failed kernel launch (GBP_EHIP) can still be returned, by the belief stage or by the linearise pass of
+ * gbp_lin_extend_nonlinear: the handle then holds the new graph, but its beliefs -- and the new factors' eta_f, Lambda_f (zero) and
+ * linpoint -- are not those of a completed call, and it should be destroyed.
+ *
+ * gbp_lin_extend_nonlinear: var_nodes.append / factors.append / adj_factors.append, update_all_beliefs() (gbp.py:56-58), then
+ * compute_factor() on the NEW factors only (gbp.py:267-294).  Ids, adjacency order and the index and size rules are those of
+ * gbp_lin_extend; measurements must be finite and sqrt_info positive and finite, as for gbp_lin_set_nonlinear.  A new factor is
+ * linearised at its two adjacent belief means as they are AFTER the belief update -- a new variable's belief is its prior, so the
+ * caller puts the odometry prediction there -- and starts with zero messages, iters_since_relin = 1 and damping 0 (gbp.py:222,
+ * 248-249).  Every old factor keeps eta_f, Lambda_f, linpoint, iters_since_relin, damping and both messages bit for bit, and every old
+ * variable its belief record: nothing relinearises in the call.  The linearisation runs over the new factors alone (work and traffic
+ * go by dF), with the lane code of gbp_lin_set_nonlinear: a handle created with the first K factors and extended by the rest before any
+ * sweep is bit-identical to the handle created whole.  dN == dF == 0: GBP_OK, nothing changes.
+ *
+ * gbp_lin_shrink_nonlinear: the descriptor and the semantics of gbp_lin_shrink -- retired variables leave with their factors, listed
+ * factors are dropped, with `fold` a leaving unlisted factor with one surviving end adds its stored message to that end's prior,
+ * survivors are renumbered monotonically, var_map / factor_map are returned.  A surviving factor keeps eta_f, Lambda_f, measurement,
+ * sqrt_info, linpoint, iters_since_relin, damping and both messages bit for bit; nothing relinearises in the call.  THE FOLD IS FROZEN:
+ * the folded message is the one the leaving factor computed at its LAST linearisation point, and once it is part of a prior it never
+ * relinearises again (the reference's priors are linear too). */
+typedef struct {
+    int32_t n_new_vars, n_new_factors;      /* dN, dF >= 0                                                          */
+    const int32_t *var_a, *var_b;           /* dF: ids in [0, N + dN), a != b; old-old, old-new and new-new allowed */
+    const double *measurement;              /* dF x 3, finite (not whitened)                                        */
+    const double *sqrt_info;                /* dF x 3, positive and finite                                          */
+    const double *prior_eta, *prior_lam;    /* dN x 3, dN x 3 x 3                                                   */
+} gbp_lin_extend_nonlinear_desc_t;
+int  gbp_lin_extend_nonlinear(gbp_lin_t *h, const gbp_lin_extend_nonlinear_desc_t *d);   /* appends + gbp.py:56-58 + compute_factor gbp.py:267-294 on the new factors */
+int  gbp_lin_shrink_nonlinear(gbp_lin_t *h, const gbp_lin_shrink_desc_t *d);
 
 #ifdef __cplusplus
 }

@@ -38,6 +38,11 @@ ap.add_argument('--nonlinear', action='store_true',
                 help='instead of the run above: the same two graphs re-posed as SE(2) pose graphs; time iterate(n, relinearise=True) with beta = +inf and with '
                      'beta = 0 against iterate(n) on the same handle, and one host relinearisation + gbp_lin_create against iterate(1, relinearise=True); '
                      'writes profiles/linear_nonlinear.json')
+ap.add_argument('--nonlinear-live', action='store_true',
+                help='time gbp_lin_extend_nonlinear (+1000 poses, +5000 factors) and gbp_lin_shrink_nonlinear (the 1000 oldest poses, folded) against '
+                     're-creating the handle (gbp_lin_create + gbp_lin_set_nonlinear) and against the linear extend / shrink, and the nonlinear sweep '
+                     'against --parent-lib; writes profiles/linear_nonlinear_live.json')
+ap.add_argument('--parent-lib', default=None, help="--nonlinear-live: the parent commit's libgbp_hip.so, loaded beside this one for the yardsticks")
 ap.add_argument('--parent-results', default=None,
                 help="--extend / --shrink / --until / --nonlinear: a file of lines 'parent {json}' / 'here {json}', each the JSON line of a plain run of this tool from the parent "
                      "commit's tree or from this one (run alternating, in the same session); summarised per workload under sweeps_per_s_vs_parent")
@@ -563,6 +568,145 @@ def nonlinear_profile():
     print(json.dumps(out))
 
 
+class RawSE2:
+    """gbp_lin_create + gbp_lin_set_nonlinear through the C ABI of ANY build of the library (this one or --parent-lib)."""
+
+    def __init__(self, lib, va, vb, z, s, pe, pl, beta, minlin):
+        import ctypes as ct
+        from gbp_amd import _capi
+        self.lib, self.ct = lib, ct
+        F, N = va.shape[0], pe.shape[0]
+        fe, fl = np.zeros((F, 6)), np.zeros((F, 6, 6))
+        d = _capi.LinDesc()
+        d.n_vars, d.dofs, d.n_factors, d.device = N, 3, F, 0
+        d.var_a, d.var_b = _capi.iptr(va), _capi.iptr(vb)
+        d.factor_eta, d.factor_lam, d.factor_const = _capi.dptr(fe), _capi.dptr(fl), None
+        d.prior_eta, d.prior_lam, d.eta_damping = _capi.dptr(pe), _capi.dptr(pl), 0.4
+        self.h = ct.c_void_p()
+        for name in ('gbp_lin_create', 'gbp_lin_set_nonlinear', 'gbp_lin_iterate_nonlinear', 'gbp_lin_sync'):
+            getattr(lib, name).restype = ct.c_int
+        lib.gbp_lin_destroy.restype = None
+        assert lib.gbp_lin_create(ct.byref(self.h), ct.byref(d)) == 0
+        nd = _capi.LinNonlinear(1, 4, int(minlin), 0, float(beta), _capi.dptr(z), _capi.dptr(s))
+        assert lib.gbp_lin_set_nonlinear(self.h, ct.byref(nd)) == 0
+        assert lib.gbp_lin_sync(self.h) == 0
+
+    def sweeps(self, n):
+        t = time.perf_counter()
+        assert self.lib.gbp_lin_iterate_nonlinear(self.h, self.ct.c_int32(n), None) == 0 and self.lib.gbp_lin_sync(self.h) == 0
+        return 1e3 * (time.perf_counter() - t) / n
+
+    def close(self):
+        self.lib.gbp_lin_destroy(self.h)
+
+
+def nonlinear_live_profile():
+    """Host clock around whole calls, each ending in gbp_lin_sync, after one untimed warm-up round; --repeats alternating rounds, medians
+    reported, spread = (max - min) / median.  Per round and graph, on a handle that has run 4 relinearising sweeps: (a) extend_se2 by 1000
+    poses and 5000 factors (each new pose joined to the pose before it and to 4 random older poses); (b) on the grown handle, shrink
+    retiring the 1000 oldest poses with the fold; (c) the yardstick for each: gbp_lin_create + gbp_lin_set_nonlinear of the grown / the
+    surviving graph from host arrays that are already packed, through --parent-lib where given (else this library: the same code) -- it
+    loses every message, linearisation point, iters and damping besides; (d) the linear gbp_lin_extend / gbp_lin_shrink of the same sizes
+    on a linear handle of the same graph.  Counted: a linear extend / shrink moves per factor the sweep's arrays (2 ends, 6 + 21 factor
+    doubles, 18 message doubles, 18 of vmsg, 2 edge slots); the nonlinear calls move 16 more values per factor (3 + 3 + 6 + iters +
+    damping), and the extend adds one linearise launch over the new factors.  (e) the sweep of gbp_lin_iterate_nonlinear at beta = +inf
+    and at beta = 0 (min_linear_iters 0), this library against --parent-lib on handles of the same graph, alternating, once with the
+    parent's handle created first and once with this library's."""
+    import ctypes as ct
+    from gbp_amd import _capi
+    here = _capi.load()
+    parent = ct.CDLL(os.path.abspath(a.parent_lib)) if a.parent_lib else None
+    dN, per = 1000, 5
+    runs = []
+    for N, k in ((200_000, 5), (1_000_000, 1)):
+        rs = np.random.RandomState(0)
+        va, vb, z, s, pe, pl = se2_graph(N, k, rs)
+        F = va.shape[0]
+        # the appended part: pose N + i hangs on the pose before it and on 4 random older ones
+        na = np.concatenate([np.arange(N - 1, N + dN - 1)[:, None], rs.randint(0, N, (dN, per - 1))], 1).reshape(-1).astype(np.int32)
+        nb = np.repeat(np.arange(N, N + dN), per).astype(np.int32)
+        nz, ns = rs.normal(0, 0.3, (dN * per, 3)), np.tile(np.array([10.0, 10.0, 20.0]), (dN * per, 1))
+        npl = np.ascontiguousarray(np.broadcast_to(np.diag([1.0, 1.0, 4.0]), (dN, 3, 3)))
+        npe = rs.normal(0, 1, (dN, 3))
+        ga, gb, gz, gs = np.concatenate([va, na]), np.concatenate([vb, nb]), np.concatenate([z, nz]), np.concatenate([s, ns])
+        gpe, gpl = np.concatenate([pe, npe]), np.concatenate([pl, npl])
+        keep = (ga >= dN) & (gb >= dN)                       # what survives retiring poses 0 .. 999
+        sa, sb, sz, ss = ga[keep] - dN, gb[keep] - dN, np.ascontiguousarray(gz[keep]), np.ascontiguousarray(gs[keep])
+        spe, spl = np.ascontiguousarray(gpe[dN:]), np.ascontiguousarray(gpl[dN:])
+        sa, sb = np.ascontiguousarray(sa.astype(np.int32)), np.ascontiguousarray(sb.astype(np.int32))
+        lfe, lfl = np.zeros((dN * per, 6)), np.ascontiguousarray(np.broadcast_to(np.eye(6), (dN * per, 6, 6)))
+        ylib = parent or here
+
+        def timed(fn, sync):
+            t = time.perf_counter(); fn(); sync()
+            return 1e3 * (time.perf_counter() - t)
+
+        def recreate(args):
+            t = time.perf_counter()
+            h = RawSE2(ylib, *args, 0.05, 2)
+            t = 1e3 * (time.perf_counter() - t)
+            h.close()
+            return t
+
+        rec = {key: [] for key in ('extend_se2', 'shrink_nonlinear', 'recreate_grown', 'recreate_survivors', 'extend_linear', 'shrink_linear')}
+        for rnd in range(a.repeats + 1):                    # round 0 is the warm-up
+            e = LinearEngine.se2_pose_graph(va, vb, z, s, pe, pl, 0.05, 4, 2, eta_damping=0.4)
+            e.iterate(4, relinearise=True); e.sync()
+            row = {'extend_se2': timed(lambda: e.extend_se2(na, nb, nz, ns, npe, npl), e.sync)}
+            row['shrink_nonlinear'] = timed(lambda: e.retire(np.arange(dN)), e.sync)
+            assert e.sizes() == (N, int(keep.sum()))
+            e.close()
+            row['recreate_grown'] = recreate((ga, gb, gz, gs, gpe, gpl))
+            row['recreate_survivors'] = recreate((sa, sb, sz, ss, spe, spl))
+            l = LinearEngine(va, vb, np.zeros((F, 6)), np.ascontiguousarray(np.broadcast_to(np.eye(6), (F, 6, 6))), pe, pl, eta_damping=0.4)
+            l.update_all_beliefs(); l.iterate(4); l.sync()
+            row['extend_linear'] = timed(lambda: l.extend(na, nb, lfe, lfl, npe, npl), l.sync)
+            row['shrink_linear'] = timed(lambda: l.retire(np.arange(dN)), l.sync)
+            l.close()
+            if rnd:
+                for key, v in row.items():
+                    rec[key].append(v)
+        med = {key: statistics.median(v) for key, v in rec.items()}
+        spread = {key: (max(v) - min(v)) / med[key] for key, v in rec.items()}
+        lin_values = 2 + 27 + 18 + 18 + 2                     # per factor, moved by the linear calls
+        sweeps = None
+        if parent:
+            sweeps = {}
+            # both orders of creation: which handle's arrays are allocated first moves a handle's sweep by more than its rounds differ
+            for tag, beta, minlin in (('beta_inf', float('inf'), 2), ('beta_0', 0.0, 0)):
+                for order in ('parent_created_first', 'here_created_first'):
+                    first, second = (parent, here) if order == 'parent_created_first' else (here, parent)
+                    h1 = RawSE2(first, va, vb, z, s, pe, pl, beta, minlin)
+                    h2 = RawSE2(second, va, vb, z, s, pe, pl, beta, minlin)
+                    hp, hh = (h1, h2) if order == 'parent_created_first' else (h2, h1)
+                    hp.sweeps(a.warmup); hh.sweeps(a.warmup)
+                    tp, th = [], []
+                    for _ in range(a.repeats):
+                        tp.append(hp.sweeps(a.steps)); th.append(hh.sweeps(a.steps))
+                    hp.close(); hh.close()
+                    mp, mh = statistics.median(tp), statistics.median(th)
+                    sweeps[tag + '_' + order] = {"ms_per_sweep_parent": mp, "ms_per_sweep_here": mh, "ratio_here_over_parent": mh / mp,
+                                                 "spread_parent": (max(tp) - min(tp)) / mp, "spread_here": (max(th) - min(th)) / mh, "ms_all_parent": tp, "ms_all_here": th}
+        runs.append({"vars": N, "k": k, "factors": F, "new_vars": dN, "new_factors": dN * per, "retired_vars": dN, "surviving_factors": int(keep.sum()),
+                     "ms": med, "spread": spread, "ms_all": rec, "yardstick_library": "parent" if parent else "this library (no --parent-lib given)",
+                     "ratio_recreate_over_extend_se2": med['recreate_grown'] / med['extend_se2'],
+                     "ratio_recreate_over_shrink_nonlinear": med['recreate_survivors'] / med['shrink_nonlinear'],
+                     "ratio_extend_se2_over_linear": med['extend_se2'] / med['extend_linear'], "ratio_shrink_nonlinear_over_linear": med['shrink_nonlinear'] / med['shrink_linear'],
+                     "ratio_counted_values": (lin_values + 16) / lin_values, "counters_collected": False, "nonlinear_sweep_vs_parent": sweeps})
+    out = {"what": "tools/bench_linear.py --nonlinear-live on one MI355X: gbp_lin_extend_nonlinear and gbp_lin_shrink_nonlinear against re-creating the handle and "
+                   "against the linear calls, and the nonlinear sweep against the parent commit's library, on the 200k x 3 ring (k = 5) and the 1M-variable "
+                   "chain (k = 1) re-posed as SE(2)",
+           "method": " ".join(nonlinear_live_profile.__doc__.split()), "repeats": a.repeats, "sweep_steps": a.steps, "runs": runs}
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'profiles', 'linear_nonlinear_live.json')
+    with open(path, 'w') as fh:
+        json.dump(out, fh, indent=1)
+        fh.write('\n')
+    print(json.dumps(out))
+
+
+if a.nonlinear_live:
+    nonlinear_live_profile()
+    sys.exit(0)
 if a.nonlinear:
     nonlinear_profile()
     sys.exit(0)
