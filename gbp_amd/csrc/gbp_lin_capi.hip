@@ -65,12 +65,12 @@ static int lin_create_impl(gbp_lin *h, const gbp_lin_desc_t *d)
     LHIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     h->D = D;
     h->has_const = d->factor_const != nullptr;
-    const int P = D * (D + 1) / 2, P2 = D * (2 * D + 1), D2 = 2 * D, R = D + P;
+    const LinRows r = lin_rows(D);
     h->p.damping = d->eta_damping;
 
     // factor data -> SoA, packed upper; adjacency CSR in ascending factor id (= append order, ndim_posegraph.py:86-88)
     std::vector<int32_t> va(d->var_a, d->var_a + F), vb(d->var_b, d->var_b + F), vptr((size_t)N + 1, 0), vadj((size_t)2 * F);
-    std::vector<double> feta((size_t)D2 * F), flam((size_t)P2 * F), fconst((size_t)F, 0.0), prior((size_t)N * R);
+    std::vector<double> feta((size_t)r.eta2 * F), flam((size_t)r.lam2 * F), fconst((size_t)F, 0.0), prior((size_t)N * r.msg);
     for (int f = 0; f < F; ++f) {
         if (va[f] < 0 || va[f] >= N || vb[f] < 0 || vb[f] >= N || va[f] == vb[f])
             return set_error(GBP_EINVAL, "factor %d joins variables (%d, %d): need two different ids in [0, %d)", f, va[f], vb[f], N);
@@ -93,15 +93,16 @@ static int lin_create_impl(gbp_lin *h, const gbp_lin_desc_t *d)
     // The host vectors above are the sources of the copies and outlive the one synchronisation, on the failure path too.
     LinScratch mem;
     LinGen g;
-    auto copy = [&](auto *dst, const auto &v) { return v.empty() ? hipSuccess : hipMemcpyAsync(dst, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice, h->stream); };
-    auto zero = [&](double *dst, size_t n) { return n ? hipMemsetAsync(dst, 0, n * sizeof(double), h->stream) : hipSuccess; };
+    LinParams &n = g.p;
+    auto copy = [&](const auto *dst, const auto &v) { return v.empty() ? hipSuccess : hipMemcpyAsync(lin_mut(dst), v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice, h->stream); };
+    auto zero = [&](double *dst, size_t cnt) { return cnt ? hipMemsetAsync(dst, 0, cnt * sizeof(double), h->stream) : hipSuccess; };
     const int rc = [&]() -> int {
-        LCHK(lin_gen_alloc(h, mem, g, N, F, false, true));
-        LHIPCHK(copy(g.va, va)); LHIPCHK(copy(g.vb, vb)); LHIPCHK(copy(g.vptr, vptr)); LHIPCHK(copy(g.vadj, vadj));
-        LHIPCHK(copy(g.feta, feta)); LHIPCHK(copy(g.flam, flam)); LHIPCHK(copy(g.fconst, fconst)); LHIPCHK(copy(g.prior, prior));
-        LHIPCHK(copy(g.epos_a, epos_a)); LHIPCHK(copy(g.epos_b, epos_b));
-        LHIPCHK(zero(g.msg_a, (size_t)R * F)); LHIPCHK(zero(g.msg_b, (size_t)R * F)); LHIPCHK(zero(g.vmsg, (size_t)2 * F * R));
-        LHIPCHK(zero(g.bel, (size_t)N * (R + D))); LHIPCHK(zero(g.d_red, (size_t)g.red_blocks));
+        LCHK(lin_gen_alloc(h, mem, g, N, F));
+        LHIPCHK(copy(n.va, va)); LHIPCHK(copy(n.vb, vb)); LHIPCHK(copy(n.vptr, vptr)); LHIPCHK(copy(n.vadj, vadj));
+        LHIPCHK(copy(n.feta, feta)); LHIPCHK(copy(n.flam, flam)); LHIPCHK(copy(n.fconst, fconst)); LHIPCHK(copy(n.prior, prior));
+        LHIPCHK(copy(n.epos_a, epos_a)); LHIPCHK(copy(n.epos_b, epos_b));
+        LHIPCHK(zero(n.msg_a, (size_t)r.msg * F)); LHIPCHK(zero(n.msg_b, (size_t)r.msg * F)); LHIPCHK(zero(n.vmsg, (size_t)2 * F * r.msg));
+        LHIPCHK(zero(n.bel, (size_t)N * r.rec)); LHIPCHK(zero(g.d_red, (size_t)g.red_blocks));
         LHIPCHK(hipStreamSynchronize(h->stream));
         return GBP_OK;
     }();

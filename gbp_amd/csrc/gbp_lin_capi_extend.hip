@@ -5,11 +5,13 @@
 // One call: validate on the host (only the appended part is looked at), pack and upload the new factors and priors, allocate EVERY new
 // array (lin_gen_alloc), build them on the device from the old ones -- which are only read -- and synchronise; only then commit the
 // new generation (lin_gen_commit, gbp_lin_generation.hpp) and, where the handle had beliefs, run the belief stage over all variables.
+// Which arrays are re-strided, from which old array and with which fill for the appended factors is not said here: ext_build walks
+// lin_gen_columns and looks up the uploaded rows of a column by its id.
 // A failure before the commit frees what was allocated and leaves the handle as it was.  Host work and host <-> device traffic are
 // proportional to dN and dF; no existing array crosses to the host.
 //
 // gbp_lin_extend_nonlinear is the same call on a handle of gbp_lin_set_nonlinear: the same build with zero eta_f, Lambda_f for the new
-// factors and the five per-factor arrays of LinNonlin re-strided with the rest, the same commit, the belief stage, and then
+// factors (no uploaded rows: the fill) and the per-factor arrays of LinNonlin re-strided with the rest, the same commit, the belief stage, and then
 // compute_factor (gbp.py:267-294) over the new factors alone (lin_nonlin_linearise, gbp_lin_capi_nonlin.hip).
 #include "gbp_lin_extend.hpp"
 #include "gbp_lin_generation.hpp"
@@ -52,52 +54,55 @@ void ext_restride(gbp_lin *h, const T *src, const T *tail, T *dst, int rows, int
 
 int ext_blocks(size_t n) { return (int)((n + EXT_BLOCK - 1) / EXT_BLOCK); }
 
+// the uploaded rows [row][dF] of the appended factors, by column; nullptr: the column's fill (lin_gen_columns) applies to them
+struct ExtTails {
+    const int *i[LC_COUNT] = {};
+    const double *d[LC_COUNT] = {};
+    const int *of(LinCol c, int) const { return i[c]; }
+    const double *of(LinCol c, double) const { return d[c]; }
+};
+
 // everything up to and including the synchronisation after which nothing can fail: the new arrays, built on the device.  nl: the
-// descriptor of gbp_lin_extend_nonlinear, whose sizes, ends and priors `d` repeats; its factors arrive as measurements, eta_f and
-// Lambda_f start at zero (the linearise pass after the commit writes them) and so does const_f where the handle has one
-int ext_build(gbp_lin *h, const gbp_lin_extend_desc_t *d, const gbp_lin_extend_nonlinear_desc_t *nl, bool robust, LinScratch &mem, ExtHost &host, LinGen &n)
+// descriptor of gbp_lin_extend_nonlinear, whose sizes, ends and priors `d` repeats; its factors arrive as measurements, and eta_f,
+// Lambda_f (the linearise pass after the commit writes them) and const_f have no uploaded rows: they start at their fill, zero
+int ext_build(gbp_lin *h, const gbp_lin_extend_desc_t *d, const gbp_lin_extend_nonlinear_desc_t *nl, LinScratch &mem, ExtHost &host, LinGen &n)
 {
     const LinParams &p = h->p;
-    const int D = h->D, D2 = 2 * D, P = D * (D + 1) / 2, P2 = D * (2 * D + 1), R = D + P, REC = D + P + D;
+    const LinRows r = lin_rows(h->D);
+    const int R = r.msg, REC = r.rec;
     const int N = p.N, F = p.F, dN = d->n_new_vars, dF = d->n_new_factors, N1 = N + dN, F1 = F + dF;
 
     // ---- the appended part, packed as gbp_lin_create packs the whole: SoA rows [row][dF], packed upper triangles ----
-    std::vector<int> &ha = host.a, &hb = host.b, &hloss = host.loss;
-    std::vector<double> &hfeta = host.feta, &hflam = host.flam, &hfconst = host.fconst, &hprior = host.prior, &hthr = host.thr, &hnvar = host.nvar;
-    ha.assign(d->var_a, d->var_a + dF); hb.assign(d->var_b, d->var_b + dF);
-    hprior.resize((size_t)dN * R);
+    host.a.assign(d->var_a, d->var_a + dF); host.b.assign(d->var_b, d->var_b + dF);
+    host.prior.resize((size_t)dN * R);
+    lin_pack_priors(h->D, dN, d->prior_eta, d->prior_lam, host.prior.data());
+    ExtTails t;
+    LCHK(ext_upload(h, mem, &t.i[LC_VA], host.a)); LCHK(ext_upload(h, mem, &t.i[LC_VB], host.b));
     if (!nl) {
-        hfeta.resize((size_t)D2 * dF); hflam.resize((size_t)P2 * dF);
-        lin_pack_factors(D, dF, d->factor_eta, d->factor_lam, hfeta.data(), hflam.data());
-        if (h->has_const) hfconst.assign(d->factor_const, d->factor_const + dF);
-    } else {                                                // SoA rows [3][dF], as gbp_lin_set_nonlinear packs the whole
-        host.meas.resize((size_t)NL_M * dF); host.sinfo.resize((size_t)NL_M * dF);
-        for (int f = 0; f < dF; ++f)
-            for (int k = 0; k < NL_M; ++k) {
-                host.meas[(size_t)k * dF + f] = nl->measurement[(size_t)f * NL_M + k];
-                host.sinfo[(size_t)k * dF + f] = nl->sqrt_info[(size_t)f * NL_M + k];
-            }
-    }
-    lin_pack_priors(D, dN, d->prior_eta, d->prior_lam, hprior.data());
-    if (robust && d->loss && dF) {
-        hloss.assign(d->loss, d->loss + dF);
-        hthr.assign((size_t)dF, 1.0); hnvar.assign((size_t)dF, 1.0);
-        for (int f = 0; f < dF; ++f) {
-            if (hloss[f] != GBP_LIN_LOSS_NONE) hthr[f] = d->threshold[f];
-            if (hloss[f] == GBP_LIN_LOSS_CONSTANT) hnvar[f] = d->noise_var[f];
+        host.feta.resize((size_t)r.eta2 * dF); host.flam.resize((size_t)r.lam2 * dF);
+        lin_pack_factors(h->D, dF, d->factor_eta, d->factor_lam, host.feta.data(), host.flam.data());
+        LCHK(ext_upload(h, mem, &t.d[LC_FETA], host.feta)); LCHK(ext_upload(h, mem, &t.d[LC_FLAM], host.flam));
+        if (h->has_const) {
+            host.fconst.assign(d->factor_const, d->factor_const + dF);
+            LCHK(ext_upload(h, mem, &t.d[LC_FCONST], host.fconst));
         }
+    } else {                                                // as gbp_lin_set_nonlinear packs the whole
+        host.meas.resize((size_t)NL_M * dF); host.sinfo.resize((size_t)NL_M * dF);
+        lin_pack_measurements(dF, nl->measurement, nl->sqrt_info, host.meas.data(), host.sinfo.data());
+        LCHK(ext_upload(h, mem, &t.d[LC_MEAS], host.meas)); LCHK(ext_upload(h, mem, &t.d[LC_SINFO], host.sinfo));
     }
-    const int *ta = nullptr, *tb = nullptr, *tloss = nullptr;
-    const double *tfeta = nullptr, *tflam = nullptr, *tfconst = nullptr, *tthr = nullptr, *tnvar = nullptr, *tmeas = nullptr, *tsinfo = nullptr;
-    LCHK(ext_upload(h, mem, &ta, ha)); LCHK(ext_upload(h, mem, &tb, hb));
-    if (!nl) {
-        LCHK(ext_upload(h, mem, &tfeta, hfeta)); LCHK(ext_upload(h, mem, &tflam, hflam));
-        if (h->has_const) LCHK(ext_upload(h, mem, &tfconst, hfconst));
-    } else { LCHK(ext_upload(h, mem, &tmeas, host.meas)); LCHK(ext_upload(h, mem, &tsinfo, host.sinfo)); }
-    if (!hloss.empty()) { LCHK(ext_upload(h, mem, &tloss, hloss)); LCHK(ext_upload(h, mem, &tthr, hthr)); LCHK(ext_upload(h, mem, &tnvar, hnvar)); }
+    if (n.robust && d->loss && dF) {
+        host.loss.assign(d->loss, d->loss + dF);
+        host.thr.assign((size_t)dF, LIN_NEW_THR); host.nvar.assign((size_t)dF, LIN_NEW_NVAR);
+        for (int f = 0; f < dF; ++f) {
+            if (host.loss[f] != GBP_LIN_LOSS_NONE) host.thr[f] = d->threshold[f];
+            if (host.loss[f] == GBP_LIN_LOSS_CONSTANT) host.nvar[f] = d->noise_var[f];
+        }
+        LCHK(ext_upload(h, mem, &t.i[LC_LOSS], host.loss)); LCHK(ext_upload(h, mem, &t.d[LC_THR], host.thr)); LCHK(ext_upload(h, mem, &t.d[LC_NVAR], host.nvar));
+    }
 
     // ---- every allocation of the call, before the first kernel ----
-    LCHK(lin_gen_alloc(h, mem, n, N1, F1, robust, true, nl != nullptr));     // d_red grows when ceil(F / 256) does
+    LCHK(lin_gen_alloc(h, mem, n, N1, F1));                 // d_red grows when ceil(F / 256) does
     int *keys = nullptr, *vals = nullptr, *keys_s = nullptr, *vals_s = nullptr, *enew = nullptr;
     void *sort_tmp = nullptr;
     int bits = 1;
@@ -108,58 +113,45 @@ int ext_build(gbp_lin *h, const gbp_lin_extend_desc_t *d, const gbp_lin_extend_n
     LCHK(mem.get(&enew, (size_t)2 * F, false));
     { char *q = nullptr; LCHK(mem.get(&q, sort_bytes, false)); sort_tmp = q; }
 
-    // ---- factor-strided arrays: [row][F] -> [row][F1] ----
-    ext_restride<int>(h, p.va, ta, n.va, 1, F, dF, 0); ext_restride<int>(h, p.vb, tb, n.vb, 1, F, dF, 0);
-    ext_restride<double>(h, p.feta, tfeta, n.feta, D2, F, dF, 0.0); ext_restride<double>(h, p.flam, tflam, n.flam, P2, F, dF, 0.0);
-    ext_restride<double>(h, p.fconst, tfconst, n.fconst, 1, F, dF, 0.0);
-    ext_restride<double>(h, p.msg_a, nullptr, n.msg_a, R, F, dF, 0.0); ext_restride<double>(h, p.msg_b, nullptr, n.msg_b, R, F, dF, 0.0);
-    if (robust) {
-        // a handle whose losses were cleared keeps stale losses in its arrays: its old factors are at NONE
-        const bool old = h->p.w != nullptr;
-        ext_restride<int>(h, old ? h->rob.loss : nullptr, tloss, n.loss, 1, F, dF, GBP_LIN_LOSS_NONE);
-        ext_restride<double>(h, old ? h->rob.thr : nullptr, tthr, n.thr, 1, F, dF, 1.0);
-        ext_restride<double>(h, old ? h->rob.nvar : nullptr, tnvar, n.nvar, 1, F, dF, 1.0);
-        ext_restride<double>(h, old ? h->rob.w : nullptr, nullptr, n.w, 1, F, dF, 1.0);
-        ext_restride<int>(h, old ? h->rob.flag : nullptr, nullptr, n.flag, 1, F, dF, 0);
-    }
-    if (nl) {
-        // the old factors' rows as they are; the new factors' linpoint, iters and damping hold a fill until the linearise pass
-        ext_restride<double>(h, h->nl.meas, tmeas, n.meas, NL_M, F, dF, 0.0); ext_restride<double>(h, h->nl.sinfo, tsinfo, n.sinfo, NL_M, F, dF, 1.0);
-        ext_restride<double>(h, h->nl.linpoint, nullptr, n.linpoint, 2 * NL_D, F, dF, 0.0);
-        ext_restride<int>(h, h->nl.iters, nullptr, n.iters, 1, F, dF, 1); ext_restride<double>(h, h->nl.fdamp, nullptr, n.fdamp, 1, F, dF, 0.0);
-    }
+    // ---- factor-strided arrays: [row][F] -> [row][F1], the old factors' rows as they are (the fill where the handle has none to
+    // give), then the uploaded rows or the fill.  epos_a / epos_b are not among them: the two edge kernels below write them ----
+    lin_gen_columns(h, n, [&](auto c) {
+        if (n.has(c.group) && c.id != LC_EPOS_A && c.id != LC_EPOS_B) ext_restride(h, c.old, t.of(c.id, c.fill), c.neu, c.rows, F, dF, c.fill);
+    });
     LHIPCHK(hipGetLastError());
     // ---- variable-strided records: the old ones as they are, the new priors behind them; new belief records start at zero ----
+    double *nbel = n.p.bel, *nprior = lin_mut(n.p.prior);
+    int *nvptr = lin_mut(n.p.vptr), *nvadj = lin_mut(n.p.vadj), *nepos_a = lin_mut(n.p.epos_a), *nepos_b = lin_mut(n.p.epos_b);
     if (N) {
-        LHIPCHK(hipMemcpyAsync(n.bel, p.bel, (size_t)N * REC * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        LHIPCHK(hipMemcpyAsync(n.prior, p.prior, (size_t)N * R * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        LHIPCHK(hipMemcpyAsync(nbel, p.bel, (size_t)N * REC * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        LHIPCHK(hipMemcpyAsync(nprior, p.prior, (size_t)N * R * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     }
     if (dN) {
-        LHIPCHK(hipMemsetAsync(n.bel + (size_t)N * REC, 0, (size_t)dN * REC * sizeof(double), h->stream));
-        LHIPCHK(hipMemcpyAsync(n.prior + (size_t)N * R, hprior.data(), hprior.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        LHIPCHK(hipMemsetAsync(nbel + (size_t)N * REC, 0, (size_t)dN * REC * sizeof(double), h->stream));
+        LHIPCHK(hipMemcpyAsync(nprior + (size_t)N * R, host.prior.data(), host.prior.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     }
     if (n.d_red) LHIPCHK(hipMemsetAsync(n.d_red, 0, (size_t)n.red_blocks * sizeof(double), h->stream));
     // ---- the CSR: new edges sorted by variable (stable: ascending factor id within one), merged behind each variable's old list ----
     const int *skeys = keys_s, *svals = vals_s;
     if (dF) {
-        hipLaunchKernelGGL(k_ext_edges, dim3(ext_blocks((size_t)2 * dF)), dim3(EXT_BLOCK), 0, h->stream, ta, tb, F, dF, keys, vals);
+        hipLaunchKernelGGL(k_ext_edges, dim3(ext_blocks((size_t)2 * dF)), dim3(EXT_BLOCK), 0, h->stream, t.i[LC_VA], t.i[LC_VB], F, dF, keys, vals);
         LHIPCHK(hipGetLastError());
         const int rc = sort_pairs(sort_tmp, sort_bytes, keys, keys_s, vals, vals_s, (size_t)2 * dF, bits, h->stream);
         if (rc != (int)hipSuccess) return set_error(GBP_EHIP, "sorting the new edges failed: %s", hipGetErrorString((hipError_t)rc));
     }
-    hipLaunchKernelGGL(k_ext_vptr, dim3(ext_blocks((size_t)N1 + 1)), dim3(EXT_BLOCK), 0, h->stream, p.vptr, N, N1, skeys, 2 * dF, n.vptr);
+    hipLaunchKernelGGL(k_ext_vptr, dim3(ext_blocks((size_t)N1 + 1)), dim3(EXT_BLOCK), 0, h->stream, p.vptr, N, N1, skeys, 2 * dF, nvptr);
     if (F) {
-        hipLaunchKernelGGL(k_ext_old_edges, dim3(ext_blocks((size_t)2 * F)), dim3(EXT_BLOCK), 0, h->stream, p.vptr, (const int *)n.vptr, p.vadj, p.va, p.vb,
-                           2 * F, n.vadj, n.epos_a, n.epos_b, enew);
-        lin_dispatch(D, [&](auto dd) {
+        hipLaunchKernelGGL(k_ext_old_edges, dim3(ext_blocks((size_t)2 * F)), dim3(EXT_BLOCK), 0, h->stream, p.vptr, (const int *)nvptr, p.vadj, p.va, p.vb,
+                           2 * F, nvadj, nepos_a, nepos_b, enew);
+        lin_dispatch(h->D, [&](auto dd) {
             constexpr int RR = LinDims<decltype(dd)::value>::P + decltype(dd)::value;
             const size_t cnt = (size_t)2 * F * RR;
-            hipLaunchKernelGGL((k_ext_move_vmsg<RR>), dim3(ext_blocks(cnt)), dim3(EXT_BLOCK), 0, h->stream, (const double *)p.vmsg, (const int *)enew, cnt, n.vmsg);
+            hipLaunchKernelGGL((k_ext_move_vmsg<RR>), dim3(ext_blocks(cnt)), dim3(EXT_BLOCK), 0, h->stream, (const double *)p.vmsg, (const int *)enew, cnt, n.p.vmsg);
         });
     }
     if (dF)
-        hipLaunchKernelGGL(k_ext_new_edges, dim3(ext_blocks((size_t)2 * dF * R)), dim3(EXT_BLOCK), 0, h->stream, p.vptr, N, skeys, svals, 2 * dF, R, n.vadj,
-                           n.epos_a, n.epos_b, n.vmsg);
+        hipLaunchKernelGGL(k_ext_new_edges, dim3(ext_blocks((size_t)2 * dF * R)), dim3(EXT_BLOCK), 0, h->stream, p.vptr, N, skeys, svals, 2 * dF, R, nvadj,
+                           nepos_a, nepos_b, n.p.vmsg);
     LHIPCHK(hipGetLastError());
     LHIPCHK(hipStreamSynchronize(h->stream));              // nothing below can fail
     return GBP_OK;
@@ -199,7 +191,9 @@ int ext_run(gbp_lin *h, const gbp_lin_extend_desc_t *d, const gbp_lin_extend_non
     LinScratch mem;
     ExtHost host;                                           // read by the stream until the synchronisation in ext_build, or the one below
     LinGen n;
-    const int rc = ext_build(h, d, nl, robust, mem, host, n);
+    n.robust = robust;
+    n.nonlinear = nl != nullptr;
+    const int rc = ext_build(h, d, nl, mem, host, n);
     if (rc != GBP_OK) {                                     // the handle's arrays were only read: it goes on as it was
         (void)hipStreamSynchronize(h->stream);              // before `mem` frees what the stream may still be writing
         return rc;
@@ -245,10 +239,7 @@ int gbp_lin_extend_nonlinear(gbp_lin_t *h, const gbp_lin_extend_nonlinear_desc_t
     LCHK(ext_validate(h, &d, true));
     const int F = h->p.F, dF = nl->n_new_factors;
     if (dF && (!nl->measurement || !nl->sqrt_info)) return set_error(GBP_EINVAL, "NULL array in the descriptor");
-    for (size_t i = 0; i < (size_t)dF * NL_M; ++i) {        // the rules of gbp_lin_set_nonlinear
-        if (!(nl->sqrt_info[i] > 0.0) || !std::isfinite(nl->sqrt_info[i])) return set_error(GBP_EINVAL, "new factor %d: sqrt_info must be positive and finite", (int)(i / NL_M));
-        if (!std::isfinite(nl->measurement[i])) return set_error(GBP_EINVAL, "new factor %d: the measurement must be finite", (int)(i / NL_M));
-    }
+    LCHK(lin_check_measurements(nl->measurement, nl->sqrt_info, dF, "new factor"));    // the rules of gbp_lin_set_nonlinear
     if (!nl->n_new_vars && !dF) return GBP_OK;
     LCHK(ext_run(h, &d, nl, false));                        // ends with the belief stage: a nonlinear handle has beliefs
     // compute_factor on the new factors only (gbp.py:267-294), at the belief means as that stage left them; the joint is stale already

@@ -7,11 +7,11 @@
 // factor: measurement and square-root information, the linearisation point, iters_since_relin and the factor's damping.  A sweep is
 // three kernels queued on the handle's stream (k_lin_relin, k_lin_factor<3, false, LinRelin>, k_lin_belief): no host round trip; the
 // only atomics are integer adds of the per-sweep counts.  Every call that may relinearise clears map_ready, as a change of robust
-// weights does.
+// weights does.  The five per-factor arrays are the nonlinear columns of a generation (lin_gen_columns, gbp_lin_generation.hpp):
+// gbp_lin_set_nonlinear allocates them through that list, and extend / shrink rebuild them with the graph's.
+#include "gbp_lin_generation.hpp"
 #include "gbp_lin_nonlin.hpp"
 #include "gbp_lin_sweep.hpp"
-
-#include <cmath>
 
 using namespace gbp;
 
@@ -78,29 +78,26 @@ int gbp_lin_set_nonlinear(gbp_lin_t *h, const gbp_lin_nonlinear_desc_t *d)
     if (d->num_undamped_iters < 0 || d->min_linear_iters < 0) return set_error(GBP_EINVAL, "num_undamped_iters and min_linear_iters must not be negative");
     if (!(d->beta >= 0.0)) return set_error(GBP_EINVAL, "beta must not be negative (+inf: never relinearise)");
     if (F && (!d->measurement || !d->sqrt_info)) return set_error(GBP_EINVAL, "NULL array in the descriptor");
-    for (size_t i = 0; i < (size_t)F * NL_M; ++i) {
-        if (!(d->sqrt_info[i] > 0.0) || !std::isfinite(d->sqrt_info[i])) return set_error(GBP_EINVAL, "factor %d: sqrt_info must be positive and finite", (int)(i / NL_M));
-        if (!std::isfinite(d->measurement[i])) return set_error(GBP_EINVAL, "factor %d: the measurement must be finite", (int)(i / NL_M));
-    }
+    LCHK(lin_check_measurements(d->measurement, d->sqrt_info, F, "factor"));
     if (h->p.w) return set_error(GBP_ESTATE, "losses are set: robust nonlinear factors are not supported");
     if (h->nonlinear) return set_error(GBP_ESTATE, "the handle already has nonlinear factors");
 
     std::vector<double> z((size_t)NL_M * F), s((size_t)NL_M * F);     // SoA, stride F
-    for (int f = 0; f < F; ++f)
-        for (int k = 0; k < NL_M; ++k) { z[(size_t)k * F + f] = d->measurement[(size_t)f * NL_M + k]; s[(size_t)k * F + f] = d->sqrt_info[(size_t)f * NL_M + k]; }
-    LinNonlin nl{};
-    double *dz = nullptr, *ds = nullptr;
-    LCHK(lin_alloc(h, &dz, z.size())); LCHK(lin_alloc(h, &ds, s.size()));
-    LCHK(lin_alloc(h, &nl.linpoint, (size_t)2 * NL_D * F)); LCHK(lin_alloc(h, &nl.iters, (size_t)F)); LCHK(lin_alloc(h, &nl.fdamp, (size_t)F));
+    lin_pack_measurements(F, d->measurement, d->sqrt_info, z.data(), s.data());
+    LinGen g;                                               // the nonlinear columns of the generation the handle holds
+    int rc = GBP_OK;
+    lin_gen_columns(h, g, [&](auto c) { if (rc == GBP_OK && c.group == LIN_NONLIN) rc = lin_alloc(h, &c.neu, (size_t)c.rows * F); });
+    LCHK(rc);
+    LinNonlin &nl = g.nl;
     LCHK(lin_alloc(h, &nl.counts, 1));
-    nl.meas = dz; nl.sinfo = ds; nl.cap = 1;
-    nl.feta = const_cast<double *>(h->p.feta); nl.flam = const_cast<double *>(h->p.flam);
+    nl.cap = 1;
     nl.beta = d->beta; nl.num_undamped = d->num_undamped_iters; nl.min_linear = d->min_linear_iters; nl.model = d->model;
     if (F) {
-        LHIPCHK(hipMemcpyAsync(dz, z.data(), z.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        LHIPCHK(hipMemcpyAsync(ds, s.data(), s.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        LHIPCHK(hipMemcpyAsync(lin_mut(nl.meas), z.data(), z.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        LHIPCHK(hipMemcpyAsync(lin_mut(nl.sinfo), s.data(), s.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     }
     h->nl = nl;
+    lin_nl_point(h);
     if (!h->has_beliefs) LCHK(gbp_lin_update_beliefs(h));  // belief = prior (+ whatever messages the handle holds)
     nl_relin(h, NL_INIT, nullptr);                         // compute_all_factors gbp.py:60-62
     LHIPCHK(hipGetLastError());

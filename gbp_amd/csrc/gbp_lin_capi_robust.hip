@@ -7,7 +7,9 @@
 // LinParams::w is nullptr until losses are set and again after they are cleared: such a handle runs the plain kernels only.  Every call
 // that changes the weights clears map_ready, so the next solve re-makes the LDL^T of the diagonal blocks and the joint eta in the same
 // workspace; the iterate of the last solve stays where it is (gbp_lin_get_map).  A robust sweep is three kernels queued on the handle's
-// stream (k_lin_robustify, k_lin_factor<D, true>, k_lin_belief): no host round trip, no floating-point atomics.
+// stream (k_lin_robustify, k_lin_factor<D, true>, k_lin_belief): no host round trip, no floating-point atomics.  The five arrays of
+// LinRobust are the robust columns of a generation (lin_gen_columns, gbp_lin_generation.hpp): the first gbp_lin_set_robust allocates
+// them through that list, and the values it starts from are the list's fills.
 #include "gbp_lin_robust.hpp"
 #include "gbp_lin_generation.hpp"
 
@@ -22,11 +24,12 @@ int rob_upload(gbp_lin *h, const T *dst, const std::vector<T> &v)
     return GBP_OK;
 }
 
-// every weight 1, every flag 0
+// every weight and every flag as a new factor has them: 1 and 0
 int rob_reset(gbp_lin *h)
 {
     const size_t F = (size_t)h->p.F;
-    LCHK(rob_upload(h, h->rob.w, std::vector<double>(F, 1.0)));
+    static_assert(LIN_NEW_FLAG == 0, "the flags are reset by a memset");
+    LCHK(rob_upload(h, h->rob.w, std::vector<double>(F, LIN_NEW_W)));
     if (F) LHIPCHK(hipMemsetAsync(h->rob.flag, 0, F * sizeof(int), h->stream));
     LHIPCHK(hipStreamSynchronize(h->stream));              // the host vectors above are temporaries
     return GBP_OK;
@@ -70,13 +73,16 @@ int gbp_lin_set_robust(gbp_lin_t *h, const int32_t *loss, const double *threshol
     LCHK(lin_check_losses(loss, threshold, noise_var, F, "factor", &any));
     if (any && !h->has_const)
         return set_error(GBP_EINVAL, "a loss needs the factors' constants: the handle was created with factor_const == NULL");
-    if (!h->rob_alloc) {
-        LCHK(lin_alloc(h, &h->rob.loss, (size_t)F)); LCHK(lin_alloc(h, &h->rob.thr, (size_t)F)); LCHK(lin_alloc(h, &h->rob.nvar, (size_t)F));
-        LCHK(lin_alloc(h, &h->rob.w, (size_t)F)); LCHK(lin_alloc(h, &h->rob.flag, (size_t)F));
+    if (!h->rob_alloc) {                                    // the robust columns of the generation the handle holds
+        LinGen g;
+        int rc = GBP_OK;
+        lin_gen_columns(h, g, [&](auto c) { if (rc == GBP_OK && c.group == LIN_ROBUST) rc = lin_alloc(h, &c.neu, (size_t)c.rows * F); });
+        LCHK(rc);
+        h->rob = g.rob;
         h->rob_alloc = true;
     }
     std::vector<int> hl(loss, loss + F);
-    std::vector<double> ht((size_t)F, 1.0), hn((size_t)F, 1.0);
+    std::vector<double> ht((size_t)F, LIN_NEW_THR), hn((size_t)F, LIN_NEW_NVAR);
     for (int f = 0; f < F; ++f) {
         if (loss[f] != GBP_LIN_LOSS_NONE) ht[f] = threshold[f];
         if (loss[f] == GBP_LIN_LOSS_CONSTANT) hn[f] = noise_var[f];

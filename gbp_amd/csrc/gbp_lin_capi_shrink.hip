@@ -9,8 +9,10 @@
 // frees what was allocated and leaves the handle as it was.  Host work and host <-> device traffic are proportional to the two lists,
 // plus the maps where the caller asks for them; no existing array crosses to the host.
 //
-// gbp_lin_shrink_nonlinear is the same call on a handle of gbp_lin_set_nonlinear: the five per-factor arrays of LinNonlin are gathered
-// through the same list of survivors.  Nothing relinearises; a folded message is the one its factor computed at its last
+// Which arrays are gathered through the list of surviving factors is not said here: shr_build walks lin_gen_columns.
+//
+// gbp_lin_shrink_nonlinear is the same call on a handle of gbp_lin_set_nonlinear: the per-factor arrays of LinNonlin are columns of the
+// same walk.  Nothing relinearises; a folded message is the one its factor computed at its last
 // linearisation point and is frozen in the prior from then on.
 #include "gbp_lin_shrink.hpp"
 #include "gbp_lin_generation.hpp"
@@ -46,10 +48,10 @@ int shr_check_list(const int32_t *ids, int count, int n, const char *what)
 }
 
 // everything up to and including the synchronisation after which nothing can fail: the new arrays, built on the device
-int shr_build(gbp_lin *h, const gbp_lin_shrink_desc_t *d, bool robust, LinScratch &mem, LinGen &n)
+int shr_build(gbp_lin *h, const gbp_lin_shrink_desc_t *d, LinScratch &mem, LinGen &n)
 {
     const LinParams &p = h->p;
-    const int D = h->D, D2 = 2 * D, P = D * (D + 1) / 2, P2 = D * (2 * D + 1), R = D + P, REC = D + P + D;
+    const int R = lin_rows(h->D).msg, REC = lin_rows(h->D).rec;
     const int N = p.N, F = p.F, nr = d->n_retire_vars, nd = d->n_drop_factors;
     const size_t total = (size_t)N + 3 * (size_t)F;             // the union index space [ N | F | 2F ], + 1 for the scan's total
 
@@ -86,39 +88,33 @@ int shr_build(gbp_lin *h, const gbp_lin_shrink_desc_t *d, bool robust, LinScratc
     // d_red stays: it holds ceil(F / 256) >= max(1, ceil(F' / 256)) partials, and the energy's launch goes by red_blocks (the nonlinear one too: lin_nonlin_energy)
     int *maps = nullptr, *surv_v = nullptr, *surv_f = nullptr;          // maps: [N | F] of before the call
     LCHK(mem.get(&maps, (size_t)N + F, false)); LCHK(mem.get(&surv_v, (size_t)N1, false)); LCHK(mem.get(&surv_f, (size_t)F1, false));
-    LCHK(lin_gen_alloc(h, mem, n, N1, F1, robust, false, h->nonlinear));
+    LCHK(lin_gen_alloc(h, mem, n, N1, F1));
+    int *nvptr = lin_mut(n.p.vptr), *nvadj = lin_mut(n.p.vadj), *nepos_a = lin_mut(n.p.epos_a), *nepos_b = lin_mut(n.p.epos_b);
 
     // ---- the maps and the lists of survivors ----
     const int *ckeep = keep, *cpos = pos, *csurv = surv_f, *cmaps = maps;
     if (N + F) hipLaunchKernelGGL(k_shr_maps, dim3(shr_blocks((size_t)N + F)), dim3(SHR_BLOCK), 0, h->stream, ckeep, cpos, N, F, maps, surv_v, surv_f);
-    // ---- factor-strided arrays: [row][F] -> [row][F1] ----
+    // ---- factor-strided arrays: [row][F] -> [row][F1], the survivors' rows gathered.  Not va / vb, whose entries are renumbered on
+    // the way (k_shr_ends), and not epos_a / epos_b: k_shr_edges below writes them ----
     if (F1) {
-        hipLaunchKernelGGL(k_shr_ends, dim3(shr_blocks((size_t)F1)), dim3(SHR_BLOCK), 0, h->stream, p.va, csurv, cmaps, n.va, F1);
-        hipLaunchKernelGGL(k_shr_ends, dim3(shr_blocks((size_t)F1)), dim3(SHR_BLOCK), 0, h->stream, p.vb, csurv, cmaps, n.vb, F1);
+        hipLaunchKernelGGL(k_shr_ends, dim3(shr_blocks((size_t)F1)), dim3(SHR_BLOCK), 0, h->stream, p.va, csurv, cmaps, lin_mut(n.p.va), F1);
+        hipLaunchKernelGGL(k_shr_ends, dim3(shr_blocks((size_t)F1)), dim3(SHR_BLOCK), 0, h->stream, p.vb, csurv, cmaps, lin_mut(n.p.vb), F1);
     }
-    shr_gather<double>(h, p.feta, csurv, n.feta, D2, F, F1); shr_gather<double>(h, p.flam, csurv, n.flam, P2, F, F1);
-    shr_gather<double>(h, p.fconst, csurv, n.fconst, 1, F, F1);
-    shr_gather<double>(h, p.msg_a, csurv, n.msg_a, R, F, F1); shr_gather<double>(h, p.msg_b, csurv, n.msg_b, R, F, F1);
-    if (robust) {
-        shr_gather<int>(h, h->rob.loss, csurv, n.loss, 1, F, F1); shr_gather<double>(h, h->rob.thr, csurv, n.thr, 1, F, F1);
-        shr_gather<double>(h, h->rob.nvar, csurv, n.nvar, 1, F, F1); shr_gather<double>(h, h->rob.w, csurv, n.w, 1, F, F1);
-        shr_gather<int>(h, h->rob.flag, csurv, n.flag, 1, F, F1);
-    }
-    if (h->nonlinear) {
-        shr_gather<double>(h, h->nl.meas, csurv, n.meas, NL_M, F, F1); shr_gather<double>(h, h->nl.sinfo, csurv, n.sinfo, NL_M, F, F1);
-        shr_gather<double>(h, h->nl.linpoint, csurv, n.linpoint, 2 * NL_D, F, F1);
-        shr_gather<int>(h, h->nl.iters, csurv, n.iters, 1, F, F1); shr_gather<double>(h, h->nl.fdamp, csurv, n.fdamp, 1, F, F1);
-    }
+    (void)&shr_gather<double>;      // instantiated ahead of <int>, which the walk meets first: the kernels keep their order in the code object
+    lin_gen_columns(h, n, [&](auto c) {
+        const bool own_kernel = c.id == LC_VA || c.id == LC_VB || c.id == LC_EPOS_A || c.id == LC_EPOS_B;
+        if (n.has(c.group) && !own_kernel) shr_gather(h, c.old, csurv, c.neu, c.rows, F, F1);
+    });
     LHIPCHK(hipGetLastError());
     // ---- the CSR of the survivors, the rows of vmsg with it ----
-    hipLaunchKernelGGL(k_shr_vptr, dim3(shr_blocks((size_t)N + 1)), dim3(SHR_BLOCK), 0, h->stream, ckeep, cpos, p.vptr, N, F, N1, n.vptr);
+    hipLaunchKernelGGL(k_shr_vptr, dim3(shr_blocks((size_t)N + 1)), dim3(SHR_BLOCK), 0, h->stream, ckeep, cpos, p.vptr, N, F, N1, nvptr);
     if (F)
-        hipLaunchKernelGGL(k_shr_edges, dim3(shr_blocks((size_t)2 * F * R)), dim3(SHR_BLOCK), 0, h->stream, ckeep, cpos, p.vadj, N, F, R, (const double *)p.vmsg, n.vadj,
-                           n.epos_a, n.epos_b, n.vmsg);
+        hipLaunchKernelGGL(k_shr_edges, dim3(shr_blocks((size_t)2 * F * R)), dim3(SHR_BLOCK), 0, h->stream, ckeep, cpos, p.vadj, N, F, R, (const double *)p.vmsg, nvadj,
+                           nepos_a, nepos_b, n.p.vmsg);
     // ---- the fold into the priors; the survivors' belief records ----
     if (N)
         hipLaunchKernelGGL(k_shr_fold, dim3(shr_blocks((size_t)N * REC)), dim3(SHR_BLOCK), 0, h->stream, ckeep, cpos, p.vptr, p.vadj, (const int *)fold_side, N, R, REC,
-                           p.prior, (const double *)p.vmsg, (const double *)p.bel, n.prior, n.bel);
+                           p.prior, (const double *)p.vmsg, (const double *)p.bel, lin_mut(n.p.prior), n.p.bel);
     LHIPCHK(hipGetLastError());
     if (d->var_map && N) LHIPCHK(hipMemcpyAsync(d->var_map, maps, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     if (d->factor_map && F) LHIPCHK(hipMemcpyAsync(d->factor_map, maps + N, (size_t)F * sizeof(int), hipMemcpyDeviceToHost, h->stream));
@@ -146,11 +142,12 @@ int shr_run(gbp_lin *h, const gbp_lin_shrink_desc_t *d)
         if (d->factor_map) for (int f = 0; f < h->p.F; ++f) d->factor_map[f] = f;
         return GBP_OK;
     }
-    const bool robust = h->p.w != nullptr;                  // a handle whose losses were cleared keeps stale arrays: they are freed, not carried
     LHIPCHK(hipStreamSynchronize(h->stream));
     LinScratch mem;
     LinGen n;
-    const int rc = shr_build(h, d, robust, mem, n);
+    n.robust = h->p.w != nullptr;                           // a handle whose losses were cleared keeps stale arrays: they are freed, not carried
+    n.nonlinear = h->nonlinear;
+    const int rc = shr_build(h, d, mem, n);
     if (rc != GBP_OK) {                                     // the handle's arrays were only read: it goes on as it was
         (void)hipStreamSynchronize(h->stream);              // before `mem` frees what the stream may still be writing
         return rc;

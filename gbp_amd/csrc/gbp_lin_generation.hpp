@@ -1,11 +1,14 @@
 // gbp_lin_generation.hpp -- host code only: what gbp_lin_create, gbp_lin_extend and gbp_lin_shrink (and the two calls that grow and
 // shrink a nonlinear handle, gbp_lin_extend_nonlinear / gbp_lin_shrink_nonlinear) share.  Each of them builds a complete
 // new GENERATION of the handle's graph arrays while the old one is only read, synchronises, and commits:
-//   LinScratch       the device memory of one call: `keep` becomes the handle's at the commit, `temp` goes with the call
-//   LinGen           the arrays of one generation; lin_gen_alloc is the one place that says which they are and how large each is
-//   lin_gen_commit   the one swap: frees the generation that is replaced, drops what a change of N or F invalidates, installs the new one
-// and the host routines that pack the caller's factors and priors and that check a list of losses.  The builds themselves stay with
-// their entry points: they are different algorithms (upload, sort-and-merge, scan-and-gather).
+//   LinScratch        the device memory of one call: `keep` becomes the handle's at the commit, `temp` goes with the call
+//   LinGen            the arrays of one generation, in the handle's own structs (LinParams, LinRobust, LinNonlin)
+//   lin_gen_columns   the one list of the arrays with stride F: rows, the value an appended factor starts with, the handle's old array.
+//                     lin_gen_alloc, lin_gen_commit, the restrides of extend, the gathers of shrink and the first allocations of
+//                     gbp_lin_set_robust / gbp_lin_set_nonlinear all walk it; lin_gen_others lists the five arrays of another stride
+//   lin_gen_commit    the one swap: frees the generation that is replaced, drops what a change of N or F invalidates, installs the new one
+// and the host routines that pack the caller's factors, priors and measurements and that check a list of losses or of measurements.
+// The builds themselves stay with their entry points: they are different algorithms (upload, sort-and-merge, scan-and-gather).
 #pragma once
 #include "gbp_lin_handle.hpp"
 
@@ -30,47 +33,99 @@ struct LinScratch {
     static void release(std::vector<void *> &v) { for (void *q : v) (void)hipFree(q); v.clear(); }
 };
 
-// the arrays that replace the handle's (LinParams, LinRobust and LinNonlin say what each holds)
+// rows of the SoA arrays and lengths of the records of a handle of d dofs (LinParams says which is which):
+// 2d; d(2d+1), packed upper 2d x 2d; d + d(d+1)/2, a message or a prior; that + d, a belief
+struct LinRows { int eta2, lam2, msg, rec; };
+inline LinRows lin_rows(int D) { return {2 * D, D * (2 * D + 1), D + D * (D + 1) / 2, D + D * (D + 1) / 2 + D}; }
+
+enum LinGroup { LIN_GRAPH, LIN_ROBUST, LIN_NONLIN };    // whose arrays: LinParams, LinRobust, LinNonlin
+enum LinCol { LC_VA, LC_VB, LC_FETA, LC_FLAM, LC_FCONST, LC_MSG_A, LC_MSG_B, LC_EPOS_A, LC_EPOS_B, LC_LOSS, LC_THR, LC_NVAR, LC_W, LC_FLAG,
+              LC_MEAS, LC_SINFO, LC_LINPOINT, LC_ITERS, LC_FDAMP, LC_COUNT };
+
+// What a factor holds before anything was said or computed about it: no loss (its threshold and variance are then not read), weight 1,
+// not flagged; and until the linearise pass (NL_INIT, gbp_lin_nonlin.hpp) writes the last three: a linearisation point of 0,
+// iters_since_relin 1, damping 0.  gbp_lin_set_robust and lin_gen_columns (the factors appended by an extend) both start from these.
+constexpr int LIN_NEW_LOSS = GBP_LIN_LOSS_NONE, LIN_NEW_FLAG = 0, LIN_NEW_ITERS = 1;
+constexpr double LIN_NEW_THR = 1.0, LIN_NEW_NVAR = 1.0, LIN_NEW_W = 1.0, LIN_NEW_SINFO = 1.0, LIN_NEW_FDAMP = 0.0;
+
+// the arrays that replace the handle's.  Of `p`, damping and w are the commit's to set; of `nl`, only the five per-factor arrays are used
 struct LinGen {
-    int N = 0, F = 0;
-    int *va = nullptr, *vb = nullptr, *vptr = nullptr, *vadj = nullptr, *epos_a = nullptr, *epos_b = nullptr;
-    double *feta = nullptr, *flam = nullptr, *fconst = nullptr, *msg_a = nullptr, *msg_b = nullptr, *bel = nullptr, *prior = nullptr, *vmsg = nullptr;
+    LinParams p{};
+    LinRobust rob{};
+    LinNonlin nl{};
     double *d_red = nullptr;                        // nullptr: the handle's stays
     int red_blocks = 0;
-    bool robust = false;                            // losses are set after the commit: the five arrays below exist
-    int *loss = nullptr, *flag = nullptr;
-    double *thr = nullptr, *nvar = nullptr, *w = nullptr;
-    bool nonlinear = false;                         // the handle is nonlinear: the five per-factor arrays below exist
-    double *meas = nullptr, *sinfo = nullptr, *linpoint = nullptr, *fdamp = nullptr;
-    int *iters = nullptr;
+    bool robust = false;                            // losses are set after the commit: rob's arrays exist
+    bool nonlinear = false;                         // the handle is nonlinear: nl's per-factor arrays exist
+    bool has(LinGroup grp) const { return grp == LIN_GRAPH || (grp == LIN_ROBUST ? robust : nonlinear); }
 };
 
-// Every array of a generation of N1 variables and F1 factors, nothing written yet.  grow_red: a larger d_red where ceil(F1 / 256)
-// exceeds what the handle has (a new handle has none).  nonlinear: the per-factor arrays of LinNonlin too (a nonlinear handle has d = 3).
-inline int lin_gen_alloc(gbp_lin *h, LinScratch &mem, LinGen &g, int N1, int F1, bool robust, bool grow_red, bool nonlinear = false)
+// a generation's arrays are its build's to write until the commit, whatever the kernels that read them later are promised
+template <typename T> T *lin_mut(const T *q) { return const_cast<T *>(q); }
+
+// One array [rows][F] of T.  old: the handle's as a build may read it, nullptr where the handle has none or where its copy is stale;
+// owned: the handle's as the commit frees it, nullptr where the handle has none; neu: the generation's; fill: what a factor appended
+// by an extend starts with where nothing is uploaded for it
+template <typename T> struct LinColumn {
+    LinCol id;
+    LinGroup group;
+    const T *old, *owned;
+    T *&neu;
+    int rows;
+    T fill;
+};
+
+// Every array with stride F, whether `g` has its group or not (LinGen::has): visit(LinColumn<int or double>).  A handle whose losses
+// were cleared keeps stale losses and weights in its robust arrays: its old factors are at NONE, so `old` is nullptr and the fill applies.
+template <typename V>
+void lin_gen_columns(const gbp_lin *h, LinGen &g, V &&visit)
 {
-    const size_t D = (size_t)h->D, P = D * (D + 1) / 2, P2 = D * (2 * D + 1), R = D + P, REC = D + P + D, N = (size_t)N1, F = (size_t)F1;
-    g.N = N1; g.F = F1; g.robust = robust;
-    LCHK(mem.get(&g.va, F, true)); LCHK(mem.get(&g.vb, F, true));
-    LCHK(mem.get(&g.feta, 2 * D * F, true)); LCHK(mem.get(&g.flam, P2 * F, true)); LCHK(mem.get(&g.fconst, F, true));
-    LCHK(mem.get(&g.msg_a, R * F, true)); LCHK(mem.get(&g.msg_b, R * F, true));
-    LCHK(mem.get(&g.bel, N * REC, true)); LCHK(mem.get(&g.prior, N * R, true));
-    LCHK(mem.get(&g.vptr, N + 1, true)); LCHK(mem.get(&g.vadj, 2 * F, true));
-    LCHK(mem.get(&g.epos_a, F, true)); LCHK(mem.get(&g.epos_b, F, true));
-    LCHK(mem.get(&g.vmsg, 2 * F * R, true));
+    const LinRows r = lin_rows(h->D);
+    const LinParams &o = h->p;
+    const LinRobust orob = h->rob_alloc ? h->rob : LinRobust{};
+    const LinNonlin onl = h->nonlinear ? h->nl : LinNonlin{};
+    auto col = [&](LinCol id, LinGroup grp, const auto *owned, auto *&neu, int rows, auto fill) {
+        using T = decltype(fill);
+        visit(LinColumn<T>{id, grp, grp == LIN_ROBUST && !o.w ? nullptr : owned, owned, const_cast<T *&>(neu), rows, fill});
+    };
+    col(LC_VA, LIN_GRAPH, o.va, g.p.va, 1, 0); col(LC_VB, LIN_GRAPH, o.vb, g.p.vb, 1, 0);
+    col(LC_FETA, LIN_GRAPH, o.feta, g.p.feta, r.eta2, 0.0); col(LC_FLAM, LIN_GRAPH, o.flam, g.p.flam, r.lam2, 0.0);
+    col(LC_FCONST, LIN_GRAPH, o.fconst, g.p.fconst, 1, 0.0);
+    col(LC_MSG_A, LIN_GRAPH, o.msg_a, g.p.msg_a, r.msg, 0.0); col(LC_MSG_B, LIN_GRAPH, o.msg_b, g.p.msg_b, r.msg, 0.0);
+    col(LC_EPOS_A, LIN_GRAPH, o.epos_a, g.p.epos_a, 1, 0); col(LC_EPOS_B, LIN_GRAPH, o.epos_b, g.p.epos_b, 1, 0);
+    col(LC_LOSS, LIN_ROBUST, orob.loss, g.rob.loss, 1, LIN_NEW_LOSS); col(LC_THR, LIN_ROBUST, orob.thr, g.rob.thr, 1, LIN_NEW_THR);
+    col(LC_NVAR, LIN_ROBUST, orob.nvar, g.rob.nvar, 1, LIN_NEW_NVAR); col(LC_W, LIN_ROBUST, orob.w, g.rob.w, 1, LIN_NEW_W);
+    col(LC_FLAG, LIN_ROBUST, orob.flag, g.rob.flag, 1, LIN_NEW_FLAG);
+    col(LC_MEAS, LIN_NONLIN, onl.meas, g.nl.meas, NL_M, 0.0); col(LC_SINFO, LIN_NONLIN, onl.sinfo, g.nl.sinfo, NL_M, LIN_NEW_SINFO);
+    col(LC_LINPOINT, LIN_NONLIN, onl.linpoint, g.nl.linpoint, 2 * NL_D, 0.0);
+    col(LC_ITERS, LIN_NONLIN, onl.iters, g.nl.iters, 1, LIN_NEW_ITERS); col(LC_FDAMP, LIN_NONLIN, onl.fdamp, g.nl.fdamp, 1, LIN_NEW_FDAMP);
+}
+
+// The arrays of a generation with another stride, for N = g.p.N and F = g.p.F: visit(the handle's, the generation's, elements)
+template <typename V>
+void lin_gen_others(const gbp_lin *h, LinGen &g, V &&visit)
+{
+    const LinRows r = lin_rows(h->D);
+    const size_t N = (size_t)g.p.N, F = (size_t)g.p.F;
+    visit(h->p.bel, g.p.bel, N * r.rec); visit(h->p.prior, const_cast<double *&>(g.p.prior), N * r.msg);
+    visit(h->p.vptr, const_cast<int *&>(g.p.vptr), N + 1); visit(h->p.vadj, const_cast<int *&>(g.p.vadj), 2 * F);
+    visit(h->p.vmsg, g.p.vmsg, 2 * F * r.msg);
+}
+
+// Every array of a generation of N1 variables and F1 factors, nothing written yet: the graph's, and those of the groups that g.robust
+// and g.nonlinear name (set by the caller).  d_red too where ceil(F1 / 256) exceeds what the handle has: a new handle has none, an
+// extend may pass it, and a shrink cannot (F1 <= F, and the handle holds at least ceil(F / 256)).
+inline int lin_gen_alloc(gbp_lin *h, LinScratch &mem, LinGen &g, int N1, int F1)
+{
+    g.p.N = N1; g.p.F = F1;
+    int rc = GBP_OK;
+    lin_gen_columns(h, g, [&](auto c) { if (rc == GBP_OK && g.has(c.group)) rc = mem.get(&c.neu, (size_t)c.rows * F1, true); });
+    lin_gen_others(h, g, [&](const auto *, auto *&neu, size_t n) { if (rc == GBP_OK) rc = mem.get(&neu, n, true); });
+    LCHK(rc);
     const int red_blocks = std::max(1, (F1 + 255) / 256);
-    if (grow_red && red_blocks > h->red_blocks) {
+    if (red_blocks > h->red_blocks) {
         LCHK(mem.get(&g.d_red, (size_t)red_blocks, true));
         g.red_blocks = red_blocks;
-    }
-    if (robust) {
-        LCHK(mem.get(&g.loss, F, true)); LCHK(mem.get(&g.thr, F, true)); LCHK(mem.get(&g.nvar, F, true));
-        LCHK(mem.get(&g.w, F, true)); LCHK(mem.get(&g.flag, F, true));
-    }
-    g.nonlinear = nonlinear;
-    if (nonlinear) {
-        LCHK(mem.get(&g.meas, NL_M * F, true)); LCHK(mem.get(&g.sinfo, NL_M * F, true)); LCHK(mem.get(&g.linpoint, 2 * NL_D * F, true));
-        LCHK(mem.get(&g.iters, F, true)); LCHK(mem.get(&g.fdamp, F, true));
     }
     return GBP_OK;
 }
@@ -101,37 +156,34 @@ inline void lin_drop_solvers(gbp_lin *h)
     h->until.nbel = h->until.nen = 0;
 }
 
-// The swap, after the synchronisation that ends the build of `g`: nothing here can fail.  The arrays that are replaced are freed and
+// LinNonlin::feta / flam -- what the relinearise stage writes -- are the handle's own factor arrays: set here, by whoever changes either
+inline void lin_nl_point(gbp_lin *h) { h->nl.feta = const_cast<double *>(h->p.feta); h->nl.flam = const_cast<double *>(h->p.flam); }
+
+// The swap, after the synchronisation that ends the build of `g`: nothing here can fail.  Every array that is replaced is freed and
 // taken out of `allocs` (a handle rebuilt a thousand times holds one generation) -- the robust ones of a handle whose losses were
-// cleared too: they are stale and not carried -- and the call's `temp` with them; `keep` becomes the handle's.  A nonlinear handle's
-// five per-factor arrays go the same way, and LinNonlin::feta / flam -- what the relinearise stage writes -- are re-pointed at the new
-// generation's factor arrays: the old ones are freed here.  The per-sweep counts buffer does not depend on F and stays.
-inline void lin_gen_commit(gbp_lin *h, LinScratch &mem, const LinGen &g)
+// cleared too: they are stale and not carried -- and the call's `temp` with them; `keep` becomes the handle's.  The parts of `g` are
+// installed whole; what does not belong to a generation stays as the handle has it: the damping, the nonlinear settings, and the
+// per-sweep counts buffer, which does not depend on F.
+inline void lin_gen_commit(gbp_lin *h, LinScratch &mem, LinGen &g)
 {
     LinScratch::release(mem.temp);
-    LinParams &p = h->p;
-    for (const void *q : {(const void *)p.va, (const void *)p.vb, (const void *)p.feta, (const void *)p.flam, (const void *)p.fconst, (const void *)p.msg_a,
-                          (const void *)p.msg_b, (const void *)p.bel, (const void *)p.prior, (const void *)p.vptr, (const void *)p.vadj, (const void *)p.vmsg,
-                          (const void *)p.epos_a, (const void *)p.epos_b})
-        lin_free(h, q);
-    if (h->rob_alloc)
-        for (const void *q : {(const void *)h->rob.loss, (const void *)h->rob.thr, (const void *)h->rob.nvar, (const void *)h->rob.w, (const void *)h->rob.flag}) lin_free(h, q);
-    if (g.nonlinear)
-        for (const void *q : {(const void *)h->nl.meas, (const void *)h->nl.sinfo, (const void *)h->nl.linpoint, (const void *)h->nl.iters, (const void *)h->nl.fdamp}) lin_free(h, q);
+    lin_gen_columns(h, g, [&](auto c) { lin_free(h, c.owned); });
+    lin_gen_others(h, g, [&](const auto *owned, auto *&, size_t) { lin_free(h, owned); });
     lin_drop_solvers(h);
     if (g.d_red) { lin_free(h, h->d_red); h->d_red = g.d_red; h->red_blocks = g.red_blocks; }
     h->allocs.insert(h->allocs.end(), mem.keep.begin(), mem.keep.end());
     mem.keep.clear();
-    p.N = g.N; p.F = g.F;
-    p.va = g.va; p.vb = g.vb; p.feta = g.feta; p.flam = g.flam; p.fconst = g.fconst; p.msg_a = g.msg_a; p.msg_b = g.msg_b;
-    p.bel = g.bel; p.prior = g.prior; p.vptr = g.vptr; p.vadj = g.vadj; p.vmsg = g.vmsg; p.epos_a = g.epos_a; p.epos_b = g.epos_b;
-    p.w = g.robust ? g.w : nullptr;
-    h->rob = g.robust ? LinRobust{g.loss, g.thr, g.nvar, g.w, g.flag} : LinRobust{};
+    g.p.damping = h->p.damping;
+    g.p.w = g.robust ? g.rob.w : nullptr;
+    h->p = g.p;
+    h->rob = g.rob;                                 // all nullptr where the generation has no losses
     h->rob_alloc = g.robust;
     if (g.nonlinear) {
-        LinNonlin &nl = h->nl;
-        nl.meas = g.meas; nl.sinfo = g.sinfo; nl.linpoint = g.linpoint; nl.iters = g.iters; nl.fdamp = g.fdamp;
-        nl.feta = g.feta; nl.flam = g.flam;
+        const LinNonlin &o = h->nl;
+        g.nl.counts = o.counts; g.nl.cap = o.cap;
+        g.nl.beta = o.beta; g.nl.num_undamped = o.num_undamped; g.nl.min_linear = o.min_linear; g.nl.model = o.model;
+        h->nl = g.nl;
+        lin_nl_point(h);
     }
 }
 
@@ -183,4 +235,23 @@ inline int lin_check_losses(const int32_t *loss, const double *thr, const double
         }
     }
     return GBP_OK;
+}
+
+// The rules for `count` measurements with their square-root informations, both [count][NL_M] (include/gbp_lin.h,
+// gbp_lin_set_nonlinear); `prefix` names a factor in the message.  Refused, entry by entry: a sqrt_info that is not positive and
+// finite, then a measurement that is not finite.
+inline int lin_check_measurements(const double *meas, const double *sinfo, int count, const char *prefix)
+{
+    for (size_t i = 0; i < (size_t)count * NL_M; ++i) {
+        if (!(sinfo[i] > 0.0) || !std::isfinite(sinfo[i])) return set_error(GBP_EINVAL, "%s %d: sqrt_info must be positive and finite", prefix, (int)(i / NL_M));
+        if (!std::isfinite(meas[i])) return set_error(GBP_EINVAL, "%s %d: the measurement must be finite", prefix, (int)(i / NL_M));
+    }
+    return GBP_OK;
+}
+
+// the same two lists -> SoA rows with stride `count`: out_meas, out_sinfo [NL_M][count]
+inline void lin_pack_measurements(int count, const double *meas, const double *sinfo, double *out_meas, double *out_sinfo)
+{
+    for (int f = 0; f < count; ++f)
+        for (int k = 0; k < NL_M; ++k) { out_meas[(size_t)k * count + f] = meas[(size_t)f * NL_M + k]; out_sinfo[(size_t)k * count + f] = sinfo[(size_t)f * NL_M + k]; }
 }

@@ -35,6 +35,35 @@ def _host_factors(factors, index):
     return va, vb, fe, fl, fc, loss, thr, nvar
 
 
+def _new_priors(prior_eta, prior_lam, D):
+    """(dN, prior_eta (dN, D), prior_lam (dN, D, D)) of an extend; None: no new variables."""
+    dN = 0 if prior_eta is None else f64(prior_eta).reshape(-1, D).shape[0]
+    pe = f64(np.zeros((0, D)) if prior_eta is None else prior_eta, (dN, D))
+    pl = f64(np.zeros((0, D, D)) if prior_lam is None else prior_lam, (dN, D, D))
+    return dN, pe, pl
+
+
+def _loss_arrays(loss, threshold, noise_var, count):
+    """(codes int32, thresholds, noise variances or None) of `count` factors from one loss name or `count` of them and scalars or
+    `count` values; at least one entry long, so that an empty list still is a non-NULL pointer."""
+    names = [loss] * count if isinstance(loss, str) else list(loss)
+    if len(names) != count:
+        raise ValueError(f"expected {count} losses, got {len(names)}")
+    bad = [l for l in names if l not in _capi.LIN_LOSS]
+    if bad:
+        raise ValueError(f"unknown loss {bad[0]!r}: None, 'huber' or 'constant'")
+    n = max(count, 1)
+    codes = np.zeros(n, dtype=np.int32)
+    codes[:count] = [_capi.LIN_LOSS[l] for l in names]
+    thr = np.ones(n)
+    thr[:count] = np.broadcast_to(np.asarray(threshold, dtype=np.float64), (count,))
+    nv = None
+    if noise_var is not None:
+        nv = np.ones(n)
+        nv[:count] = np.broadcast_to(np.asarray(noise_var, dtype=np.float64), (count,))
+    return codes, thr, nv
+
+
 class UntilResult:
     """What LinearEngine.iterate_until returns: iters (the deciding sweep, or max_iters), converged, reason (GBP_LIN_STOP_*:
     _capi.LIN_STOP_STEP, LIN_STOP_MAP, or LIN_STOP_NONE when max_iters ran out), and one value per sweep run: step, energy,
@@ -106,9 +135,7 @@ class LinearEngine:
         dF = var_a.shape[0]
         if var_b.shape[0] != dF:
             raise ValueError("var_a / var_b length mismatch")
-        dN = 0 if prior_eta is None else f64(prior_eta).reshape(-1, self.D).shape[0]
-        pe = f64(np.zeros((0, self.D)) if prior_eta is None else prior_eta, (dN, self.D))
-        pl = f64(np.zeros((0, self.D, self.D)) if prior_lam is None else prior_lam, (dN, self.D, self.D))
+        dN, pe, pl = _new_priors(prior_eta, prior_lam, self.D)
         fe = f64(np.asarray(factor_eta, dtype=np.float64).reshape(dF, 2 * self.D))
         fl = f64(np.asarray(factor_lam, dtype=np.float64).reshape(dF, 2 * self.D, 2 * self.D))
         fc = None if factor_const is None else f64(factor_const, (dF,))
@@ -119,16 +146,7 @@ class LinearEngine:
         d.prior_eta, d.prior_lam = dptr(pe), dptr(pl)
         keep = None
         if loss is not None and dF:
-            names = [loss] * dF if isinstance(loss, str) else list(loss)
-            if len(names) != dF:
-                raise ValueError(f"expected {dF} losses, got {len(names)}")
-            bad = [l for l in names if l not in _capi.LIN_LOSS]
-            if bad:
-                raise ValueError(f"unknown loss {bad[0]!r}: None, 'huber' or 'constant'")
-            codes = np.array([_capi.LIN_LOSS[l] for l in names], dtype=np.int32)
-            thr = np.ascontiguousarray(np.broadcast_to(np.asarray(threshold, dtype=np.float64), (dF,)))
-            nv = None if noise_var is None else np.ascontiguousarray(np.broadcast_to(np.asarray(noise_var, dtype=np.float64), (dF,)))
-            keep = (codes, thr, nv)
+            keep = codes, thr, nv = _loss_arrays(loss, threshold, noise_var, dF)
             d.loss, d.threshold, d.noise_var = iptr(codes), dptr(thr), dptr(nv)
         check(self._lib.gbp_lin_extend(self._h, ct.byref(d)))
         del keep
@@ -262,9 +280,7 @@ class LinearEngine:
             raise ValueError("var_a / var_b length mismatch")
         z = f64(np.asarray(measurement, dtype=np.float64).reshape(dF, 3))
         s = f64(np.ascontiguousarray(np.broadcast_to(np.asarray(sqrt_info, dtype=np.float64), (dF, 3))))
-        dN = 0 if prior_eta is None else f64(prior_eta).reshape(-1, self.D).shape[0]
-        pe = f64(np.zeros((0, self.D)) if prior_eta is None else prior_eta, (dN, self.D))
-        pl = f64(np.zeros((0, self.D, self.D)) if prior_lam is None else prior_lam, (dN, self.D, self.D))
+        dN, pe, pl = _new_priors(prior_eta, prior_lam, self.D)
         d = _capi.LinExtNonlinear(dN, dF, iptr(var_a), iptr(var_b), dptr(z), dptr(s), dptr(pe), dptr(pl))
         check(self._lib.gbp_lin_extend_nonlinear(self._h, ct.byref(d)))
         self.N, self.F = self.N + dN, self.F + dF
@@ -310,21 +326,7 @@ class LinearEngine:
         if loss is None:
             check(self._lib.gbp_lin_set_robust(self._h, None, None, None))
             return
-        names = [loss] * self.F if isinstance(loss, str) else list(loss)
-        if len(names) != self.F:
-            raise ValueError(f"expected {self.F} losses, got {len(names)}")
-        bad = [l for l in names if l not in _capi.LIN_LOSS]
-        if bad:
-            raise ValueError(f"unknown loss {bad[0]!r}: None, 'huber' or 'constant'")
-        n = max(self.F, 1)                                   # F = 0: still a non-NULL `loss`, which NULL would read as "clear"
-        codes = np.zeros(n, dtype=np.int32)
-        codes[:self.F] = [_capi.LIN_LOSS[l] for l in names]
-        thr = np.ones(n)
-        thr[:self.F] = np.broadcast_to(np.asarray(threshold, dtype=np.float64), (self.F,))
-        nv = None
-        if noise_var is not None:
-            nv = np.ones(n)
-            nv[:self.F] = np.broadcast_to(np.asarray(noise_var, dtype=np.float64), (self.F,))
+        codes, thr, nv = _loss_arrays(loss, threshold, noise_var, self.F)   # F = 0: still a non-NULL `loss`, which NULL would read as "clear"
         check(self._lib.gbp_lin_set_robust(self._h, iptr(codes), dptr(thr), dptr(nv)))
 
     def robustify_all_factors(self):

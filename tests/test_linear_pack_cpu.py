@@ -1,6 +1,7 @@
-"""The host routines that gbp_lin_create, gbp_lin_extend and gbp_lin_set_robust share (gbp_amd/csrc/gbp_lin_generation.hpp), compiled for
-the host through tests/hostmath/lin_pack_shim.hip and run on a CPU: packing factors and priors for upload against numpy.triu_indices,
-and the rules for a list of losses against the message of every refusal the header documents, for both callers' prefixes."""
+"""The host routines that gbp_lin_create, gbp_lin_extend, gbp_lin_set_robust, gbp_lin_set_nonlinear and gbp_lin_extend_nonlinear share
+(gbp_amd/csrc/gbp_lin_generation.hpp), compiled for the host through tests/hostmath/lin_pack_shim.hip and run on a CPU: packing factors
+and priors for upload against numpy.triu_indices, measurements against a numpy transpose, and the rules for a list of losses and for a
+list of measurements against the message of every refusal the header documents, for both callers' prefixes."""
 import ctypes as ct
 import os
 import shutil
@@ -33,6 +34,8 @@ def shim():
     so.lin_pack_factors_host.argtypes, so.lin_pack_factors_host.restype = [i, i, dp, dp, dp, dp], None
     so.lin_pack_priors_host.argtypes, so.lin_pack_priors_host.restype = [i, i, dp, dp, dp], None
     so.lin_check_losses_host.argtypes, so.lin_check_losses_host.restype = [ip, dp, dp, i, ct.c_char_p, ct.POINTER(ct.c_int)], i
+    so.lin_check_measurements_host.argtypes, so.lin_check_measurements_host.restype = [dp, dp, i, ct.c_char_p], i
+    so.lin_pack_measurements_host.argtypes, so.lin_pack_measurements_host.restype = [i, dp, dp, dp, dp], None
     so.lin_pack_last_error.argtypes, so.lin_pack_last_error.restype = [], ct.c_char_p
     return so
 
@@ -129,3 +132,68 @@ def test_valid_list_passes_and_sets_any(shim, prefix):
     assert (rc, any_, got) == (0, 1, "")
     rc, any_, got = check(shim, prefix, [NONE, NONE, HUBER], [0.0, 0.0, 3.0], None)
     assert (rc, any_, got) == (0, 1, "")
+
+
+# ---- measurements of the nonlinear factors: gbp_lin_set_nonlinear ("factor") and gbp_lin_extend_nonlinear ("new factor") ----
+MEAS_PREFIXES = ('factor', 'new factor')
+BAD_SINFO = [0.0, -2.0, np.nan, np.inf]
+BAD_MEAS = [np.nan, np.inf, -np.inf]
+
+
+def check_meas(so, prefix, z, s):
+    z, s = np.ascontiguousarray(z, dtype=np.float64), np.ascontiguousarray(s, dtype=np.float64)
+    rc = so.lin_check_measurements_host(dptr(z), dptr(s), z.shape[0], prefix.encode())
+    return rc, so.lin_pack_last_error().decode()
+
+
+def entries(count):
+    """the first, a middle and the last of the count * 3 entries"""
+    n = 3 * count
+    return sorted({0, n // 2, n - 1}) if n else []
+
+
+@pytest.mark.parametrize('count', [0, 1, 3])
+def test_measurements_are_packed_as_soa_rows(shim, count):
+    """out_meas and out_sinfo [3][count] are the transposes of the two [count][3] lists; the outputs start as NaN, so an entry not
+    written shows."""
+    rs = np.random.RandomState(200 + count)
+    z, s = rs.randn(count, 3), rs.rand(count, 3) + 0.5
+    oz, os_ = np.full((3, count), np.nan), np.full((3, count), np.nan)
+    shim.lin_pack_measurements_host(count, dptr(z), dptr(s), dptr(oz), dptr(os_))
+    assert np.array_equal(oz, z.T)
+    assert np.array_equal(os_, s.T)
+
+
+@pytest.mark.parametrize('prefix', MEAS_PREFIXES)
+@pytest.mark.parametrize('count', [0, 1, 3])
+def test_valid_measurements_pass(shim, count, prefix):
+    rs = np.random.RandomState(300 + count)
+    assert check_meas(shim, prefix, rs.randn(count, 3), rs.rand(count, 3) + 1e-300) == (0, "")
+
+
+@pytest.mark.parametrize('prefix', MEAS_PREFIXES)
+@pytest.mark.parametrize('count', [1, 3])
+def test_measurement_refusals_name_the_factor_with_the_callers_prefix(shim, count, prefix):
+    """A bad value in the first, a middle and the last entry: entry i belongs to factor i // 3.  (count = 0 has no entry to refuse: it
+    is among the cases of test_valid_measurements_pass.)"""
+    rs = np.random.RandomState(400 + count)
+    for i in entries(count):
+        for bad in BAD_SINFO:
+            z, s = rs.randn(count, 3), rs.rand(count, 3) + 0.5
+            s.reshape(-1)[i] = bad
+            assert check_meas(shim, prefix, z, s) == (EINVAL, f"{prefix} {i // 3}: sqrt_info must be positive and finite")
+        for bad in BAD_MEAS:
+            z, s = rs.randn(count, 3), rs.rand(count, 3) + 0.5
+            z.reshape(-1)[i] = bad
+            assert check_meas(shim, prefix, z, s) == (EINVAL, f"{prefix} {i // 3}: the measurement must be finite")
+
+
+@pytest.mark.parametrize('prefix', MEAS_PREFIXES)
+def test_measurement_refusals_go_entry_by_entry(shim, prefix):
+    """Within one entry sqrt_info is looked at before the measurement; across entries the earlier one is refused, whichever list it is in."""
+    z, s = np.zeros((3, 3)), np.ones((3, 3))
+    z[1, 1], s[1, 1] = np.nan, 0.0
+    assert check_meas(shim, prefix, z, s) == (EINVAL, f"{prefix} 1: sqrt_info must be positive and finite")
+    z, s = np.zeros((3, 3)), np.ones((3, 3))
+    z[0, 2], s[2, 0] = np.inf, -1.0
+    assert check_meas(shim, prefix, z, s) == (EINVAL, f"{prefix} 0: the measurement must be finite")
