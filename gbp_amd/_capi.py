@@ -178,6 +178,9 @@ SIGNATURES = {
     'gbp_lin_get_linearisation': (ct.c_int, [ct.c_void_p, _dp, _ip, _dp]),
     'gbp_lin_extend_nonlinear': (ct.c_int, [ct.c_void_p, ct.c_void_p]),
     'gbp_lin_shrink_nonlinear': (ct.c_int, [ct.c_void_p, ct.c_void_p]),
+    'gbp_lin_set_robust_nonlinear': (ct.c_int, [ct.c_void_p, ct.c_int32, ct.c_int32, _ip, _dp]),
+    'gbp_lin_robustify_nonlinear': (ct.c_int, [ct.c_void_p]),
+    'gbp_lin_iterate_nonlinear_robust': (ct.c_int, [ct.c_void_p, ct.c_int32, _ip, _ip]),
     'gbp_ba_get_lmk_order': (ct.c_int, [ct.c_void_p, _ip]),
     'gbp_ba_fused_max_cams': (ct.c_int, []),
     'gbp_ba_plan_info': (ct.c_int, [ct.c_void_p, _ip, ct.c_int32]),

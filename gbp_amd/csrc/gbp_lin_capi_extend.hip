@@ -241,7 +241,10 @@ int gbp_lin_extend_nonlinear(gbp_lin_t *h, const gbp_lin_extend_nonlinear_desc_t
     if (dF && (!nl->measurement || !nl->sqrt_info)) return set_error(GBP_EINVAL, "NULL array in the descriptor");
     LCHK(lin_check_measurements(nl->measurement, nl->sqrt_info, dF, "new factor"));    // the rules of gbp_lin_set_nonlinear
     if (!nl->n_new_vars && !dF) return GBP_OK;
-    LCHK(ext_run(h, &d, nl, false));                        // ends with the belief stage: a nonlinear handle has beliefs
+    // Losses (gbp_lin_set_robust_nonlinear) stay set: the old factors carry loss, threshold, weight and flag, the new ones start at the
+    // columns' fills -- NONE, weight 1, flag 0 -- until that call gives them a loss by range.  Ends with the belief stage: a nonlinear
+    // handle has beliefs
+    LCHK(ext_run(h, &d, nl, h->p.w != nullptr));
     // compute_factor on the new factors only (gbp.py:267-294), at the belief means as that stage left them; the joint is stale already
     return lin_nonlin_linearise(h, F, F + dF);
 }

@@ -6,7 +6,8 @@
 // batch MAP and the marginals read the factor "at the current linearisation point" (gbp.py:96-97) without knowing.  What is added per
 // factor: measurement and square-root information, the linearisation point, iters_since_relin and the factor's damping.  A sweep is
 // three kernels queued on the handle's stream (k_lin_relin, k_lin_factor<3, false, LinRelin>, k_lin_belief): no host round trip; the
-// only atomics are integer adds of the per-sweep counts.  Every call that may relinearise clears map_ready, as a change of robust
+// only atomics are integer adds of the per-sweep counts.  With losses set (gbp_lin_capi_nonlin_robust.hip) the factor stage is
+// k_lin_factor<3, true, LinRelin>, at the weights as they stand.  Every call that may relinearise clears map_ready, as a change of robust
 // weights does.  The five per-factor arrays are the nonlinear columns of a generation (lin_gen_columns, gbp_lin_generation.hpp):
 // gbp_lin_set_nonlinear allocates them through that list, and extend / shrink rebuild them with the graph's.
 #include "gbp_lin_generation.hpp"
@@ -23,30 +24,42 @@ int nl_check_state(gbp_lin *h)
     return GBP_OK;
 }
 
-// a counts buffer of at least n slots
-int nl_counts(gbp_lin *h, int n)
-{
-    LinNonlin &nl = h->nl;
-    if (n > nl.cap) {
-        int *c = nullptr;
-        LCHK(lin_alloc(h, &c, (size_t)n));
-        lin_free(h, nl.counts);                             // no call is in flight: every call that counts ends in a synchronisation
-        nl.counts = c;
-        nl.cap = n;
-    }
-    return GBP_OK;
-}
+// the buffer of the relinearisation counts, of at least n slots
+int nl_counts(gbp_lin *h, int n) { return lin_nonlin_grow_counts(h, h->nl.counts, h->nl.cap, n); }
 
 // the relinearise stage (mode: gbp_lin_nonlin.hpp), counted into `count` (nullptr: not counted)
 void nl_relin(gbp_lin *h, int mode, int *count)
 {
     if (!h->p.F) return;
-    hipLaunchKernelGGL((k_lin_relin<GBP_LIN_MODEL_SE2_BETWEEN>), dim3((h->p.F + 255) / 256), dim3(256), 0, h->stream, h->p, h->nl, mode, count);
+    hipLaunchKernelGGL((k_lin_relin<GBP_LIN_MODEL_SE2_BETWEEN>), dim3((h->p.F + 255) / 256), dim3(256), 0, h->stream, h->p, h->nl, mode, count, LinRobust{},
+                       (int *)nullptr);
 }
 
 }  // namespace
 
 namespace gbp {
+// a per-sweep counts buffer of at least n slots: grown by replacement, so the handle's allocation count stays
+int lin_nonlin_grow_counts(gbp_lin *h, int *&buf, int &cap, int n)
+{
+    if (n > cap) {
+        int *c = nullptr;
+        LCHK(lin_alloc(h, &c, (size_t)n));
+        lin_free(h, buf);                                   // no call is in flight: every call that counts ends in a synchronisation
+        buf = c;
+        cap = n;
+    }
+    return GBP_OK;
+}
+
+// the factor stage of a relinearising sweep: every factor with ITS damping (gbp.py:52), and with losses set times its weight as it stands
+void lin_nonlin_factor_stage(gbp_lin *h)
+{
+    if (!h->p.F) return;
+    const LinRelin r{h->p, h->nl.fdamp};
+    if (h->p.w) hipLaunchKernelGGL((k_lin_factor<NL_D, true, LinRelin>), dim3((h->p.F + 63) / 64), dim3(64), 0, h->stream, r);
+    else hipLaunchKernelGGL((k_lin_factor<NL_D, false, LinRelin>), dim3((h->p.F + 63) / 64), dim3(64), 0, h->stream, r);
+}
+
 int lin_nonlin_energy(gbp_lin *h, double *out)
 {
     // over red_blocks blocks, as k_lin_energy: the caller adds up red_blocks partials, and after a shrink that is more than
@@ -79,7 +92,7 @@ int gbp_lin_set_nonlinear(gbp_lin_t *h, const gbp_lin_nonlinear_desc_t *d)
     if (!(d->beta >= 0.0)) return set_error(GBP_EINVAL, "beta must not be negative (+inf: never relinearise)");
     if (F && (!d->measurement || !d->sqrt_info)) return set_error(GBP_EINVAL, "NULL array in the descriptor");
     LCHK(lin_check_measurements(d->measurement, d->sqrt_info, F, "factor"));
-    if (h->p.w) return set_error(GBP_ESTATE, "losses are set: robust nonlinear factors are not supported");
+    if (h->p.w) return set_error(GBP_ESTATE, "losses of gbp_lin_set_robust are set: a nonlinear handle takes its losses afterwards, from gbp_lin_set_robust_nonlinear");
     if (h->nonlinear) return set_error(GBP_ESTATE, "the handle already has nonlinear factors");
 
     std::vector<double> z((size_t)NL_M * F), s((size_t)NL_M * F);     // SoA, stride F
@@ -91,6 +104,7 @@ int gbp_lin_set_nonlinear(gbp_lin_t *h, const gbp_lin_nonlinear_desc_t *d)
     LinNonlin &nl = g.nl;
     LCHK(lin_alloc(h, &nl.counts, 1));
     nl.cap = 1;
+    nl.rcounts = nullptr; nl.rcap = 0;                      // allocated with the robust arrays (gbp_lin_set_robust_nonlinear)
     nl.beta = d->beta; nl.num_undamped = d->num_undamped_iters; nl.min_linear = d->min_linear_iters; nl.model = d->model;
     if (F) {
         LHIPCHK(hipMemcpyAsync(lin_mut(nl.meas), z.data(), z.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -132,10 +146,9 @@ int gbp_lin_iterate_nonlinear(gbp_lin_t *h, int32_t n_iters, int32_t *relin_coun
     const LinNonlin &nl = h->nl;
     LHIPCHK(hipMemsetAsync(nl.counts, 0, (size_t)n_iters * sizeof(int), h->stream));
     h->map_ready = false;                                   // the joint is that of the new linearisation point
-    const LinRelin r{h->p, nl.fdamp};
     for (int it = 0; it < n_iters; ++it) {
         nl_relin(h, NL_SWEEP, nl.counts + it);
-        if (h->p.F) hipLaunchKernelGGL((k_lin_factor<NL_D, false, LinRelin>), dim3((h->p.F + 63) / 64), dim3(64), 0, h->stream, r);
+        lin_nonlin_factor_stage(h);                         // with losses set: at the weights as they stand (robustify=False)
         LCHK(gbp_lin_update_beliefs(h));
     }
     LHIPCHK(hipGetLastError());

@@ -163,7 +163,7 @@ inline void lin_nl_point(gbp_lin *h) { h->nl.feta = const_cast<double *>(h->p.fe
 // taken out of `allocs` (a handle rebuilt a thousand times holds one generation) -- the robust ones of a handle whose losses were
 // cleared too: they are stale and not carried -- and the call's `temp` with them; `keep` becomes the handle's.  The parts of `g` are
 // installed whole; what does not belong to a generation stays as the handle has it: the damping, the nonlinear settings, and the
-// per-sweep counts buffer, which does not depend on F.
+// per-sweep counts buffers, which do not depend on F.
 inline void lin_gen_commit(gbp_lin *h, LinScratch &mem, LinGen &g)
 {
     LinScratch::release(mem.temp);
@@ -180,7 +180,7 @@ inline void lin_gen_commit(gbp_lin *h, LinScratch &mem, LinGen &g)
     h->rob_alloc = g.robust;
     if (g.nonlinear) {
         const LinNonlin &o = h->nl;
-        g.nl.counts = o.counts; g.nl.cap = o.cap;
+        g.nl.counts = o.counts; g.nl.cap = o.cap; g.nl.rcounts = o.rcounts; g.nl.rcap = o.rcap;
         g.nl.beta = o.beta; g.nl.num_undamped = o.num_undamped; g.nl.min_linear = o.min_linear; g.nl.model = o.model;
         h->nl = g.nl;
         lin_nl_point(h);

@@ -13,6 +13,8 @@
 //   gbp_lin_capi_nonlin.hip  nonlinear pairwise factors relinearised on the device (kernels in gbp_lin_nonlin.hpp): the relinearise stage,
 //                            the factor stage with per-factor damping (parameter block LinRelin below), the model-aware energy; growing and
 //                            shrinking such a handle are gbp_lin_extend_nonlinear / gbp_lin_shrink_nonlinear in the extend / shrink units
+//   gbp_lin_capi_nonlin_robust.hip  robust losses on such a handle: the weight made at the linearisation point by the relinearise lane
+//                            (k_lin_relin<MODEL, true>), and the factor stage with weight and per-factor damping together
 #pragma once
 #include "../../include/gbp_ba.h"
 #include "../../include/gbp_lin.h"
@@ -101,6 +103,8 @@ struct LinNonlin {
     double *feta, *flam;             // what the relinearise stage rewrites
     int *counts;                     // [cap] factors relinearised per sweep of the call in progress
     int cap;                         // the largest n_iters seen (at least 1)
+    int *rcounts;                    // [rcap] factors flagged per sweep of gbp_lin_iterate_nonlinear_robust; allocated with the robust arrays
+    int rcap;                        // the largest n_iters that call has seen (at least 1 once losses were set; 0 before)
     double beta;                     // FactorGraph.beta gbp.py:32
     int num_undamped, min_linear;    // gbp.py:33-34
     int model;                       // GBP_LIN_MODEL_*
@@ -172,6 +176,8 @@ int lin_map_prepare(gbp_lin *h);                    // gbp_lin_capi_map.hip: Lin
 int lin_sweep(gbp_lin *h);                          // gbp_lin_capi.hip: one synchronous iteration at the weights as they stand, queued on the stream
 int lin_nonlin_energy(gbp_lin *h, double *out);     // gbp_lin_capi_nonlin.hip: red_blocks partials (one per block of 256 factors, 0 past F) into `out` = d_red, queued on the stream
 int lin_nonlin_linearise(gbp_lin *h, int f0, int f1);   // gbp_lin_capi_nonlin.hip: compute_factor on the factors [f0, f1) at their belief means, queued
+void lin_nonlin_factor_stage(gbp_lin *h);           // gbp_lin_capi_nonlin.hip: the factor stage with per-factor damping, at the weights as they stand (if any), queued
+int lin_nonlin_grow_counts(gbp_lin *h, int *&buf, int &cap, int n);   // gbp_lin_capi_nonlin.hip: a per-sweep counts buffer of at least n slots
 }
 
 // the entry points that a nonlinear handle refuses (include/gbp_lin.h): decided before anything changes

@@ -13,11 +13,19 @@
 //                          switch of gbp.py:50-51
 //   k_lin_relin<MODEL>     that over every factor; the relinearised factors of a wave are counted by a popcount and ONE integer atomic add
 //   k_lin_relin_range<MODEL>  that over a range of factors (the ones gbp_lin_extend_nonlinear appended), uncounted
-//   k_lin_energy_nl<MODEL> sum_f 0.5 |h(mu) - diag(s) z|^2 at the belief means, in the block / partials shape of k_lin_energy
-// The factor stage of such a sweep is k_lin_factor<3, false, LinRelin> (gbp_lin_sweep.hpp), instantiated in gbp_lin_capi_nonlin.hip.
+//   k_lin_energy_nl<MODEL> sum_f w_f 0.5 |h(mu) - diag(s) z|^2 at the belief means (w_f = 1 without losses), in the block / partials
+//                          shape of k_lin_energy
+// Robust losses on such factors (include/gbp_lin.h, gbp_lin_set_robust_nonlinear):
+//   nonlin_mahalanobis2<MODEL>   |diag(s) z - h(x)|^2 at a point;
+//   nonlin_robustify_one<MODEL>  w_f and the flag of one factor from M at its LINPOINT (gbp.py:309), through lin_robust_weight;
+//   lin_relin_one / k_lin_relin <MODEL, true>   the same lane with that in front: robustify and relinearise are both one lane per
+//                          factor on the same linpoint, z and s, so the robust sweep stays at three launches.
+// The factor stage of such a sweep is k_lin_factor<3, false, LinRelin>, with losses set k_lin_factor<3, true, LinRelin> (gbp_lin_sweep.hpp),
+// both instantiated in gbp_lin_capi_nonlin.hip.
 // The model routines are host/device, so a host program can run them.
 #pragma once
 #include "gbp_lin_handle.hpp"
+#include "gbp_lin_robust.hpp"
 #include "gbp_math.hpp"
 
 namespace gbp {
@@ -26,6 +34,7 @@ namespace gbp {
 constexpr int NL_SWEEP = 0;                               // the stage of a sweep: test, iters, damping switch
 constexpr int NL_ALONE = 1;                               // relinearise_factors alone (gbp.py:64-80): no damping switch
 constexpr int NL_INIT = 2;                                // compute_all_factors (gbp.py:60-62): every factor, iters = 1, damping = 0
+constexpr int NL_ROBUSTIFY = 3;                           // robustify_all_factors alone (gbp.py:82-84): k_lin_relin<MODEL, true> only
 
 template <int MODEL> struct NonlinModel;
 
@@ -90,16 +99,60 @@ GBP_HD void nonlin_factor(const double (&x)[6], const double (&z)[3], const doub
     }
 }
 
+// |diag(s) z - h(x)|^2 at a point: the squared Mahalanobis distance of Factor.robustify_loss (gbp.py:312, 322) with noise variance 1
+template <int MODEL>
+GBP_HD double nonlin_mahalanobis2(const double (&x)[6], const double (&z)[3], const double (&s)[3])
+{
+    double sn, c, h[3], m2 = 0.0;
+    sincos(x[2], &sn, &c);
+    NonlinModel<MODEL>::h(x, s, c, sn, h);
+#pragma unroll
+    for (int k = 0; k < NL_M; ++k) { const double r = s[k] * z[k] - h[k]; m2 += r * r; }
+    return m2;
+}
+
+// Factor.robustify_loss (gbp.py:296-332) of nonlinear factor f, one lane: h is evaluated at Factor.linpoint (gbp.py:309) AS IT STANDS,
+// which is the reference's reading -- here the linpoint moves with every relinearisation.  Writes w_f and the flag with plain vector
+// stores; a factor without a loss loads nothing but its loss.  Returns the flag.
+template <int MODEL>
+GBP_DEV bool nonlin_robustify_one(const LinParams &p, const LinNonlin &n, const LinRobust &r, int f)
+{
+    const size_t F = (size_t)p.F;
+    const int loss = r.loss[f];
+    int flag = 0;
+    double w = 1.0;
+    if (loss != GBP_LIN_LOSS_NONE) {
+        double x[6], z[3], s[3];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) x[k] = n.linpoint[k * F + f];
+#pragma unroll
+        for (int k = 0; k < NL_M; ++k) { z[k] = n.meas[k * F + f]; s[k] = n.sinfo[k * F + f]; }
+        w = lin_robust_weight(loss, r.thr[f], 1.0, 0.5 * nonlin_mahalanobis2<MODEL>(x, z, s), flag);
+    }
+    r.w[f] = w;
+    r.flag[f] = flag;
+    return flag != 0;
+}
+
 // The relinearise stage for factor f, one lane: shared by the two kernels below so that a factor linearised over a range comes out bit
 // for bit as one linearised with the whole graph.  A lane that does not relinearise writes iters only (and its damping in the sweep in
 // which that switches); a relinearising lane writes the 6 + 21 doubles of the factor, the 6 of the linpoint, iters and its damping.  A
 // lane that is not `live` neither loads nor stores.  Returns whether the factor was relinearised.
-template <int MODEL>
-GBP_DEV bool lin_relin_one(const LinParams &p, const LinNonlin &n, int mode, int f, bool live)
+// ROBUST (losses are set): the lane FIRST makes w_f and the flag from the linpoint as it stands (robustify_all_factors comes before
+// relinearise_factors in synchronous_iteration, gbp.py:87-90), then runs the test and the re-make below unchanged -- the re-made factor
+// is the nominal one, and the weight stays.  In mode NL_ROBUSTIFY that is all it does.  `flagged`: whether the factor was flagged.
+// The `false` instantiation reads nothing of `r` and is the code of a handle without losses.
+template <int MODEL, bool ROBUST = false>
+GBP_DEV bool lin_relin_one(const LinParams &p, const LinNonlin &n, const LinRobust &r, int mode, int f, bool live, bool &flagged)
 {
     constexpr int D = NL_D, P = LinDims<D>::P, REC = LinDims<D>::REC;
     const size_t F = (size_t)p.F;
     bool relin = false;
+    flagged = false;
+    if constexpr (ROBUST) {
+        if (live) flagged = nonlin_robustify_one<MODEL>(p, n, r, f);
+        if (mode == NL_ROBUSTIFY) return false;
+    }
     if (live) {
         const double *ma = p.bel + (size_t)p.va[f] * REC + D + P, *mb = p.bel + (size_t)p.vb[f] * REC + D + P;
         double x[6];
@@ -135,14 +188,23 @@ GBP_DEV bool lin_relin_one(const LinParams &p, const LinNonlin &n, int mode, int
 
 // One lane per factor of the graph.  Lanes past F neither load nor store.  `count`: the slot of this sweep (nullptr for NL_INIT): one
 // integer atomic add per wave that relinearised anything.
-template <int MODEL>
-__global__ __launch_bounds__(256) void k_lin_relin(LinParams p, LinNonlin n, int mode, int *count)
+// ROBUST: the fused robustify + relinearise lane; `r` is read and `rcount` counted (the same way: one ballot, one popcount, one integer
+// atomic add per wave that flagged anything) under it only.
+template <int MODEL, bool ROBUST = false>
+__global__ __launch_bounds__(256) void k_lin_relin(LinParams p, LinNonlin n, int mode, int *count, LinRobust r, int *rcount)
 {
     const int f = blockIdx.x * 256 + threadIdx.x;
-    const bool relin = lin_relin_one<MODEL>(p, n, mode, f, f < p.F);
+    bool flagged;
+    const bool relin = lin_relin_one<MODEL, ROBUST>(p, n, r, mode, f, f < p.F, flagged);
     if (count) {
         const unsigned long long who = __ballot(relin);
         if ((threadIdx.x & 63) == 0 && who) atomicAdd(count, __popcll(who));
+    }
+    if constexpr (ROBUST) {
+        if (rcount) {
+            const unsigned long long who = __ballot(flagged);
+            if ((threadIdx.x & 63) == 0 && who) atomicAdd(rcount, __popcll(who));
+        }
     }
 }
 
@@ -153,7 +215,8 @@ template <int MODEL>
 __global__ __launch_bounds__(256) void k_lin_relin_range(LinParams p, LinNonlin n, int mode, int f0, int f1)
 {
     const int f = f0 + blockIdx.x * 256 + threadIdx.x;
-    (void)lin_relin_one<MODEL>(p, n, mode, f, f < f1);
+    bool flagged;
+    (void)lin_relin_one<MODEL>(p, n, LinRobust{}, mode, f, f < f1, flagged);
 }
 
 // sum_f 0.5 |h(mu) - diag(s) z|^2 at the current belief means (gbp.py:36-44, 251-265): one partial per block, the lanes of a wave and
@@ -174,6 +237,7 @@ __global__ __launch_bounds__(256) void k_lin_energy_nl(LinParams p, LinNonlin n,
 #pragma unroll
         for (int k = 0; k < NL_M; ++k) { z[k] = n.meas[k * F + f]; s[k] = n.sinfo[k * F + f]; }
         e = nonlin_energy<MODEL>(x, z, s);
+        if (p.w) e *= p.w[f];                               // the weighted form (gbp.py:43): sigma^2 / adaptive_gauss_noise_var, as k_lin_energy
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) e += __shfl_down(e, off, 64);

@@ -234,10 +234,15 @@ class LinearEngine:
         """n sweeps; robustify=True: every sweep re-makes the weights first (synchronous_iteration(robustify=True) gbp.py:86-92).
         relinearise=True (a handle of se2_pose_graph): n x synchronous_iteration(local_relin=True) -- every sweep relinearises the
         factors whose belief means left their linearisation point by more than beta, and every factor has its own damping
-        (gbp.py:46-54, 64-80); returns the number of factors relinearised in each sweep, (n,) int32, counted on the device."""
+        (gbp.py:46-54, 64-80); returns the number of factors relinearised in each sweep, (n,) int32, counted on the device.
+        Both (losses from set_robust on such a handle): n x synchronous_iteration(local_relin=True, robustify=True) -- every sweep
+        first re-makes the weights at the linearisation points as they stand, then relinearises; returns (relin_counts,
+        robust_counts), the second the number of factors flagged in each sweep."""
         if relinearise:
             if robustify:
-                raise ValueError("robust nonlinear factors are not supported")
+                counts, flagged = np.zeros(max(int(n), 1), dtype=np.int32), np.zeros(max(int(n), 1), dtype=np.int32)
+                check(self._lib.gbp_lin_iterate_nonlinear_robust(self._h, int(n), iptr(counts), iptr(flagged)))
+                return counts[:max(int(n), 0)], flagged[:max(int(n), 0)]
             counts = np.zeros(max(int(n), 1), dtype=np.int32)
             check(self._lib.gbp_lin_iterate_nonlinear(self._h, int(n), iptr(counts)))
             return counts[:max(int(n), 0)]
@@ -319,10 +324,24 @@ class LinearEngine:
         return n.value
 
     # robust losses (Factor(loss=, mahalanobis_threshold=), Factor.robustify_loss gbp.py:296-332): one weight per factor
-    def set_robust(self, loss, threshold=2.0, noise_var=None):
+    def set_robust(self, loss, threshold=2.0, noise_var=None, first=0):
         """Per-factor losses: None, 'huber' or 'constant' (a scalar or F of them), Mahalanobis threshold(s), and -- for the constant
         loss -- the factors' noise variance(s).  loss=None clears every loss: the handle is back on the plain path.  Resets the weights
-        to 1; they are re-made from the current belief means by robustify_all_factors() / iterate(n, robustify=True)."""
+        to 1; they are re-made from the current belief means by robustify_all_factors() / iterate(n, robustify=True).
+        On an engine of se2_pose_graph the losses are those of factors first, first + 1, ... (a list: that many; one name: every
+        factor from `first` on), whose weights are reset while every other factor keeps loss, threshold and weight; the weights are
+        re-made at the LINEARISATION POINTS (gbp.py:309) by robustify_all_factors() / iterate(n, robustify=True, relinearise=True);
+        the whitened model needs no noise_var."""
+        if self._nonlinear:
+            if loss is None:
+                check(self._lib.gbp_lin_set_robust_nonlinear(self._h, 0, self.F, None, None))
+                return
+            count = self.F - int(first) if isinstance(loss, str) else len(list(loss))
+            codes, thr, _ = _loss_arrays(loss, threshold, None, max(count, 0))
+            check(self._lib.gbp_lin_set_robust_nonlinear(self._h, int(first), count, iptr(codes), dptr(thr)))
+            return
+        if first:
+            raise ValueError("a range of losses (first != 0) is for an engine of se2_pose_graph")
         if loss is None:
             check(self._lib.gbp_lin_set_robust(self._h, None, None, None))
             return
@@ -330,7 +349,7 @@ class LinearEngine:
         check(self._lib.gbp_lin_set_robust(self._h, iptr(codes), dptr(thr), dptr(nv)))
 
     def robustify_all_factors(self):
-        check(self._lib.gbp_lin_robustify(self._h))
+        check((self._lib.gbp_lin_robustify_nonlinear if self._nonlinear else self._lib.gbp_lin_robustify)(self._h))
 
     def weights(self):
         """(w (F,), robust_flag (F,) bool): sigma^2 / adaptive_gauss_noise_var and Factor.robust_flag of every factor."""

@@ -18,7 +18,8 @@
  * chosen variables), both by block-Jacobi conjugate gradients on the block-sparse joint; robust losses; growing and shrinking a live
  * graph; sweeps to convergence with the stop decided on the device (gbp_lin_iterate_until); and one NONLINEAR factor family, the SE(2)
  * relative-pose factor, relinearised on the device by the reference's local schedule (gbp_lin_set_nonlinear), on a handle that grows
- * and shrinks too (gbp_lin_extend_nonlinear / gbp_lin_shrink_nonlinear) -- below.
+ * and shrinks too (gbp_lin_extend_nonlinear / gbp_lin_shrink_nonlinear) and takes robust losses of its own, made at the linearisation
+ * point as the reference makes them (gbp_lin_set_robust_nonlinear / gbp_lin_iterate_nonlinear_robust) -- below.
  */
 #ifndef GBP_LIN_H
 #define GBP_LIN_H
@@ -312,7 +313,8 @@ int  gbp_lin_get_alloc_count(gbp_lin_t *h, int32_t *count);
  *                            LDL^T and joint eta stale, as a change of robust weights does; a solve after it is one Gauss-Newton step;
  *   gbp_lin_set_robust, gbp_lin_robustify, gbp_lin_iterate_robust, gbp_lin_iterate_until, gbp_lin_extend, gbp_lin_shrink
  *                            GBP_ESTATE with a message; nothing changes.  (gbp_lin_extend takes eta_f, Lambda_f, which a nonlinear
- *                            handle owns: such a handle grows and shrinks through the two calls below.)
+ *                            handle owns: such a handle grows and shrinks through the two calls below; the first three take M at the
+ *                            belief means: such a handle has its losses from gbp_lin_set_robust_nonlinear, further below.)
  * No floating-point atomics: two identical call sequences on two handles are bit-identical, counts included. */
 #define GBP_LIN_MODEL_SE2_BETWEEN 1
 typedef struct {
@@ -363,6 +365,53 @@ typedef struct {
 } gbp_lin_extend_nonlinear_desc_t;
 int  gbp_lin_extend_nonlinear(gbp_lin_t *h, const gbp_lin_extend_nonlinear_desc_t *d);   /* appends + gbp.py:56-58 + compute_factor gbp.py:267-294 on the new factors */
 int  gbp_lin_shrink_nonlinear(gbp_lin_t *h, const gbp_lin_shrink_desc_t *d);
+
+/* ---- robust losses on a NONLINEAR handle: Factor(loss=, mahalanobis_threshold=) on FactorGraph(nonlinear_factors=True) and
+ * synchronous_iteration(local_relin=True, robustify=True) (gbp.py:86-92) -- odometry clean, loop closures with a loss ----
+ * For a nonlinear factor robustify_loss evaluates meas_fn at Factor.linpoint, NOT at the belief means (gbp.py:309), and the linpoint
+ * moves with every relinearisation: the reference is read literally here (the linear path above departs from it because a linear
+ * factor's linpoint never moves).  With the whitened model of gbp_lin_set_nonlinear the noise variance is 1:
+ *   M_f = | diag(s_f) z_f - h(linpoint_f) |_2                                                            (gbp.py:312, 322)
+ *   loss huber    : w_f = (2 t M - t^2) / M^2  if M > t, else 1                                          (gbp.py:313-319)
+ *   loss constant : w_f = 1 / M^2              if M > t, else 1                                          (gbp.py:324, variance 1)
+ *   robust_flag_f = (M > t)
+ * The weight multiplies the factor AS LINEARISED (eta_f, Lambda_f at linpoint_f) wherever it is used -- messages, the energy
+ * sum_f w_f 0.5 |h(mu) - diag(s) z|^2 at the current means (gbp.py:43, 265), and the joint -- where the reference rescales in place by
+ * old / new (gbp.py:331-332) and compute_factor divides by the adaptive variance (gbp.py:287): rounding apart, the same.  A
+ * relinearisation re-makes the nominal factor; the weight stays.
+ *
+ * gbp_lin_set_robust_nonlinear: loss and threshold of the factors [first, first + count) (count each); their weights become 1 and their
+ * flags 0, and every other factor keeps loss, threshold, weight and flag bit for bit -- a live smoother gives a loss to the closures it
+ * has just appended without disturbing the rest.  On a handle without losses set every factor outside the range is at NONE, 1, 0.  The
+ * first call on a handle allocates the robust arrays and the buffer of the flag counts; later calls allocate nothing.  loss == NULL with
+ * first == 0 && count == F clears: all weights 1, the handle back on the plain nonlinear path; loss == NULL otherwise is GBP_EINVAL.
+ * The rules of gbp_lin_set_robust for a loss and a threshold apply (there is no noise_var: it is 1); a range outside [0, F] or a
+ * negative count: GBP_EINVAL.  A handle that is not nonlinear: GBP_ESTATE.  All decided before anything changes; count == 0: GBP_OK,
+ * nothing changes.
+ * gbp_lin_robustify_nonlinear: robustify_all_factors (gbp.py:82-84) alone, at the linpoints.  GBP_ESTATE without nonlinear factors or
+ * without losses set.
+ * gbp_lin_iterate_nonlinear_robust: n sweeps in the order of gbp.py:86-92 -- (1) robustify every factor at its linpoint as it stands
+ * BEFORE this sweep's relinearisation, (2) relinearise (gbp.py:64-80), (3) messages, each factor with its own damping and its weight,
+ * (4) beliefs -- as three kernels per sweep: (1) and (2) are one lane per factor on the same linpoint, z and s, and run fused.
+ * relin_counts as in gbp_lin_iterate_nonlinear; robust_counts[i] (host, n_iters, or NULL): the number of factors flagged in sweep i,
+ * counted the same way, its device buffer growing to the largest n_iters seen.  GBP_ESTATE as gbp_lin_robustify_nonlinear; n_iters < 0:
+ * GBP_EINVAL.  Marks the solver's LDL^T and joint eta stale.
+ *
+ * The older calls on a nonlinear handle with losses set:
+ *   gbp_lin_iterate_nonlinear, gbp_lin_iterate, gbp_lin_relinearise   at the weights as they stand (the reference's robustify=False);
+ *   gbp_lin_energy           the weighted sum above;   gbp_lin_get_weights   w and the flags;
+ *   gbp_lin_joint_matvec / joint_eta / solve_map / solve_marginals   the weighted joint: a solve after a robust sweep is one
+ *                            reweighted Gauss-Newton step;
+ *   gbp_lin_extend_nonlinear / gbp_lin_shrink_nonlinear   every old or surviving factor keeps loss, threshold, weight and flag bit for
+ *                            bit; appended factors start at NONE, weight 1, flag 0; gbp_lin_get_alloc_count still does not grow with
+ *                            repeated calls;
+ *   gbp_lin_set_robust, gbp_lin_robustify, gbp_lin_iterate_robust, gbp_lin_iterate_until, gbp_lin_extend, gbp_lin_shrink   stay
+ *                            refused with GBP_ESTATE; gbp_lin_set_nonlinear on a handle with linear losses set stays GBP_ESTATE.
+ * No floating-point atomics: two identical call sequences on two handles are bit-identical, both counts included. */
+int  gbp_lin_set_robust_nonlinear(gbp_lin_t *h, int32_t first, int32_t count, const int32_t *loss, const double *threshold);   /* Factor(loss=, mahalanobis_threshold=) gbp.py:209-210 */
+int  gbp_lin_robustify_nonlinear(gbp_lin_t *h);                                 /* robustify_all_factors gbp.py:82-84, at the linpoints */
+int  gbp_lin_iterate_nonlinear_robust(gbp_lin_t *h, int32_t n_iters, int32_t *relin_counts /* n_iters or NULL */,
+                                      int32_t *robust_counts /* n_iters or NULL */);   /* n x synchronous_iteration(local_relin=True, robustify=True) gbp.py:86-92 */
 
 #ifdef __cplusplus
 }

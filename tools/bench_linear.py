@@ -42,7 +42,11 @@ ap.add_argument('--nonlinear-live', action='store_true',
                 help='time gbp_lin_extend_nonlinear (+1000 poses, +5000 factors) and gbp_lin_shrink_nonlinear (the 1000 oldest poses, folded) against '
                      're-creating the handle (gbp_lin_create + gbp_lin_set_nonlinear) and against the linear extend / shrink, and the nonlinear sweep '
                      'against --parent-lib; writes profiles/linear_nonlinear_live.json')
-ap.add_argument('--parent-lib', default=None, help="--nonlinear-live: the parent commit's libgbp_hip.so, loaded beside this one for the yardsticks")
+ap.add_argument('--nonlinear-robust', action='store_true',
+                help='time the robust relinearising sweep (gbp_lin_iterate_nonlinear_robust) against gbp_lin_iterate_nonlinear on the two graphs of '
+                     '--nonlinear, fused and with robustify as a launch of its own, and the sweeps without losses against --parent-lib; writes '
+                     'profiles/linear_nonlinear_robust.json')
+ap.add_argument('--parent-lib', default=None, help="--nonlinear-live / --nonlinear-robust: the parent commit's libgbp_hip.so, loaded beside this one for the yardsticks")
 ap.add_argument('--parent-results', default=None,
                 help="--extend / --shrink / --until / --nonlinear: a file of lines 'parent {json}' / 'here {json}', each the JSON line of a plain run of this tool from the parent "
                      "commit's tree or from this one (run alternating, in the same session); summarised per workload under sweeps_per_s_vs_parent")
@@ -704,6 +708,103 @@ def nonlinear_live_profile():
     print(json.dumps(out))
 
 
+def nonlinear_robust_profile():
+    """Host clock around whole calls, each ending in gbp_lin_sync, after a warm-up of every form; --repeats alternating rounds of --steps
+    sweeps, medians reported per sweep, spread = (max - min) / median.  On the two graphs of --nonlinear, beta = +inf (nothing
+    relinearises, so the robustify cost stands alone), every factor with the Huber loss at threshold 2 (every lane takes the loss's
+    path).  (a) one handle WITHOUT losses: gbp_lin_iterate_nonlinear (`plain`).  (b) one handle WITH losses: gbp_lin_iterate_nonlinear
+    at the weights as they stand (`weighted`: the factor stage reads w), gbp_lin_iterate_nonlinear_robust (`robust`: the fused lane),
+    and the alternative the fusion is measured against, robustify as a launch of its own -- gbp_lin_robustify_nonlinear +
+    gbp_lin_iterate_nonlinear(1) per sweep, four launches (`separate`; that is the same lane code run in its robustify-only mode: no
+    separate kernel is kept; its robustify launch does not count the flagged factors).  (b') a third handle whose threshold is never
+    reached: the same lane, loads and stores as `robust`, but no wave adds to the sweep's flag count (`robust_nothing_flagged`) -- on
+    the handle of (b) two waves in three do, all to one address.  Counted beside robust / plain, per factor on top of the relinearising sweep's count: z and s now read
+    every sweep (6 doubles), loss (0.5), threshold (1), w written (1), flag written (0.5), w read by the factor stage (1) = 10.  An
+    excess of the measured ratio over the counted one is UNEXPLAINED here -- no counters were collected.  (c) with --parent-lib: sweeps
+    of gbp_lin_iterate_nonlinear and of gbp_lin_iterate on handles WITHOUT losses, this library against the parent commit's, alternating,
+    once with the parent's handle created first and once with this library's; the margin is the larger of the two spreads."""
+    import ctypes as ct
+    from gbp_amd import _capi
+    here = _capi.load()
+    parent = ct.CDLL(os.path.abspath(a.parent_lib)) if a.parent_lib else None
+    D, runs, n = 3, [], a.steps
+    for N, k in ((200_000, 5), (1_000_000, 1)):
+        va, vb, z, s, pe, pl = se2_graph(N, k, np.random.RandomState(0))
+        F = va.shape[0]
+        e = LinearEngine.se2_pose_graph(va, vb, z, s, pe, pl, float('inf'), 4, 2, eta_damping=0.4)
+        r = LinearEngine.se2_pose_graph(va, vb, z, s, pe, pl, float('inf'), 4, 2, eta_damping=0.4)
+        r.set_robust('huber', 2.0)
+        r0 = LinearEngine.se2_pose_graph(va, vb, z, s, pe, pl, float('inf'), 4, 2, eta_damping=0.4)
+        r0.set_robust('huber', 1e9)                           # the same lane and traffic, nothing flagged: no wave adds to the count
+
+        def timed(fn, h):
+            t = time.perf_counter(); fn(); h.sync()
+            return 1e3 * (time.perf_counter() - t) / n
+
+        def separate():
+            for _ in range(n):
+                r.robustify_all_factors(); r._lib.gbp_lin_iterate_nonlinear(r._h, 1, None)
+        forms = {'plain': lambda: timed(lambda: e._lib.gbp_lin_iterate_nonlinear(e._h, n, None), e),
+                 'weighted': lambda: timed(lambda: r._lib.gbp_lin_iterate_nonlinear(r._h, n, None), r),
+                 'robust': lambda: timed(lambda: r._lib.gbp_lin_iterate_nonlinear_robust(r._h, n, None, None), r),
+                 'robust_nothing_flagged': lambda: timed(lambda: r0._lib.gbp_lin_iterate_nonlinear_robust(r0._h, n, None, None), r0),
+                 'separate': lambda: timed(separate, r)}
+        for fn in forms.values():
+            fn()
+        rec = {key: [] for key in forms}
+        for _ in range(a.repeats):                          # alternating
+            for key, fn in forms.items():
+                rec[key].append(fn())
+        flagged = int(r.weights()[1].sum())
+        assert not r0.weights()[1].any()
+        med = {key: statistics.median(v) for key, v in rec.items()}
+        spread = {key: (max(v) - min(v)) / med[key] for key, v in rec.items()}
+        per_f = sweep_doubles(D, 1.0 / k, False) + 14           # the relinearising sweep at beta = +inf (--nonlinear)
+        vs_parent = None
+        if parent:
+            vs_parent = {}
+            for order in ('parent_created_first', 'here_created_first'):
+                first, second = (parent, here) if order == 'parent_created_first' else (here, parent)
+                h1 = RawSE2(first, va, vb, z, s, pe, pl, float('inf'), 2)
+                h2 = RawSE2(second, va, vb, z, s, pe, pl, float('inf'), 2)
+                hp, hh = (h1, h2) if order == 'parent_created_first' else (h2, h1)
+                for call in ('gbp_lin_iterate_nonlinear', 'gbp_lin_iterate'):
+                    def sweeps(h):
+                        t = time.perf_counter()
+                        rc = h.lib.gbp_lin_iterate_nonlinear(h.h, ct.c_int32(n), None) if call == 'gbp_lin_iterate_nonlinear' else h.lib.gbp_lin_iterate(h.h, ct.c_int32(n))
+                        assert rc == 0 and h.lib.gbp_lin_sync(h.h) == 0
+                        return n / (time.perf_counter() - t)
+                    sweeps(hp); sweeps(hh)
+                    tp, th = [], []
+                    for _ in range(a.repeats):
+                        tp.append(sweeps(hp)); th.append(sweeps(hh))
+                    mp, mh = statistics.median(tp), statistics.median(th)
+                    sp, sh = (max(tp) - min(tp)) / mp, (max(th) - min(th)) / mh
+                    vs_parent[call + '_' + order] = {"sweeps_per_s_parent": mp, "sweeps_per_s_here": mh, "ratio_here_over_parent": mh / mp, "spread_parent": sp,
+                                                     "spread_here": sh, "margin": max(sp, sh), "beyond_margin": abs(mh / mp - 1.0) > max(sp, sh),
+                                                     "all_parent": tp, "all_here": th}
+                hp.close(); hh.close()
+        runs.append({"vars": N, "dofs": D, "k": k, "factors": F, "ms_per_sweep": med, "spread": spread, "ms_all": rec, "flagged_at_the_end": flagged,
+                     "ratio_robust_over_plain": med['robust'] / med['plain'], "ratio_robust_over_plain_counted": (per_f + 10) / per_f,
+                     "ratio_robust_over_weighted": med['robust'] / med['weighted'], "ratio_robust_over_weighted_counted": (per_f + 10) / (per_f + 1),
+                     "ratio_separate_over_robust": med['separate'] / med['robust'],
+                     "ratio_robust_nothing_flagged_over_plain": med['robust_nothing_flagged'] / med['plain'], "doubles_per_factor_relinearising_sweep": per_f,
+                     "counters_collected": False, "sweeps_per_s_vs_parent_without_losses": vs_parent})
+        e.close(); r.close(); r0.close()
+    out = {"what": "tools/bench_linear.py --nonlinear-robust on one MI355X: ms per sweep of gbp_lin_iterate_nonlinear_robust against gbp_lin_iterate_nonlinear, "
+                   "with robustify fused into the relinearise lane and as a launch of its own, and the sweeps of handles without losses against the parent "
+                   "commit's library, on the 200k x 3 ring (k = 5) and the 1M-variable chain (k = 1) re-posed as SE(2)",
+           "method": " ".join(nonlinear_robust_profile.__doc__.split()), "repeats": a.repeats, "sweep_steps": a.steps, "runs": runs}
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'profiles', 'linear_nonlinear_robust.json')
+    with open(path, 'w') as fh:
+        json.dump(out, fh, indent=1)
+        fh.write('\n')
+    print(json.dumps(out))
+
+
+if a.nonlinear_robust:
+    nonlinear_robust_profile()
+    sys.exit(0)
 if a.nonlinear_live:
     nonlinear_live_profile()
     sys.exit(0)
