@@ -89,13 +89,13 @@ int extend_into(gbp_ba *o, gbp_ba *n, const gbp_ba_ext_t *e, std::vector<void *>
     // 1. the union's inputs, on the device
     const double *bcm = nullptr, *blm = nullptr, *bmeas = nullptr;
     const int *bcam = nullptr, *blmk = nullptr;
-    CHK(graft_stage(n, e->cam_means, (size_t)dC * 6, dev_in, scratch, &bcm)); CHK(graft_stage(n, e->lmk_means, (size_t)dL * 3, dev_in, scratch, &blm));
-    CHK(graft_stage(n, e->meas, (size_t)dF * 2, dev_in, scratch, &bmeas));
-    CHK(graft_stage(n, e->cam_idx, (size_t)dF, dev_in, scratch, &bcam)); CHK(graft_stage(n, e->lmk_idx, (size_t)dF, dev_in, scratch, &blmk));
+    CHK(stage_input(n, e->cam_means, (size_t)dC * 6, dev_in, scratch, &bcm)); CHK(stage_input(n, e->lmk_means, (size_t)dL * 3, dev_in, scratch, &blm));
+    CHK(stage_input(n, e->meas, (size_t)dF * 2, dev_in, scratch, &bmeas));
+    CHK(stage_input(n, e->cam_idx, (size_t)dF, dev_in, scratch, &bcam)); CHK(stage_input(n, e->lmk_idx, (size_t)dF, dev_in, scratch, &blmk));
     double *u_meas = nullptr, *u_cm = nullptr, *u_lm = nullptr;
     int *u_cam = nullptr, *u_lmk = nullptr;
-    CHK(graft_scratch(n, scratch, &u_meas, (size_t)F * 2)); CHK(graft_scratch(n, scratch, &u_cam, (size_t)F)); CHK(graft_scratch(n, scratch, &u_lmk, (size_t)F));
-    CHK(graft_scratch(n, scratch, &u_cm, (size_t)C * 6)); CHK(graft_scratch(n, scratch, &u_lm, (size_t)L * 3));
+    CHK(scratch_alloc(n, scratch, &u_meas, (size_t)F * 2)); CHK(scratch_alloc(n, scratch, &u_cam, (size_t)F)); CHK(scratch_alloc(n, scratch, &u_lmk, (size_t)F));
+    CHK(scratch_alloc(n, scratch, &u_cm, (size_t)C * 6)); CHK(scratch_alloc(n, scratch, &u_lm, (size_t)L * 3));
     if (F) hipLaunchKernelGGL(k_union_factors, dim3(grid_for((size_t)F)), dim3(BLOCK), 0, n->stream, op, o->d_ref_cam, o->d_ref_lmk, o->d_lmk_i2u, bmeas, bcam, blmk, dF,
                               u_meas, u_cam, u_lmk);
     const size_t nv = (size_t)C * 6 + (size_t)L * 3;
@@ -115,7 +115,7 @@ int extend_into(gbp_ba *o, gbp_ba *n, const gbp_ba_ext_t *e, std::vector<void *>
 
     // 4. the state transplant
     int *d_o2n = nullptr;
-    CHK(graft_scratch(n, scratch, &d_o2n, (size_t)op.F));
+    CHK(scratch_alloc(n, scratch, &d_o2n, (size_t)op.F));
     const size_t S = n_slots(n);
     if (p.T && op.F) hipLaunchKernelGGL(k_transplant_slots, dim3(grid_for(S)), dim3(BLOCK), 0, n->stream, p, op, ref_file, d_o2n);
     if (op.C + op.L) hipLaunchKernelGGL(k_transplant_vars, dim3(grid_for((size_t)op.C + op.L)), dim3(BLOCK), 0, n->stream, p, op, n->d_lmk_u2i, o->d_lmk_u2i);

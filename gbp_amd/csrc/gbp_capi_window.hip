@@ -298,17 +298,17 @@ int window_into(gbp_ba *o, gbp_ba *n, const Step &st, const Words &wd, std::vect
 
     // 1. the lists and the batch on the device; which variables the batch's factors keep alive (and whether their ids are sound)
     WindowLists w{nullptr, nullptr, nullptr};                  // (an empty list stays NULL: nothing is allocated or uploaded for it)
-    if (!wd.gone.empty()) CHK(graft_stage(n, wd.gone.data(), wd.gone.size(), false, scratch, &w.gone));
-    if (!wd.cam.empty()) CHK(graft_stage(n, wd.cam.data(), wd.cam.size(), false, scratch, &w.cam));
-    if (!wd.lmk.empty()) CHK(graft_stage(n, wd.lmk.data(), wd.lmk.size(), false, scratch, &w.lmk));
+    if (!wd.gone.empty()) CHK(stage_input(n, wd.gone.data(), wd.gone.size(), false, scratch, &w.gone));
+    if (!wd.cam.empty()) CHK(stage_input(n, wd.cam.data(), wd.cam.size(), false, scratch, &w.cam));
+    if (!wd.lmk.empty()) CHK(stage_input(n, wd.lmk.data(), wd.lmk.size(), false, scratch, &w.lmk));
     int *d_seen = nullptr, *d_bad = nullptr, *d_keep = nullptr, *d_pos = nullptr;
-    CHK(graft_scratch(n, scratch, &d_keep, N + 1)); CHK(graft_scratch(n, scratch, &d_pos, N + 1));
+    CHK(scratch_alloc(n, scratch, &d_keep, N + 1)); CHK(scratch_alloc(n, scratch, &d_pos, N + 1));
     Batch b{dC, dL, dF, nullptr, nullptr, nullptr, nullptr, nullptr};
-    CHK(graft_stage(n, e->cam_means, (size_t)dC * 6, dev_in, scratch, &b.cam_means)); CHK(graft_stage(n, e->lmk_means, (size_t)dL * 3, dev_in, scratch, &b.lmk_means));
-    CHK(graft_stage(n, e->meas, (size_t)dF * 2, dev_in, scratch, &b.meas));
-    CHK(graft_stage(n, e->cam_idx, (size_t)dF, dev_in, scratch, &b.cam)); CHK(graft_stage(n, e->lmk_idx, (size_t)dF, dev_in, scratch, &b.lmk));
+    CHK(stage_input(n, e->cam_means, (size_t)dC * 6, dev_in, scratch, &b.cam_means)); CHK(stage_input(n, e->lmk_means, (size_t)dL * 3, dev_in, scratch, &b.lmk_means));
+    CHK(stage_input(n, e->meas, (size_t)dF * 2, dev_in, scratch, &b.meas));
+    CHK(stage_input(n, e->cam_idx, (size_t)dF, dev_in, scratch, &b.cam)); CHK(stage_input(n, e->lmk_idx, (size_t)dF, dev_in, scratch, &b.lmk));
     if (dF) {
-        CHK(graft_scratch(n, scratch, &d_seen, Cu + Lu)); CHK(graft_scratch(n, scratch, &d_bad, 1));
+        CHK(scratch_alloc(n, scratch, &d_seen, Cu + Lu)); CHK(scratch_alloc(n, scratch, &d_bad, 1));
         HIPCHK(hipMemsetAsync(d_seen, 0, sizeof(int) * (Cu + Lu), n->stream));
         HIPCHK(hipMemsetAsync(d_bad, 0x7f, sizeof(int), n->stream));      // 0x7f7f7f7f: above every entry
         hipLaunchKernelGGL(k_window_mark, dim3(grid_for((size_t)dF)), dim3(BLOCK), 0, n->stream, b.cam, b.lmk, dF, (int)Cu, (int)Lu, w, d_seen, d_bad);
@@ -346,9 +346,9 @@ int window_into(gbp_ba *o, gbp_ba *n, const Step &st, const Words &wd, std::vect
 
     // 3. the result's inputs, on the device
     Survivors s{};
-    CHK(graft_scratch(n, scratch, &s.o2n, N)); CHK(graft_scratch(n, scratch, &s.f_n2o, (size_t)F));
-    CHK(graft_scratch(n, scratch, &s.meas, (size_t)F * 2)); CHK(graft_scratch(n, scratch, &s.cam, (size_t)F)); CHK(graft_scratch(n, scratch, &s.lmk, (size_t)F));
-    CHK(graft_scratch(n, scratch, &s.cam_means, (size_t)C * 6)); CHK(graft_scratch(n, scratch, &s.lmk_means, (size_t)L * 3));
+    CHK(scratch_alloc(n, scratch, &s.o2n, N)); CHK(scratch_alloc(n, scratch, &s.f_n2o, (size_t)F));
+    CHK(scratch_alloc(n, scratch, &s.meas, (size_t)F * 2)); CHK(scratch_alloc(n, scratch, &s.cam, (size_t)F)); CHK(scratch_alloc(n, scratch, &s.lmk, (size_t)F));
+    CHK(scratch_alloc(n, scratch, &s.cam_means, (size_t)C * 6)); CHK(scratch_alloc(n, scratch, &s.lmk_means, (size_t)L * 3));
     hipLaunchKernelGGL(k_window_compact, dim3(grid_for(N)), dim3(BLOCK), 0, n->stream, op, b, o->d_ref_cam, o->d_ref_lmk, o->d_lmk_u2i, o->d_lmk_i2u, d_keep, d_pos, s);
     HIPCHK(hipGetLastError());
 

@@ -701,6 +701,7 @@ inline SweepKernel sweep_variant(int loss, bool pinned, bool single, bool window
 
 // wg_win / wg_cams (n_win = workgroups, or 0): the workgroups' camera windows -- build_graph's decision (k_wg_cam_sets: per workgroup
 // {lowest camera, cameras in its set, offset into wg_cams, width of its interval}); without them every workgroup's table covers all cameras.
+// Every fused_upload below is listed, with its size, in fused_plan_uploads (gbp_build_plan.hpp): the owner's arena is sized by that list.
 inline int fused_plan(FusedPlan &pl, const Params &p, hipStream_t stream, int n_cus, const Overrides &o, const int4 *wg_win,
                       const int *wg_cams, int n_win)
 {

@@ -3,7 +3,7 @@
 // handle by the create path (gbp::build_graph), move the state of the factors and variables that live on into the new layout, and swap
 // the new graph in only when everything has succeeded.  Here: the per-slot and per-variable moves (device), the arrays a rebuild
 // assembles for the create path (Survivors), and on the host what every call asks of the handle and of a batch before it starts
-// (live_and_whole, sound_batch), the staging of inputs and scratch, the settings the new graph inherits, the counters it carries, the
+// (live_and_whole, sound_batch), the settings the new graph inherits, the counters it carries, the
 // swap itself and the maps of a call that changes nothing.
 #pragma once
 #include "gbp_handle.hpp"
@@ -88,28 +88,6 @@ inline int sound_batch(const Params &op, const gbp_ba_ext_t *e)
         (int64_t)op.C + dC + (int64_t)op.L + dL + (int64_t)op.F + dF >= INT32_MAX)
         return fail(GBP_EINVAL, "sizes exceed int32");
     if (op.C + dC >= (1 << (32 - META_LMK_BITS))) return fail(GBP_EINVAL, "more than %d cameras are not supported", (1 << (32 - META_LMK_BITS)) - 1);
-    return GBP_OK;
-}
-
-template <typename T>
-inline int graft_stage(gbp_ba *h, const T *src, size_t n, bool on_device, std::vector<void *> &scratch, const T **out)
-{
-    if (on_device || !n) { *out = src; return GBP_OK; }
-    void *q = nullptr;
-    HIPCHK(hipMallocAsync(&q, n * sizeof(T), h->stream));
-    scratch.push_back(q);
-    HIPCHK(hipMemcpyAsync(q, src, n * sizeof(T), hipMemcpyHostToDevice, h->stream));
-    *out = static_cast<const T *>(q);
-    return GBP_OK;
-}
-
-template <typename T>
-inline int graft_scratch(gbp_ba *h, std::vector<void *> &scratch, T **out, size_t n)
-{
-    void *q = nullptr;
-    HIPCHK(hipMallocAsync(&q, std::max<size_t>(n, 1) * sizeof(T), h->stream));
-    scratch.push_back(q);
-    *out = static_cast<T *>(q);
     return GBP_OK;
 }
 

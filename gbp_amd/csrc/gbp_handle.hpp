@@ -1,6 +1,8 @@
 // gbp_handle.hpp -- what the translation units of libgbp_hip.so share about a handle (private: include/gbp_ba.h is the boundary).
 //
-//   gbp_capi.hip        life cycle: errors, create / destroy (graph build), streams, priors, BAL reader, plan info, layout checks
+//   gbp_capi.hip        life cycle: errors, create / destroy, streams, priors, BAL reader, plan info, layout checks
+//   gbp_capi_build.hip  the graph build on the device (gbp::build_graph, a sequence of stages; its host arithmetic: gbp_build_plan.hpp):
+//                       behind create and every call that rebuilds a live handle
 //   gbp_capi_sweep.hip  every launch of a sweep (run_sweep: one SweepCall in, the cameras left where its sink says): fused + general +
 //                       stage-wise, the dense remainder, diagnostics, kernel timing
 //   gbp_capi_shard.hip  the landmark-sharded loop: RCCL, peer-store mailboxes, the exchange between reduce and finish
@@ -19,6 +21,7 @@
 #include "gbp_kernels.hpp"
 #include "gbp_fused_plan.hpp"
 #include "gbp_policy.hpp"
+#include "gbp_build_plan.hpp"
 
 #include <rccl/rccl.h>      // types only: the library is dlopen()ed when a communicator is asked for (no link-time dependency)
 
@@ -167,7 +170,6 @@ struct gbp_ba {
     hipStream_t side_stream = nullptr;           // beliefs of over-sized landmarks run beside the exchange
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 };
-constexpr int RELIN_RING = 1024;
 constexpr int CLK_RING = 4096;
 
 // ---- small helpers every unit uses (inline: one definition per unit, no state of their own) ----------------------------------
@@ -212,6 +214,30 @@ inline void *arena_take(void *ctx, size_t bytes)          // FusedPlan's allocat
     if (!h->arena || off + bytes > h->arena_bytes) return nullptr;
     h->arena_used = off + bytes;
     return static_cast<char *>(h->arena) + off;
+}
+
+// host -> device copy of a caller array that is released when the call ends (or the caller's own device pointer)
+template <typename T>
+inline int stage_input(gbp_ba *h, const T *src, size_t n, bool on_device, std::vector<void *> &scratch, const T **out)
+{
+    if (on_device || !n) { *out = src; return GBP_OK; }
+    void *q = nullptr;
+    HIPCHK(hipMallocAsync(&q, n * sizeof(T), h->stream));
+    scratch.push_back(q);
+    HIPCHK(hipMemcpyAsync(q, src, n * sizeof(T), hipMemcpyHostToDevice, h->stream));
+    *out = static_cast<const T *>(q);
+    return GBP_OK;
+}
+
+// buffers only a build or rebuild needs come from the stream-ordered pool (no device synchronisation per allocation or release)
+template <typename T>
+inline int scratch_alloc(gbp_ba *h, std::vector<void *> &scratch, T **out, size_t n)
+{
+    void *q = nullptr;
+    HIPCHK(hipMallocAsync(&q, std::max<size_t>(n, 1) * sizeof(T), h->stream));
+    scratch.push_back(q);
+    *out = static_cast<T *>(q);
+    return GBP_OK;
 }
 
 inline int ensure_tmp(gbp_ba *h, size_t bytes)
@@ -274,8 +300,10 @@ namespace gbp {
 // gbp_capi.hip
 int peer_check(gbp_ba *h, bool clear);               // a finish wave of the peer-store exchange gave up waiting: GBP_ESTATE until gbp_ba_sync has reported it
 int graph_hash(gbp_ba *h, uint64_t *out);            // digest of the factor -> (slot, camera, landmark) maps (state blobs)
+// gbp_capi_build.hip
 int build_graph(gbp_ba *h, const gbp_ba_desc_t *d, std::vector<void *> &scratch, int n_cus, const int **ref_file_out = nullptr);
                                                      // the graph of a descriptor onto a handle (gbp_ba_create, gbp_ba_extend)
+// gbp_capi.hip
 int variable_lambda_max(gbp_ba *h);                  // d_varmax = max over each variable's factors of max(Lambda_f) (gbp_ba.py:27-31)
 int prior_scalars_range(gbp_ba *h, int c0, int l0, double w2_cam, double w2_lmk, bool lmk_lambda_by_user);   // priors from d_varmax for cameras >= c0, landmarks >= l0
 // gbp_capi_sweep.hip

@@ -6,7 +6,7 @@
 // reference factor id inside a landmark) and a tile owns up to 24 whole landmarks: all factors of those
 // landmarks, nf <= 64 of the 64 slots used.  A landmark may also SPAN tiles -- one with more than 64 factors always does ("chunk"
 // tiles: nl = 1, a piece of that landmark and nothing else), and in the dense packing (graphs whose whole landmarks would leave the
-// tiles under-filled: gbp_capi.hip build_graph) tile t simply holds factors [64 t, 64 t + 64) of the landmark-major list.  A tile that
+// tiles under-filled: gbp_capi_build.hip build_graph) tile t simply holds factors [64 t, 64 t + 64) of the landmark-major list.  A tile that
 // holds only a PART of a landmark adds its part of the messages up and writes the sum to Params::parts (row 2 t: the landmark began
 // in an earlier tile, row 2 t + 1: it goes on in the next); k_lmk_finish_parts forms those beliefs after the sweep.
 // Slot id = tile*64 + lane.
@@ -37,7 +37,7 @@
 //            each camera's factors (reference order).
 //
 // (This header holds the layout and every device-side helper; the kernels themselves live with the translation unit that launches them:
-// gbp_sweep_kernels.hpp + gbp_fused.hpp -> gbp_capi_sweep.hip, gbp_view_kernels.hpp -> gbp_capi_views.hip, gbp_build.hpp -> gbp_capi.hip.)
+// gbp_sweep_kernels.hpp + gbp_fused.hpp -> gbp_capi_sweep.hip, gbp_view_kernels.hpp -> gbp_capi_views.hip, gbp_build.hpp -> gbp_capi_build.hip, gbp_prior_kernels.hpp -> gbp_capi.hip.)
 // General sweep (any shape) = k_factor_tile (one wave per tile: messages, the tile's landmark beliefs, camera messages
 // staged in camera-major order) -> k_lmk_belief_list (landmarks larger than a tile) -> k_cam_partial_staged (one
 // workgroup per camera, contiguous run) -> k_cam_finish.  k_lmk_belief / k_cam_partial form beliefs from the STORED
@@ -324,6 +324,7 @@ GBP_HD bool factor_core(const Params &p, double (&x0)[9], const double (&z)[2], 
 // word for everybody serialised 16 k same-address atomics in L2 and DOUBLED the sweep time whenever a few per cent of the
 // factors relinearised (measured: 0.116 -> 0.226 ms).
 constexpr int RELIN_LANES = 64;
+constexpr int RELIN_RING = 1024;   // per-sweep counters the handle keeps (gbp_ba::d_relin_ring)
 GBP_DEV int relin_in_wave(bool relin) { return __popcll(__ballot(relin)); }     // call with the whole tile's lanes active or not: exec-masked
 GBP_DEV void relin_add(const Params &p, int n)                                   // one lane of the wave
 {

@@ -6,7 +6,11 @@ after it and save_state() after three more sweeps.  The graph, the batch and the
 cull, retire, retire_landmarks (fold / drop), the full window_step, extend, and extend by tests/extend_cases.py's batches (extend_bare_new:
 new variables no batch factor names, priors from scalars; extend_old_only: late factors of old cameras and no new variable); each on a
 default handle (loss='huber', 6 sweeps), on a handle created with landmark reordering, and on one whose dense remainder is on
-(num_undamped_iters=0, 9 sweeps); and retire([0]) and extend on bare_camera_problem(), where a camera has no factor."""
+(num_undamped_iters=0, 9 sweeps); and retire([0]) and extend on bare_camera_problem(), where a camera has no factor.
+
+Then the create-only scenarios of tests/build_cases.py, one per path of the graph build (gbp_capi_build.hip) the live calls' small graph
+does not reach: create, priors, update_all_beliefs, three sweeps; save_state(), plan_info() and check_layout() are hashed, and `reached`
+says whether the scenario still takes the path it is named for (read from plan_info()).  --create-only runs these alone."""
 import hashlib
 import json
 import os
@@ -26,6 +30,7 @@ def sha(a):
 def main():
     from gbp_amd import _capi
     from gbp_amd.engine import BAEngine
+    from build_cases import build_scenarios, create
     from extend_cases import bare_new_batch, old_only_batch
     from window_host import bare_camera_problem, base_case
     c = base_case()
@@ -65,12 +70,24 @@ def main():
         e.close()
         return json.dumps(rec)
 
+    def created(name, s):
+        e = create(s)
+        e.iterate(3)
+        pi = e.plan_info()
+        rec = dict(scenario='create/' + name, sizes=[e.C, e.L, e.F], reached=bool(s.reached(pi)), plan_info=pi, bad_slots=e.check_layout(),
+                   state_after_3_sweeps=sha(e.save_state()))
+        e.close()
+        return json.dumps(rec)
+
     lines = [json.dumps(dict(library=os.path.basename(os.path.dirname(os.path.abspath(_capi.LIB_PATH))) + '/' + os.path.basename(_capi.LIB_PATH)))]
-    for hname, (kw, sweeps) in handles.items():
-        for cname, call in calls.items():
-            lines.append(record(f'{hname}/{cname}', live(c.base, kw, sweeps), call))
-    lines.append(record('bare_camera/retire', live(bare_camera_problem(), dict(loss='huber'), 6, bare=8), lambda e: e.retire([0])))
-    lines.append(record('bare_camera/extend', live(bare_camera_problem(), dict(loss='huber'), 6, bare=8), calls['extend']))
+    if '--create-only' not in sys.argv:
+        for hname, (kw, sweeps) in handles.items():
+            for cname, call in calls.items():
+                lines.append(record(f'{hname}/{cname}', live(c.base, kw, sweeps), call))
+        lines.append(record('bare_camera/retire', live(bare_camera_problem(), dict(loss='huber'), 6, bare=8), lambda e: e.retire([0])))
+        lines.append(record('bare_camera/extend', live(bare_camera_problem(), dict(loss='huber'), 6, bare=8), calls['extend']))
+    for name, s in build_scenarios().items():
+        lines.append(created(name, s))
     print('\n'.join(lines))
     if '--out' in sys.argv:
         with open(sys.argv[sys.argv.index('--out') + 1], 'w') as f:
