@@ -181,6 +181,7 @@ SIGNATURES = {
     'gbp_lin_set_robust_nonlinear': (ct.c_int, [ct.c_void_p, ct.c_int32, ct.c_int32, _ip, _dp]),
     'gbp_lin_robustify_nonlinear': (ct.c_int, [ct.c_void_p]),
     'gbp_lin_iterate_nonlinear_robust': (ct.c_int, [ct.c_void_p, ct.c_int32, _ip, _ip]),
+    'gbp_lin_iterate_until_nonlinear': (ct.c_int, [ct.c_void_p, ct.c_void_p, _dp, _ip, _ip, ct.c_void_p]),
     'gbp_ba_get_lmk_order': (ct.c_int, [ct.c_void_p, _ip]),
     'gbp_ba_fused_max_cams': (ct.c_int, []),
     'gbp_ba_plan_info': (ct.c_int, [ct.c_void_p, _ip, ct.c_int32]),
@@ -251,6 +252,7 @@ class LinExtNonlinear(ct.Structure):
 
 LIN_MODEL_SE2_BETWEEN = 1                           # GBP_LIN_MODEL_* (include/gbp_lin.h)
 LIN_TRACE_ENERGY, LIN_TRACE_MAP = 1, 2              # GBP_LIN_TRACE_* (include/gbp_lin.h)
+LIN_UNTIL_SETTLED = 4                               # GBP_LIN_UNTIL_SETTLED: in `want` of gbp_lin_iterate_until_nonlinear only
 LIN_STOP_NONE, LIN_STOP_STEP, LIN_STOP_MAP = 0, 1, 2   # GBP_LIN_STOP_*
 LIN_MARG_COLS = 8
 LIN_LOSS = {None: 0, 'huber': 1, 'constant': 2}     # GBP_LIN_LOSS_* (include/gbp_lin.h)

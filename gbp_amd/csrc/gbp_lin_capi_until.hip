@@ -19,10 +19,13 @@ constexpr int KNOWN_WANT = GBP_LIN_TRACE_ENERGY | GBP_LIN_TRACE_MAP;
 
 bool tol_ok(double t) { return t >= 0.0 && std::isfinite(t); }
 
+}  // namespace
+
+namespace gbp {
 // a trace buffer of at least max_iters rows, the stop word, and the partials of this generation: whatever is missing.  The trace buffer
 // (24 bytes per sweep of max_iters) is the one piece a caller can make too large, so it is asked for first: GBP_ENOMEM for it leaves
-// the handle holding exactly what it held.
-int until_workspace(gbp_lin *h, int max_iters)
+// the handle holding exactly what it held.  gbp_lin_iterate_until_nonlinear (gbp_lin_capi_until_nonlin.hip) uses the same workspace.
+int lin_until_workspace(gbp_lin *h, int max_iters)
 {
     LinUntil &u = h->until;
     if (max_iters > u.cap) {
@@ -42,6 +45,9 @@ int until_workspace(gbp_lin *h, int max_iters)
     }
     return GBP_OK;
 }
+}  // namespace gbp
+
+namespace {
 
 // sweep `it` + 1 of the call: every kernel gated on the stop word
 int until_sweep(gbp_lin *h, const gbp_lin_until_opts_t &o, const UntilRule &rule, int it)
@@ -88,7 +94,7 @@ int gbp_lin_iterate_until(gbp_lin_t *h, const gbp_lin_until_opts_t *opts, double
         if (info) *info = out;
         return GBP_OK;
     }
-    LCHK(until_workspace(h, o.max_iters));
+    LCHK(lin_until_workspace(h, o.max_iters));
     const LinUntil &u = h->until;
     const UntilRule rule{o.want, o.tol_step, o.tol_map};
     LHIPCHK(hipMemsetAsync(u.stop, 0, 2 * sizeof(int), h->stream));

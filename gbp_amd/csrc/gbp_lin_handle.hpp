@@ -10,6 +10,9 @@
 //   gbp_lin_capi_until.hip   sweeps until a tolerance is met, decided on the device, with a per-sweep trace: the gated and traced forms of
 //                            the same stage kernels (parameter blocks LinGated / LinTraced below), and what is the call's alone
 //                            (gbp_lin_until.hpp)
+//   gbp_lin_capi_until_nonlin.hip  the same on a handle with nonlinear factors: the relinearise, factor and energy stages of such a sweep in
+//                            their gated forms (LinGated, LinRelinGated below), the traced belief stage, and the finishing kernel reading
+//                            the sweep's relinearisation count (UntilSettled, gbp_lin_until.hpp)
 //   gbp_lin_capi_nonlin.hip  nonlinear pairwise factors relinearised on the device (kernels in gbp_lin_nonlin.hpp): the relinearise stage,
 //                            the factor stage with per-factor damping (parameter block LinRelin below), the model-aware energy; growing and
 //                            shrinking such a handle are gbp_lin_extend_nonlinear / gbp_lin_shrink_nonlinear in the extend / shrink units
@@ -125,11 +128,17 @@ struct LinTraced : LinParams {
 struct LinRelin : LinParams {
     const double *fdamp;         // [F] Factor.eta_damping gbp.py:248
 };
+// LinRelinGated: that factor stage in a sweep queued by gbp_lin_iterate_until_nonlinear: the factor's own damping, and the stop word.
+struct LinRelinGated : LinRelin {
+    const int *stop;
+};
 GBP_DEV double lin_damping(const LinParams &p, int) { return p.damping; }
 GBP_DEV double lin_damping(const LinRelin &p, int f) { return p.fdamp[f]; }
+GBP_DEV double lin_damping(const LinRelinGated &p, int f) { return p.fdamp[f]; }
 GBP_DEV bool lin_stopped(const LinParams &) { return false; }
 GBP_DEV bool lin_stopped(const LinGated &p) { return p.stop[0] != 0; }
 GBP_DEV bool lin_stopped(const LinTraced &p) { return p.u.stop[0] != 0; }
+GBP_DEV bool lin_stopped(const LinRelinGated &p) { return p.stop[0] != 0; }
 
 }  // namespace gbp
 
@@ -178,6 +187,7 @@ int lin_nonlin_energy(gbp_lin *h, double *out);     // gbp_lin_capi_nonlin.hip: 
 int lin_nonlin_linearise(gbp_lin *h, int f0, int f1);   // gbp_lin_capi_nonlin.hip: compute_factor on the factors [f0, f1) at their belief means, queued
 void lin_nonlin_factor_stage(gbp_lin *h);           // gbp_lin_capi_nonlin.hip: the factor stage with per-factor damping, at the weights as they stand (if any), queued
 int lin_nonlin_grow_counts(gbp_lin *h, int *&buf, int &cap, int n);   // gbp_lin_capi_nonlin.hip: a per-sweep counts buffer of at least n slots
+int lin_until_workspace(gbp_lin *h, int max_iters); // gbp_lin_capi_until.hip: LinUntil's trace buffer of at least max_iters rows, the stop word, this generation's partials
 }
 
 // the entry points that a nonlinear handle refuses (include/gbp_lin.h): decided before anything changes

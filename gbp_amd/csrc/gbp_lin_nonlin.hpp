@@ -15,6 +15,8 @@
 //   k_lin_relin_range<MODEL>  that over a range of factors (the ones gbp_lin_extend_nonlinear appended), uncounted
 //   k_lin_energy_nl<MODEL> sum_f w_f 0.5 |h(mu) - diag(s) z|^2 at the belief means (w_f = 1 without losses), in the block / partials
 //                          shape of k_lin_energy
+// k_lin_relin and k_lin_energy_nl take the parameter block as a template argument like the stages of gbp_lin_sweep.hpp: LinParams is
+// the plain form, LinGated the one gbp_lin_iterate_until_nonlinear queues (gbp_lin_capi_until_nonlin.hip).
 // Robust losses on such factors (include/gbp_lin.h, gbp_lin_set_robust_nonlinear):
 //   nonlin_mahalanobis2<MODEL>   |diag(s) z - h(x)|^2 at a point;
 //   nonlin_robustify_one<MODEL>  w_f and the flag of one factor from M at its LINPOINT (gbp.py:309), through lin_robust_weight;
@@ -190,9 +192,12 @@ GBP_DEV bool lin_relin_one(const LinParams &p, const LinNonlin &n, const LinRobu
 // integer atomic add per wave that relinearised anything.
 // ROBUST: the fused robustify + relinearise lane; `r` is read and `rcount` counted (the same way: one ballot, one popcount, one integer
 // atomic add per wave that flagged anything) under it only.
-template <int MODEL, bool ROBUST = false>
-__global__ __launch_bounds__(256) void k_lin_relin(LinParams p, LinNonlin n, int mode, int *count, LinRobust r, int *rcount)
+// PT = LinGated (a sweep queued by gbp_lin_iterate_until_nonlinear): the whole kernel -- the lane and both counts -- returns at its head
+// once the call's stop word is set; for PT = LinParams lin_stopped() is the constant false and the gate compiles away.
+template <int MODEL, bool ROBUST = false, typename PT = LinParams>
+__global__ __launch_bounds__(256) void k_lin_relin(PT p, LinNonlin n, int mode, int *count, LinRobust r, int *rcount)
 {
+    if (lin_stopped(p)) return;                             // PT = LinParams: never
     const int f = blockIdx.x * 256 + threadIdx.x;
     bool flagged;
     const bool relin = lin_relin_one<MODEL, ROBUST>(p, n, r, mode, f, f < p.F, flagged);
@@ -220,10 +225,12 @@ __global__ __launch_bounds__(256) void k_lin_relin_range(LinParams p, LinNonlin 
 }
 
 // sum_f 0.5 |h(mu) - diag(s) z|^2 at the current belief means (gbp.py:36-44, 251-265): one partial per block, the lanes of a wave and
-// the four waves of a block added in a fixed order, exactly the shape of k_lin_energy (gbp_lin_sweep.hpp)
-template <int MODEL>
-__global__ __launch_bounds__(256) void k_lin_energy_nl(LinParams p, LinNonlin n, double *out)
+// the four waves of a block added in a fixed order, exactly the shape of k_lin_energy (gbp_lin_sweep.hpp).  PT = LinGated: the energy
+// pass of a sweep of gbp_lin_iterate_until_nonlinear, gated like the stage above, into the call's own partials.
+template <int MODEL, typename PT = LinParams>
+__global__ __launch_bounds__(256) void k_lin_energy_nl(PT p, LinNonlin n, double *out)
 {
+    if (lin_stopped(p)) return;                             // PT = LinParams: never
     constexpr int D = NL_D, P = LinDims<D>::P, REC = LinDims<D>::REC;
     __shared__ double red[256 / 64];
     const int f = blockIdx.x * 256 + threadIdx.x;

@@ -7,6 +7,7 @@
 // which return at their head once gbp_lin_iterate_until's stop word is set.  For PT = LinParams lin_stopped() is the constant false and
 // the gate -- and with `if constexpr` the trace -- compiles away.  gbp_lin_capi_nonlin.hip instantiates the factor stage once more with
 // PT = LinRelin, where lin_damping() reads the factor's own damping instead of the graph's.
+// gbp_lin_capi_until_nonlin.hip instantiates it with PT = LinRelinGated (that damping and the gate) for gbp_lin_iterate_until_nonlinear.
 #pragma once
 #include "gbp_lin_robust.hpp"
 #include "gbp_lin_until.hpp"

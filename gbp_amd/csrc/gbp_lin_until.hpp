@@ -9,7 +9,9 @@
 //   until_var, until_max     what the traced belief stage adds per variable: max_k |mu_new - mu_old| and, when asked, sum_k (mu_new - x)^2
 //                            against the iterate of the last gbp_lin_solve_map;
 //   k_until_finish           one block: max of the step partials, fixed-order sums of the others (strided per thread, then a fixed
-//                            tree), row i of the device trace, and the stop word when an enabled tolerance is met.
+//                            tree), row i of the device trace, and the stop word when an enabled tolerance is met;
+//   until_row_settled        the decision of gbp_lin_iterate_until_nonlinear (gbp_lin_capi_until_nonlin.hip), whose sweeps are those of
+//                            gbp_lin_iterate_nonlinear[_robust] in gated forms: a sweep that relinearised anything may be made to decide nothing.
 // A maximum does not depend on the order it is taken in, so the step is exact; the two sums are added in a fixed order.  No
 // floating-point atomics.
 // The per-variable and finishing arithmetic are host/device routines (tests/hostmath/lin_until_shim.hip runs them on a CPU).
@@ -96,12 +98,31 @@ GBP_HD int until_row(const UntilRule &r, double step, double sq, double en, doub
     return GBP_LIN_STOP_NONE;
 }
 
+// the same row, and the decision of gbp_lin_iterate_until_nonlinear: with GBP_LIN_UNTIL_SETTLED in r.want a sweep in which any factor
+// relinearised (*count != 0, the sweep's slot of the relinearisation counts) decides nothing -- neither STEP nor MAP.  count == nullptr
+// or the bit clear: row and decision are until_row's.
+GBP_HD int until_row_settled(const UntilRule &r, const int *count, double step, double sq, double en, double *row)
+{
+    const int reason = until_row(r, step, sq, en, row);
+    if ((r.want & GBP_LIN_UNTIL_SETTLED) && count && *count != 0) return GBP_LIN_STOP_NONE;
+    return reason;
+}
+
+// the rule of gbp_lin_iterate_until_nonlinear: UntilRule and where the finishing kernel finds the sweep's relinearisation count
+struct UntilSettled : UntilRule {
+    const int *count;                // device: the slot of sweep `it` (LinNonlin::counts + it); complete when the finishing kernel runs,
+                                     // which the stream orders behind the relinearise kernel that adds to it
+};
+GBP_HD int until_decide(const UntilRule &r, double step, double sq, double en, double *row) { return until_row(r, step, sq, en, row); }
+GBP_HD int until_decide(const UntilSettled &r, double step, double sq, double en, double *row) { return until_row_settled(r, r.count, step, sq, en, row); }
+
 // ---- the finishing kernel --------------------------------------------------------------------------------------------------------
 
 // one block after sweep `it` + 1 of the call: row `it` of the trace, and the stop word.  Without variables (factors) there are no
 // partials: the step (the energy) is 0.  T = UNTIL_FIN threads (a template, so that a host-only build of this header has no kernel).
-template <int T>
-__global__ __launch_bounds__(T) void k_until_finish(LinUntil u, UntilRule r, int it)
+// RT = UntilRule: the linear call's; RT = UntilSettled: the decision also reads the sweep's relinearisation count.
+template <int T, typename RT = UntilRule>
+__global__ __launch_bounds__(T) void k_until_finish(LinUntil u, RT r, int it)
 {
     __shared__ double red[3][T];
     if (u.stop[0]) return;
@@ -115,7 +136,7 @@ __global__ __launch_bounds__(T) void k_until_finish(LinUntil u, UntilRule r, int
         __syncthreads();
     }
     if (t == 0) {
-        const int reason = until_row(r, red[0][0], red[1][0], red[2][0], u.trace + (size_t)it * 3);
+        const int reason = until_decide(r, red[0][0], red[1][0], red[2][0], u.trace + (size_t)it * 3);
         if (reason != GBP_LIN_STOP_NONE) { u.stop[1] = it + 1; u.stop[0] = reason; }
     }
 }

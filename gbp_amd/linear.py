@@ -67,12 +67,14 @@ def _loss_arrays(loss, threshold, noise_var, count):
 class UntilResult:
     """What LinearEngine.iterate_until returns: iters (the deciding sweep, or max_iters), converged, reason (GBP_LIN_STOP_*:
     _capi.LIN_STOP_STEP, LIN_STOP_MAP, or LIN_STOP_NONE when max_iters ran out), and one value per sweep run: step, energy,
-    map_distance (the last two None when not asked for)."""
-    __slots__ = ('iters', 'converged', 'reason', 'step', 'energy', 'map_distance')
+    map_distance (the last two None when not asked for).  From iterate_until_nonlinear also relin_counts, and with robustify
+    robust_counts: the factors relinearised / flagged in each sweep run, int32 (None otherwise)."""
+    __slots__ = ('iters', 'converged', 'reason', 'step', 'energy', 'map_distance', 'relin_counts', 'robust_counts')
 
-    def __init__(self, iters, converged, reason, step, energy, map_distance):
+    def __init__(self, iters, converged, reason, step, energy, map_distance, relin_counts=None, robust_counts=None):
         self.iters, self.converged, self.reason = iters, converged, reason
         self.step, self.energy, self.map_distance = step, energy, map_distance
+        self.relin_counts, self.robust_counts = relin_counts, robust_counts
 
     def __repr__(self):
         return f"UntilResult(iters={self.iters}, converged={self.converged}, reason={self.reason})"
@@ -316,6 +318,26 @@ class LinearEngine:
         rows = trace[:i.iters]
         return UntilResult(i.iters, bool(i.converged), i.reason, rows[:, 0].copy(),
                            rows[:, 1].copy() if energy else None, rows[:, 2].copy() if map_distance else None)
+
+    def iterate_until_nonlinear(self, max_iters, tol_step=0.0, tol_map=0.0, energy=False, map_distance=False, robustify=False, settled=False,
+                                check_every=8):
+        """iterate_until for an engine of se2_pose_graph: up to max_iters sweeps of iterate(1, relinearise=True) (robustify=True: of
+        iterate(1, robustify=True, relinearise=True)) in one call, the stop decided on the device by the rule of iterate_until.
+        energy / map_distance add what energy() / map_distance() would return after every sweep -- the distance is from the last
+        solve_map(), one Gauss-Newton step, wherever the linearisation has moved since.  settled=True: a sweep in which any factor
+        relinearised decides nothing, so a graph that relinearises in every sweep runs out max_iters.  The state afterwards is bit for
+        bit that of iterate(result.iters, robustify, relinearise=True), whatever check_every is.  Returns an UntilResult with
+        relin_counts (and, with robustify, robust_counts) per sweep run."""
+        want = (_capi.LIN_TRACE_ENERGY if energy else 0) | (_capi.LIN_TRACE_MAP if map_distance else 0) | (_capi.LIN_UNTIL_SETTLED if settled else 0)
+        o = _capi.LinUntilOpts(int(max_iters), int(check_every), int(bool(robustify)), want, float(tol_step), float(tol_map))
+        i = _capi.LinUntilInfo()
+        n = max(int(max_iters), 1)
+        trace, counts, flagged = np.full((n, 3), np.nan), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        check(self._lib.gbp_lin_iterate_until_nonlinear(self._h, ct.byref(o), dptr(trace), iptr(counts), iptr(flagged) if robustify else None, ct.byref(i)))
+        rows = trace[:i.iters]
+        return UntilResult(i.iters, bool(i.converged), i.reason, rows[:, 0].copy(), rows[:, 1].copy() if energy else None,
+                           rows[:, 2].copy() if map_distance else None, relin_counts=counts[:i.iters].copy(),
+                           robust_counts=flagged[:i.iters].copy() if robustify else None)
 
     def alloc_count(self):
         """The number of device allocations the handle owns (graph arrays and workspaces)."""

@@ -19,7 +19,8 @@
  * graph; sweeps to convergence with the stop decided on the device (gbp_lin_iterate_until); and one NONLINEAR factor family, the SE(2)
  * relative-pose factor, relinearised on the device by the reference's local schedule (gbp_lin_set_nonlinear), on a handle that grows
  * and shrinks too (gbp_lin_extend_nonlinear / gbp_lin_shrink_nonlinear) and takes robust losses of its own, made at the linearisation
- * point as the reference makes them (gbp_lin_set_robust_nonlinear / gbp_lin_iterate_nonlinear_robust) -- below.
+ * point as the reference makes them (gbp_lin_set_robust_nonlinear / gbp_lin_iterate_nonlinear_robust), and iterates to convergence on
+ * the device as well (gbp_lin_iterate_until_nonlinear) -- below.
  */
 #ifndef GBP_LIN_H
 #define GBP_LIN_H
@@ -407,11 +408,55 @@ int  gbp_lin_shrink_nonlinear(gbp_lin_t *h, const gbp_lin_shrink_desc_t *d);
  *                            repeated calls;
  *   gbp_lin_set_robust, gbp_lin_robustify, gbp_lin_iterate_robust, gbp_lin_iterate_until, gbp_lin_extend, gbp_lin_shrink   stay
  *                            refused with GBP_ESTATE; gbp_lin_set_nonlinear on a handle with linear losses set stays GBP_ESTATE.
+ *                            (Sweeps to convergence on such a handle: gbp_lin_iterate_until_nonlinear, at the end of this header.)
  * No floating-point atomics: two identical call sequences on two handles are bit-identical, both counts included. */
 int  gbp_lin_set_robust_nonlinear(gbp_lin_t *h, int32_t first, int32_t count, const int32_t *loss, const double *threshold);   /* Factor(loss=, mahalanobis_threshold=) gbp.py:209-210 */
 int  gbp_lin_robustify_nonlinear(gbp_lin_t *h);                                 /* robustify_all_factors gbp.py:82-84, at the linpoints */
 int  gbp_lin_iterate_nonlinear_robust(gbp_lin_t *h, int32_t n_iters, int32_t *relin_counts /* n_iters or NULL */,
                                       int32_t *robust_counts /* n_iters or NULL */);   /* n x synchronous_iteration(local_relin=True, robustify=True) gbp.py:86-92 */
+
+/* ---- iterating a NONLINEAR handle to convergence on the device: the loop
+ *        for i in range(n): graph.synchronous_iteration(local_relin=True[, robustify=True]); print(graph.energy(), norm(graph.get_means() - mu))
+ * in ONE call, without a synchronisation and two downloads per sweep ----
+ * gbp_lin_iterate_until_nonlinear takes the options and the info of gbp_lin_iterate_until (which stays refused on a nonlinear handle).
+ * Up to max_iters sweeps are queued; robustify 0: each is exactly one sweep of gbp_lin_iterate_nonlinear (relinearise; factor with
+ * per-factor damping, at the standing weights if losses are set; belief), robustify 1: exactly one of gbp_lin_iterate_nonlinear_robust
+ * (the fused robustify + relinearise lane; factor; belief) -- the same three kernels, plus the energy pass when asked for, plus the
+ * one-block finishing kernel.  Row i of the trace (written for i < iters only) describes the state after sweep i + 1:
+ *   column 0  step      max |mu_new - mu_old|, taken inside the belief stage as in gbp_lin_iterate_until: bit-equal to the same expression
+ *                       over two gbp_lin_get_means downloads.
+ *   column 1  energy    what gbp_lin_energy returns on this handle after the sweep: sum_f w_f 0.5 |h(mu) - diag(s) z|^2 through the
+ *                       nonlinear h (w_f = 1 without losses), added in a fixed order on the device.  NaN unless GBP_LIN_TRACE_ENERGY.
+ *   column 2  distance  |means - x|_2 against the iterate of the last gbp_lin_solve_map.  That solve is ONE Gauss-Newton step at the
+ *                       linearisation point and the weights it found; the distance is from that solve, wherever the linearisation has
+ *                       moved since.  NaN unless GBP_LIN_TRACE_MAP.
+ * relin_counts[i] / robust_counts[i] (host, max_iters each, or NULL): what gbp_lin_iterate_nonlinear / gbp_lin_iterate_nonlinear_robust
+ * return for sweep i, counted the same way (one ballot, one popcount and one integer atomic add per wave) in the handle's own count
+ * buffers, which grow to max_iters; downloaded once after the call, and only the first `iters` entries are written.
+ * The stop rule is gbp_lin_iterate_until's: STEP is tested before MAP, the device decides and sets the stop word.  With
+ * GBP_LIN_UNTIL_SETTLED in `want` a sweep in which ANY factor relinearised decides neither: a step can be small in the very sweep that
+ * moves linearisation points, and only the device knows.  (The finishing kernel reads that sweep's count slot; the stream orders it behind
+ * the relinearise kernel's adds.)  A graph that relinearises in every sweep therefore never stops under this bit: converged = 0, reason
+ * NONE, GBP_OK.  The bit belongs to this call alone: gbp_lin_iterate_until answers it with GBP_EINVAL like any unknown bit.
+ * Every kernel of a sweep queued behind the deciding one returns at its head, the relinearise lane included: it writes no iters,
+ * linpoint, factor, damping, weight or flag and adds to no count.  So after the call both messages, beliefs and means, eta_f, Lambda_f,
+ * linpoint, iters_since_relin and the per-factor damping, weights and flags are bit for bit those of gbp_lin_iterate_nonlinear(h, iters)
+ * (or gbp_lin_iterate_nonlinear_robust) on an identical handle, for every check_every.
+ * The call marks the solver's LDL^T and joint eta stale (the linearisation point and the weights may have moved).  It reuses the
+ * workspace of gbp_lin_iterate_until: the partials are dropped by gbp_lin_extend_nonlinear / gbp_lin_shrink_nonlinear and re-made by the
+ * next call; a repeated call of the same size allocates nothing (gbp_lin_get_alloc_count).  No floating-point atomics: two identical call
+ * sequences on two handles give bit-identical traces and counts.
+ * GBP_ESTATE: a handle without nonlinear factors; robustify without losses set; GBP_LIN_TRACE_MAP without a solve (also after
+ * gbp_lin_extend_nonlinear / gbp_lin_shrink_nonlinear, until the next solve).  GBP_EINVAL: opts NULL; max_iters < 0; check_every < 1;
+ * robustify not 0 or 1; bits in want outside ENERGY | MAP | SETTLED; a tolerance that is negative or not finite; tol_map > 0 without
+ * GBP_LIN_TRACE_MAP; robust_counts != NULL with robustify == 0.  All decided before anything changes.  max_iters == 0: GBP_OK, nothing
+ * written.  Without factors the step is exactly 0 from the first sweep and both counts are 0. */
+#define GBP_LIN_UNTIL_SETTLED 4   /* in `want`, this call only: a sweep in which any factor relinearised decides nothing */
+int  gbp_lin_iterate_until_nonlinear(gbp_lin_t *h, const gbp_lin_until_opts_t *opts,
+                                     double *trace          /* host, max_iters x 3, or NULL */,
+                                     int32_t *relin_counts  /* host, max_iters, or NULL */,
+                                     int32_t *robust_counts /* host, max_iters, or NULL; must be NULL when opts->robustify == 0 */,
+                                     gbp_lin_until_info_t *info /* or NULL */);
 
 #ifdef __cplusplus
 }

@@ -46,7 +46,11 @@ ap.add_argument('--nonlinear-robust', action='store_true',
                 help='time the robust relinearising sweep (gbp_lin_iterate_nonlinear_robust) against gbp_lin_iterate_nonlinear on the two graphs of '
                      '--nonlinear, fused and with robustify as a launch of its own, and the sweeps without losses against --parent-lib; writes '
                      'profiles/linear_nonlinear_robust.json')
-ap.add_argument('--parent-lib', default=None, help="--nonlinear-live / --nonlinear-robust: the parent commit's libgbp_hip.so, loaded beside this one for the yardsticks")
+ap.add_argument('--nonlinear-until', action='store_true',
+                help='ms per sweep of iterate_until_nonlinear (plain, with the energy column, with both columns) against iterate_nonlinear and the host '
+                     'loop iterate(1, relinearise=True); energy(), at beta = +inf and beta = 0; with --parent-lib the older sweeps against the parent '
+                     "commit's library; writes profiles/linear_nonlinear_until.json")
+ap.add_argument('--parent-lib', default=None, help="--nonlinear-live / --nonlinear-robust / --nonlinear-until: the parent commit's libgbp_hip.so, loaded beside this one for the yardsticks")
 ap.add_argument('--parent-results', default=None,
                 help="--extend / --shrink / --until / --nonlinear: a file of lines 'parent {json}' / 'here {json}', each the JSON line of a plain run of this tool from the parent "
                      "commit's tree or from this one (run alternating, in the same session); summarised per workload under sweeps_per_s_vs_parent")
@@ -802,6 +806,112 @@ def nonlinear_robust_profile():
     print(json.dumps(out))
 
 
+def nonlinear_until_profile():
+    """Host clock around whole calls, each ending in a stream synchronise, after a warm-up of every form; --repeats alternating rounds of
+    --steps sweeps, medians reported per sweep, spread = (max - min) / median.  On the two graphs of --nonlinear, once with beta = +inf
+    (the relinearise stage runs and relinearises nothing) and once with beta = 0, min_linear_iters = 0 (every factor relinearises in every
+    sweep), tolerances off so that every form runs --steps sweeps: `iterate_nonlinear` (gbp_lin_iterate_nonlinear), `until`
+    (gbp_lin_iterate_until_nonlinear, no column asked for), `until_energy`, `until_both` (energy and MAP distance, after one solve_map),
+    and `host_loop`, the loop the call replaces: iterate(1, relinearise=True); energy() per sweep -- three calls that run the same
+    device code as before this call existed, timed on this library.  Counted beside each ratio over iterate_nonlinear, in doubles per
+    factor on top of the relinearising sweep's count (--nonlinear: the plain sweep + 14 at beta = +inf, + 53 at beta = 0): the trace
+    reads the old mean per variable (3) and writes one partial per 7 variables, and with the distance reads x (3) and writes a second
+    partial, times variables per factor; the energy pass gathers two means (6) and reads z and s (6) and one partial per 256 factors.
+    Each adds kernel boundaries priced at 3.2 us: the finishing kernel (1), the energy pass (1).  The counts are of algorithmic bytes;
+    an excess of a measured ratio over its count by more than the spread is UNEXPLAINED here -- no counters were collected.  With
+    --parent-lib: gbp_lin_iterate_nonlinear and gbp_lin_iterate, this library against the parent commit's in one process, alternating,
+    once with the parent's handle created first and once with this library's; the margin is the larger of the two spreads."""
+    import ctypes as ct
+    from gbp_amd import _capi
+    here = _capi.load()
+    parent = ct.CDLL(os.path.abspath(a.parent_lib)) if a.parent_lib else None
+    D, runs, n, boundary_ms = 3, [], a.steps, 3.2e-3
+    for N, k in ((200_000, 5), (1_000_000, 1)):
+        va, vb, z, s, pe, pl = se2_graph(N, k, np.random.RandomState(0))
+        F = va.shape[0]
+        for tag, beta, minlin, extra in (('beta_inf', float('inf'), 2, 14), ('beta_0', 0.0, 0, 53)):
+            e = LinearEngine.se2_pose_graph(va, vb, z, s, pe, pl, beta, 4, minlin, eta_damping=0.4)
+            e.solve_map()
+
+            def timed(fn):
+                t = time.perf_counter(); fn(); e.sync()
+                return 1e3 * (time.perf_counter() - t) / n
+
+            def until(want):
+                o = _capi.LinUntilOpts(n, 8, 0, want, 0.0, 0.0)
+                i = _capi.LinUntilInfo()
+                assert e._lib.gbp_lin_iterate_until_nonlinear(e._h, ct.byref(o), None, None, None, ct.byref(i)) == 0 and i.iters == n
+
+            def host_loop():
+                for _ in range(n):
+                    e.iterate(1, relinearise=True); e.energy()
+            forms = {'iterate_nonlinear': lambda: timed(lambda: e._lib.gbp_lin_iterate_nonlinear(e._h, n, None)),
+                     'until': lambda: timed(lambda: until(0)),
+                     'until_energy': lambda: timed(lambda: until(_capi.LIN_TRACE_ENERGY)),
+                     'until_both': lambda: timed(lambda: until(_capi.LIN_TRACE_ENERGY | _capi.LIN_TRACE_MAP)),
+                     'host_loop': lambda: timed(host_loop)}
+            for fn in forms.values():
+                fn()
+            rec = {key: [] for key in forms}
+            for _ in range(a.repeats):                      # alternating
+                for key, fn in forms.items():
+                    rec[key].append(fn())
+            med = {key: statistics.median(v) for key, v in rec.items()}
+            spread = {key: (max(v) - min(v)) / med[key] for key, v in rec.items()}
+            vpf = 1.0 / k
+            per_f = sweep_doubles(D, vpf, False) + extra
+            add = {'until': vpf * (3 + 1 / 7.0), 'until_energy': vpf * (3 + 1 / 7.0) + 12 + 1 / 256.0,
+                   'until_both': vpf * (6 + 2 / 7.0) + 12 + 1 / 256.0, 'host_loop': 12 + 1 / 256.0}
+            bounds = {'until': 1, 'until_energy': 2, 'until_both': 2, 'host_loop': 1}
+            ratios = {}
+            for key in add:
+                measured, base = med[key] / med['iterate_nonlinear'], med['iterate_nonlinear']
+                counted = (per_f + add[key]) / per_f + bounds[key] * boundary_ms / base
+                margin = max(spread[key], spread['iterate_nonlinear'])
+                ratios[key] = {"measured": measured, "counted": counted, "doubles_added_per_factor": add[key], "kernel_boundaries_added": bounds[key],
+                               "margin": margin, "unexplained_excess": bool(measured - counted > margin)}
+            runs.append({"vars": N, "dofs": D, "k": k, "factors": F, "beta": tag, "ms_per_sweep": med, "spread": spread, "ms_all": rec,
+                         "doubles_per_factor_relinearising_sweep": per_f, "ratio_over_iterate_nonlinear": ratios,
+                         "ratio_host_loop_over_until_energy": med['host_loop'] / med['until_energy'], "counters_collected": False})
+            e.close()
+        if parent:
+            vs_parent = {}
+            for order in ('parent_created_first', 'here_created_first'):
+                first, second = (parent, here) if order == 'parent_created_first' else (here, parent)
+                h1 = RawSE2(first, va, vb, z, s, pe, pl, float('inf'), 2)
+                h2 = RawSE2(second, va, vb, z, s, pe, pl, float('inf'), 2)
+                hp, hh = (h1, h2) if order == 'parent_created_first' else (h2, h1)
+                for call in ('gbp_lin_iterate_nonlinear', 'gbp_lin_iterate'):
+                    def sweeps(h):
+                        t = time.perf_counter()
+                        rc = h.lib.gbp_lin_iterate_nonlinear(h.h, ct.c_int32(n), None) if call == 'gbp_lin_iterate_nonlinear' else h.lib.gbp_lin_iterate(h.h, ct.c_int32(n))
+                        assert rc == 0 and h.lib.gbp_lin_sync(h.h) == 0
+                        return n / (time.perf_counter() - t)
+                    sweeps(hp); sweeps(hh)
+                    tp, th = [], []
+                    for _ in range(a.repeats):
+                        tp.append(sweeps(hp)); th.append(sweeps(hh))
+                    mp, mh = statistics.median(tp), statistics.median(th)
+                    sp, sh = (max(tp) - min(tp)) / mp, (max(th) - min(th)) / mh
+                    vs_parent[call + '_' + order] = {"sweeps_per_s_parent": mp, "sweeps_per_s_here": mh, "ratio_here_over_parent": mh / mp, "spread_parent": sp,
+                                                     "spread_here": sh, "margin": max(sp, sh), "beyond_margin": abs(mh / mp - 1.0) > max(sp, sh),
+                                                     "all_parent": tp, "all_here": th}
+                hp.close(); hh.close()
+            runs.append({"vars": N, "dofs": D, "k": k, "factors": F, "sweeps_per_s_vs_parent": vs_parent})
+    out = {"what": "tools/bench_linear.py --nonlinear-until on one MI355X: ms per sweep of gbp_lin_iterate_until_nonlinear against gbp_lin_iterate_nonlinear and "
+                   "the host loop it replaces, and the older sweeps against the parent commit's library, on the 200k x 3 ring (k = 5) and the 1M-variable "
+                   "chain (k = 1) re-posed as SE(2)",
+           "method": " ".join(nonlinear_until_profile.__doc__.split()), "repeats": a.repeats, "sweep_steps": a.steps, "runs": runs}
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'profiles', 'linear_nonlinear_until.json')
+    with open(path, 'w') as fh:
+        json.dump(out, fh, indent=1)
+        fh.write('\n')
+    print(json.dumps(out))
+
+
+if a.nonlinear_until:
+    nonlinear_until_profile()
+    sys.exit(0)
 if a.nonlinear_robust:
     nonlinear_robust_profile()
     sys.exit(0)
