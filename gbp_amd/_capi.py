@@ -251,6 +251,8 @@ class LinExtNonlinear(ct.Structure):
 
 
 LIN_MODEL_SE2_BETWEEN = 1                           # GBP_LIN_MODEL_* (include/gbp_lin.h)
+LIN_MODEL_SE3_BETWEEN = 2
+LIN_MODEL_DOFS = {LIN_MODEL_SE2_BETWEEN: 3, LIN_MODEL_SE3_BETWEEN: 6}   # dofs of a variable = rows of a measurement
 LIN_TRACE_ENERGY, LIN_TRACE_MAP = 1, 2              # GBP_LIN_TRACE_* (include/gbp_lin.h)
 LIN_UNTIL_SETTLED = 4                               # GBP_LIN_UNTIL_SETTLED: in `want` of gbp_lin_iterate_until_nonlinear only
 LIN_STOP_NONE, LIN_STOP_STEP, LIN_STOP_MAP = 0, 1, 2   # GBP_LIN_STOP_*

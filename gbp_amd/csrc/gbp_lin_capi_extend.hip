@@ -87,8 +87,9 @@ int ext_build(gbp_lin *h, const gbp_lin_extend_desc_t *d, const gbp_lin_extend_n
             LCHK(ext_upload(h, mem, &t.d[LC_FCONST], host.fconst));
         }
     } else {                                                // as gbp_lin_set_nonlinear packs the whole
-        host.meas.resize((size_t)NL_M * dF); host.sinfo.resize((size_t)NL_M * dF);
-        lin_pack_measurements(dF, nl->measurement, nl->sqrt_info, host.meas.data(), host.sinfo.data());
+        const int M = lin_model_rows(h->nl.model);
+        host.meas.resize((size_t)M * dF); host.sinfo.resize((size_t)M * dF);
+        lin_pack_measurements(M, dF, nl->measurement, nl->sqrt_info, host.meas.data(), host.sinfo.data());
         LCHK(ext_upload(h, mem, &t.d[LC_MEAS], host.meas)); LCHK(ext_upload(h, mem, &t.d[LC_SINFO], host.sinfo));
     }
     if (n.robust && d->loss && dF) {
@@ -239,7 +240,7 @@ int gbp_lin_extend_nonlinear(gbp_lin_t *h, const gbp_lin_extend_nonlinear_desc_t
     LCHK(ext_validate(h, &d, true));
     const int F = h->p.F, dF = nl->n_new_factors;
     if (dF && (!nl->measurement || !nl->sqrt_info)) return set_error(GBP_EINVAL, "NULL array in the descriptor");
-    LCHK(lin_check_measurements(nl->measurement, nl->sqrt_info, dF, "new factor"));    // the rules of gbp_lin_set_nonlinear
+    LCHK(lin_check_measurements(h->nl.model, nl->measurement, nl->sqrt_info, dF, "new factor"));    // the rules of gbp_lin_set_nonlinear
     if (!nl->n_new_vars && !dF) return GBP_OK;
     // Losses (gbp_lin_set_robust_nonlinear) stay set: the old factors carry loss, threshold, weight and flag, the new ones start at the
     // columns' fills -- NONE, weight 1, flag 0 -- until that call gives them a loss by range.  Ends with the belief stage: a nonlinear

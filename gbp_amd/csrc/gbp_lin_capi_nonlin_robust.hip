@@ -1,11 +1,11 @@
 // gbp_lin_capi_nonlin_robust.hip -- robust losses on a nonlinear handle (include/gbp_lin.h): Factor(loss=, mahalanobis_threshold=) on
 // FactorGraph(nonlinear_factors=True), Factor.robustify_loss (gbp.py:296-332), robustify_all_factors (gbp.py:82-84) and
-// synchronous_iteration(local_relin=True, robustify=True) (gbp.py:86-92) for the SE(2) relative-pose factor.
+// synchronous_iteration(local_relin=True, robustify=True) (gbp.py:86-92) for the SE(2) and SE(3) relative-pose factors.
 //
 // The weight is made from M_f = |diag(s) z - h(linpoint_f)| -- at the LINPOINT, the reference's reading (gbp.py:309), which here moves
 // with every relinearisation -- by the relinearise lane itself: k_lin_relin<MODEL, true> (gbp_lin_nonlin.hpp) robustifies a factor at
 // its linpoint as it stands and then runs the relinearisation test and re-make unchanged, so a robust relinearising sweep is still three
-// kernels (that, k_lin_factor<3, true, LinRelin>, k_lin_belief), with no host round trip and no floating-point atomics.  The weight
+// kernels (that, k_lin_factor<D, true, LinRelin>, k_lin_belief), with no host round trip and no floating-point atomics.  The weight
 // multiplies the factor as linearised wherever it is used, exactly as on a linear handle: LinParams::w is what the factor stage, the
 // energy and the joint read, and nullptr -- the plain nonlinear path -- until losses are set and again after they are cleared.  The
 // arrays are the robust columns of a generation (lin_gen_columns): the first gbp_lin_set_robust_nonlinear allocates them through that
@@ -29,8 +29,10 @@ int nlr_check_state(gbp_lin *h)
 void nlr_relin(gbp_lin *h, int mode, int *count, int *rcount)
 {
     if (!h->p.F) return;
-    hipLaunchKernelGGL((k_lin_relin<GBP_LIN_MODEL_SE2_BETWEEN, true>), dim3((h->p.F + 255) / 256), dim3(256), 0, h->stream, h->p, h->nl, mode, count, h->rob,
-                       rcount);
+    lin_model_dispatch(h->nl.model, [&](auto m) {
+        hipLaunchKernelGGL((k_lin_relin<decltype(m)::value, true>), dim3((h->p.F + 255) / 256), dim3(256), 0, h->stream, h->p, h->nl, mode, count, h->rob,
+                           rcount);
+    });
 }
 
 template <typename T>

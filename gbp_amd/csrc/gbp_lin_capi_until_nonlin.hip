@@ -6,8 +6,8 @@
 // the kernel text that call launches, instantiated with the parameter block that gates it --
 //   k_lin_relin<MODEL, ROBUST, LinGated>      relinearise (with losses and robustify: the fused robustify + relinearise lane), counted into
 //                                             the handle's own count buffers; a gated launch writes nothing and adds to no count;
-//   k_lin_factor<3, ROBUST, LinRelinGated>    per-factor damping and the stop word in one block;
-//   k_lin_belief<3, LinTraced>                gated, with the step and the squared MAP distance of its block;
+//   k_lin_factor<D, ROBUST, LinRelinGated>    per-factor damping and the stop word in one block;
+//   k_lin_belief<D, LinTraced>                gated, with the step and the squared MAP distance of its block;
 //   k_lin_energy_nl<MODEL, LinGated>          when the energy is traced, into the call's own partials;
 //   k_until_finish<UNTIL_FIN, UntilSettled>   the row, and the decision, which under GBP_LIN_UNTIL_SETTLED reads the sweep's count slot.
 // Sweeps are queued check_every at a time; the host reads the stop word (8 bytes) after each batch; trace and counts are copied out once,
@@ -22,13 +22,14 @@ using namespace gbp;
 namespace {
 
 constexpr int KNOWN_WANT = GBP_LIN_TRACE_ENERGY | GBP_LIN_TRACE_MAP | GBP_LIN_UNTIL_SETTLED;
-constexpr int MODEL = GBP_LIN_MODEL_SE2_BETWEEN;
 
 bool tol_ok(double t) { return t >= 0.0 && std::isfinite(t); }
 
 // sweep `it` + 1 of the call: every kernel gated on the stop word
+template <int MODEL>
 int until_nl_sweep(gbp_lin *h, const gbp_lin_until_opts_t &o, const UntilSettled &rule, int it)
 {
+    constexpr int D = NonlinModel<MODEL>::D;
     const LinUntil &u = h->until;
     const LinNonlin &nl = h->nl;
     const LinGated g{h->p, u.stop};
@@ -38,10 +39,10 @@ int until_nl_sweep(gbp_lin *h, const gbp_lin_until_opts_t &o, const UntilSettled
         if (o.robustify) hipLaunchKernelGGL((k_lin_relin<MODEL, true, LinGated>), lanes, dim3(256), 0, h->stream, g, nl, NL_SWEEP, nl.counts + it, h->rob, nl.rcounts + it);
         else hipLaunchKernelGGL((k_lin_relin<MODEL, false, LinGated>), lanes, dim3(256), 0, h->stream, g, nl, NL_SWEEP, nl.counts + it, LinRobust{}, (int *)nullptr);
         const LinRelinGated r{{h->p, nl.fdamp}, u.stop};
-        if (h->p.w) hipLaunchKernelGGL((k_lin_factor<NL_D, true, LinRelinGated>), waves, dim3(64), 0, h->stream, r);
-        else hipLaunchKernelGGL((k_lin_factor<NL_D, false, LinRelinGated>), waves, dim3(64), 0, h->stream, r);
+        if (h->p.w) hipLaunchKernelGGL((k_lin_factor<D, true, LinRelinGated>), waves, dim3(64), 0, h->stream, r);
+        else hipLaunchKernelGGL((k_lin_factor<D, false, LinRelinGated>), waves, dim3(64), 0, h->stream, r);
     }
-    if (h->p.N) hipLaunchKernelGGL((k_lin_belief<NL_D, LinTraced>), dim3(u.nbel), dim3(64), 0, h->stream, t);
+    if (h->p.N) hipLaunchKernelGGL((k_lin_belief<D, LinTraced>), dim3(u.nbel), dim3(64), 0, h->stream, t);
     if (h->p.F && (o.want & GBP_LIN_TRACE_ENERGY)) hipLaunchKernelGGL((k_lin_energy_nl<MODEL, LinGated>), dim3(u.nen), dim3(256), 0, h->stream, g, nl, u.en_part);
     UntilSettled r = rule;
     r.count = nl.counts + it;
@@ -89,7 +90,11 @@ int gbp_lin_iterate_until_nonlinear(gbp_lin_t *h, const gbp_lin_until_opts_t *op
     int it = 0, stop[2] = {0, 0};
     while (it < o.max_iters && !stop[0]) {
         const int n = std::min(o.check_every, o.max_iters - it);
-        for (int j = 0; j < n; ++j, ++it) LCHK(until_nl_sweep(h, o, rule, it));
+        for (int j = 0; j < n; ++j, ++it) {
+            int rc = GBP_OK;
+            lin_model_dispatch(nl.model, [&](auto m) { rc = until_nl_sweep<decltype(m)::value>(h, o, rule, it); });
+            LCHK(rc);
+        }
         LHIPCHK(hipMemcpyAsync(stop, u.stop, sizeof(stop), hipMemcpyDeviceToHost, h->stream));
         LHIPCHK(hipStreamSynchronize(h->stream));
     }

@@ -77,10 +77,14 @@ template <typename T> struct LinColumn {
 
 // Every array with stride F, whether `g` has its group or not (LinGen::has): visit(LinColumn<int or double>).  A handle whose losses
 // were cleared keeps stale losses and weights in its robust arrays: its old factors are at NONE, so `old` is nullptr and the fill applies.
+// The three nonlinear arrays wider than a row take their rows from the handle's model (lin_model_rows / lin_model_dofs); a handle that
+// is not nonlinear yet has none, and the model its caller is about to install is passed as `model` (gbp_lin_set_nonlinear).
 template <typename V>
-void lin_gen_columns(const gbp_lin *h, LinGen &g, V &&visit)
+void lin_gen_columns(const gbp_lin *h, LinGen &g, V &&visit, int model = 0)
 {
     const LinRows r = lin_rows(h->D);
+    if (h->nonlinear) model = h->nl.model;
+    const int nl_m = lin_model_rows(model), nl_d = lin_model_dofs(model);
     const LinParams &o = h->p;
     const LinRobust orob = h->rob_alloc ? h->rob : LinRobust{};
     const LinNonlin onl = h->nonlinear ? h->nl : LinNonlin{};
@@ -96,8 +100,8 @@ void lin_gen_columns(const gbp_lin *h, LinGen &g, V &&visit)
     col(LC_LOSS, LIN_ROBUST, orob.loss, g.rob.loss, 1, LIN_NEW_LOSS); col(LC_THR, LIN_ROBUST, orob.thr, g.rob.thr, 1, LIN_NEW_THR);
     col(LC_NVAR, LIN_ROBUST, orob.nvar, g.rob.nvar, 1, LIN_NEW_NVAR); col(LC_W, LIN_ROBUST, orob.w, g.rob.w, 1, LIN_NEW_W);
     col(LC_FLAG, LIN_ROBUST, orob.flag, g.rob.flag, 1, LIN_NEW_FLAG);
-    col(LC_MEAS, LIN_NONLIN, onl.meas, g.nl.meas, NL_M, 0.0); col(LC_SINFO, LIN_NONLIN, onl.sinfo, g.nl.sinfo, NL_M, LIN_NEW_SINFO);
-    col(LC_LINPOINT, LIN_NONLIN, onl.linpoint, g.nl.linpoint, 2 * NL_D, 0.0);
+    col(LC_MEAS, LIN_NONLIN, onl.meas, g.nl.meas, nl_m, 0.0); col(LC_SINFO, LIN_NONLIN, onl.sinfo, g.nl.sinfo, nl_m, LIN_NEW_SINFO);
+    col(LC_LINPOINT, LIN_NONLIN, onl.linpoint, g.nl.linpoint, 2 * nl_d, 0.0);
     col(LC_ITERS, LIN_NONLIN, onl.iters, g.nl.iters, 1, LIN_NEW_ITERS); col(LC_FDAMP, LIN_NONLIN, onl.fdamp, g.nl.fdamp, 1, LIN_NEW_FDAMP);
 }
 
@@ -237,21 +241,39 @@ inline int lin_check_losses(const int32_t *loss, const double *thr, const double
     return GBP_OK;
 }
 
-// The rules for `count` measurements with their square-root informations, both [count][NL_M] (include/gbp_lin.h,
+// The rules for `count` measurements of `model` with their square-root informations, both [count][M] (include/gbp_lin.h,
 // gbp_lin_set_nonlinear); `prefix` names a factor in the message.  Refused, entry by entry: a sqrt_info that is not positive and
-// finite, then a measurement that is not finite.
-inline int lin_check_measurements(const double *meas, const double *sinfo, int count, const char *prefix)
+// finite, then a measurement that is not finite; then, for GBP_LIN_MODEL_SE3_BETWEEN, factor by factor a measured rotation vector
+// (the last three entries) whose norm is not below pi.
+inline int lin_check_measurements(int model, const double *meas, const double *sinfo, int count, const char *prefix)
 {
-    for (size_t i = 0; i < (size_t)count * NL_M; ++i) {
-        if (!(sinfo[i] > 0.0) || !std::isfinite(sinfo[i])) return set_error(GBP_EINVAL, "%s %d: sqrt_info must be positive and finite", prefix, (int)(i / NL_M));
-        if (!std::isfinite(meas[i])) return set_error(GBP_EINVAL, "%s %d: the measurement must be finite", prefix, (int)(i / NL_M));
+    const int M = lin_model_rows(model);
+    for (size_t i = 0; i < (size_t)count * M; ++i) {
+        if (!(sinfo[i] > 0.0) || !std::isfinite(sinfo[i])) return set_error(GBP_EINVAL, "%s %d: sqrt_info must be positive and finite", prefix, (int)(i / M));
+        if (!std::isfinite(meas[i])) return set_error(GBP_EINVAL, "%s %d: the measurement must be finite", prefix, (int)(i / M));
     }
+    if (model == GBP_LIN_MODEL_SE3_BETWEEN)
+        for (int f = 0; f < count; ++f) {
+            const double *w = meas + (size_t)f * M + 3;
+            if (!(std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]) < 3.14159265358979323846))
+                return set_error(GBP_EINVAL, "%s %d: the measured rotation vector must have a norm below pi", prefix, f);
+        }
     return GBP_OK;
 }
 
-// the same two lists -> SoA rows with stride `count`: out_meas, out_sinfo [NL_M][count]
-inline void lin_pack_measurements(int count, const double *meas, const double *sinfo, double *out_meas, double *out_sinfo)
+// the form from before there was a second model: GBP_LIN_MODEL_SE2_BETWEEN
+inline int lin_check_measurements(const double *meas, const double *sinfo, int count, const char *prefix)
+{
+    return lin_check_measurements(GBP_LIN_MODEL_SE2_BETWEEN, meas, sinfo, count, prefix);
+}
+
+// the same two lists -> SoA rows with stride `count`: out_meas, out_sinfo [M][count]
+inline void lin_pack_measurements(int M, int count, const double *meas, const double *sinfo, double *out_meas, double *out_sinfo)
 {
     for (int f = 0; f < count; ++f)
-        for (int k = 0; k < NL_M; ++k) { out_meas[(size_t)k * count + f] = meas[(size_t)f * NL_M + k]; out_sinfo[(size_t)k * count + f] = sinfo[(size_t)f * NL_M + k]; }
+        for (int k = 0; k < M; ++k) { out_meas[(size_t)k * count + f] = meas[(size_t)f * M + k]; out_sinfo[(size_t)k * count + f] = sinfo[(size_t)f * M + k]; }
+}
+inline void lin_pack_measurements(int count, const double *meas, const double *sinfo, double *out_meas, double *out_sinfo)
+{
+    lin_pack_measurements(lin_model_rows(GBP_LIN_MODEL_SE2_BETWEEN), count, meas, sinfo, out_meas, out_sinfo);
 }

@@ -96,11 +96,14 @@ struct LinUntil {
 // per-factor is SoA with stride F like the rest of the handle, and travels with a generation: gbp_lin_extend_nonlinear /
 // gbp_lin_shrink_nonlinear rebuild the five per-factor arrays with the graph's, and lin_gen_commit (gbp_lin_generation.hpp) installs
 // them.  feta / flam are the handle's own factor arrays (LinParams::feta / flam), writable; the same commit re-points them.
-constexpr int NL_D = 3;                                   // dofs of a variable of every model so far
-constexpr int NL_M = 3;                                   // rows of a measurement
+// Per model: D, the dofs of a variable, and M, the rows of a measurement -- 3 and 3 for GBP_LIN_MODEL_SE2_BETWEEN, 6 and 6 for
+// GBP_LIN_MODEL_SE3_BETWEEN.  NonlinModel<MODEL>::D / ::M (gbp_lin_nonlin.hpp) are the same numbers where the model is a template
+// argument; these two are for the host code that has the handle's model as a value (0: not a model).
+constexpr int lin_model_dofs(int model) { return model == GBP_LIN_MODEL_SE2_BETWEEN ? 3 : model == GBP_LIN_MODEL_SE3_BETWEEN ? 6 : 0; }
+constexpr int lin_model_rows(int model) { return lin_model_dofs(model); }
 struct LinNonlin {
-    const double *meas, *sinfo;      // [3][F] measurement z, square-root information s
-    double *linpoint;                // [6][F] Factor.linpoint gbp.py:231 = [xa; xb]
+    const double *meas, *sinfo;      // [M][F] measurement z, square-root information s
+    double *linpoint;                // [2D][F] Factor.linpoint gbp.py:231 = [xa; xb]
     int *iters;                      // [F] Factor.iters_since_relin gbp.py:249
     double *fdamp;                   // [F] Factor.eta_damping gbp.py:248
     double *feta, *flam;             // what the relinearise stage rewrites
@@ -227,4 +230,12 @@ static void lin_dispatch(int D, K &&k)
     case 5: k(std::integral_constant<int, 5>{}); break;
     default: k(std::integral_constant<int, 6>{}); break;
     }
+}
+
+// the handle's model as a template argument: k(std::integral_constant<int, GBP_LIN_MODEL_*>).  gbp_lin_set_nonlinear admits no other value
+template <typename K>
+static void lin_model_dispatch(int model, K &&k)
+{
+    if (model == GBP_LIN_MODEL_SE3_BETWEEN) k(std::integral_constant<int, GBP_LIN_MODEL_SE3_BETWEEN>{});
+    else k(std::integral_constant<int, GBP_LIN_MODEL_SE2_BETWEEN>{});
 }

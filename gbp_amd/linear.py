@@ -100,7 +100,8 @@ class LinearEngine:
         d.prior_eta, d.prior_lam = dptr(prior_eta), dptr(prior_lam)
         d.eta_damping = float(eta_damping)
         self._h = ct.c_void_p()
-        self._nonlinear = False                              # set_nonlinear was called: the handle grows by extend_se2, shrinks by gbp_lin_shrink_nonlinear
+        self._nonlinear = False                              # set_nonlinear was called: the handle grows by extend_se2 / extend_se3, shrinks by gbp_lin_shrink_nonlinear
+        self._model = None                                   # its model then (_capi.LIN_MODEL_*)
         check(self._lib.gbp_lin_create(ct.byref(self._h), ct.byref(d)))
 
     @classmethod
@@ -267,12 +268,35 @@ class LinearEngine:
         eng.set_nonlinear(measurement, sqrt_info, beta, num_undamped_iters, min_linear_iters)
         return eng
 
+    @classmethod
+    def se3_pose_graph(cls, var_a, var_b, measurement, sqrt_info, prior_eta, prior_lam, beta, num_undamped_iters, min_linear_iters,
+                       eta_damping=0.0, device=0):
+        """A spatial pose graph on variables (t, w) in R^6, translation then rotation vector (R = Exp(w)): factor f joins var_a[f] and
+        var_b[f] with measurement[f] = (z_t, z_w), the pose of b in the frame of a with the relative rotation as a rotation vector, and
+        sqrt_info[f] > 0 per component.  Everything else is se2_pose_graph's: linearised on the device at the prior means, relinearised
+        by iterate(n, relinearise=True) on the reference's local schedule; losses, extend_se3, retire / cull and
+        iterate_until_nonlinear work as on a planar graph, linearisation() returns (F, 12) points.
+        The domain: w is never wrapped -- keep it continuous along the trajectory; |w| > pi is legal -- while relative rotations and
+        z_w stay below pi in norm (a z_w at or past pi is refused).  Jr(w) loses rank at |w| = 2 pi k."""
+        var_a = i32(var_a).reshape(-1)
+        F = var_a.shape[0]
+        eng = cls(var_a, var_b, np.zeros((F, 12)), np.zeros((F, 12, 12)), prior_eta, prior_lam, eta_damping=eta_damping, device=device)
+        if eng.D != 6:
+            raise ValueError("an SE(3) pose has 6 dofs")
+        eng.set_nonlinear(measurement, sqrt_info, beta, num_undamped_iters, min_linear_iters, model=_capi.LIN_MODEL_SE3_BETWEEN)
+        return eng
+
     def set_nonlinear(self, measurement, sqrt_info, beta, num_undamped_iters, min_linear_iters, model=_capi.LIN_MODEL_SE2_BETWEEN):
-        z = f64(np.asarray(measurement, dtype=np.float64).reshape(self.F, 3))
-        s = f64(np.ascontiguousarray(np.broadcast_to(np.asarray(sqrt_info, dtype=np.float64), (self.F, 3))))
+        """gbp_lin_set_nonlinear: measurement and sqrt_info are F x M for the model's M (3 for LIN_MODEL_SE2_BETWEEN, 6 for
+        LIN_MODEL_SE3_BETWEEN, whose domain rule se3_pose_graph states); a model the library does not know is sent as it is, with
+        the arrays it was given, and refused there."""
+        M = _capi.LIN_MODEL_DOFS.get(int(model))
+        z = np.asarray(measurement, dtype=np.float64)
+        z = f64(z.reshape(self.F, M) if M else np.atleast_2d(z))
+        s = f64(np.ascontiguousarray(np.broadcast_to(np.asarray(sqrt_info, dtype=np.float64), z.shape)))
         d = _capi.LinNonlinear(int(model), int(num_undamped_iters), int(min_linear_iters), 0, float(beta), dptr(z), dptr(s))
         check(self._lib.gbp_lin_set_nonlinear(self._h, ct.byref(d)))
-        self._nonlinear = True
+        self._nonlinear, self._model = True, int(model)
 
     def extend_se2(self, var_a, var_b, measurement, sqrt_info, prior_eta=None, prior_lam=None):
         """Append dN poses (their priors: ids N .. N + dN - 1; put the odometry prediction there) and dF relative-pose factors (ids
@@ -281,12 +305,23 @@ class LinearEngine:
         adjacent belief means as they are after the belief update of the grown graph (a new pose's belief is its prior), with zero
         messages, iters_since_relin 1 and damping 0 (compute_factor gbp.py:267-294, 248-249).  solve_map / marginals results are dropped
         until the next solve.  `extend` stays refused on such an engine: it takes eta_f, Lambda_f, which the engine owns."""
+        self._extend_nonlinear(_capi.LIN_MODEL_SE2_BETWEEN, var_a, var_b, measurement, sqrt_info, prior_eta, prior_lam)
+
+    def extend_se3(self, var_a, var_b, measurement, sqrt_info, prior_eta=None, prior_lam=None):
+        """extend_se2 for an engine of se3_pose_graph: measurement and sqrt_info are dF x 6, the priors dN x 6 and dN x 6 x 6; the
+        domain rule of se3_pose_graph holds for the new measurements too."""
+        self._extend_nonlinear(_capi.LIN_MODEL_SE3_BETWEEN, var_a, var_b, measurement, sqrt_info, prior_eta, prior_lam)
+
+    def _extend_nonlinear(self, model, var_a, var_b, measurement, sqrt_info, prior_eta, prior_lam):
+        if self._nonlinear and self._model != model:
+            raise ValueError("extend_se2 is for an engine of se2_pose_graph, extend_se3 for one of se3_pose_graph")
+        M = _capi.LIN_MODEL_DOFS[model]
         var_a, var_b = i32(var_a).reshape(-1), i32(var_b).reshape(-1)
         dF = var_a.shape[0]
         if var_b.shape[0] != dF:
             raise ValueError("var_a / var_b length mismatch")
-        z = f64(np.asarray(measurement, dtype=np.float64).reshape(dF, 3))
-        s = f64(np.ascontiguousarray(np.broadcast_to(np.asarray(sqrt_info, dtype=np.float64), (dF, 3))))
+        z = f64(np.asarray(measurement, dtype=np.float64).reshape(dF, M))
+        s = f64(np.ascontiguousarray(np.broadcast_to(np.asarray(sqrt_info, dtype=np.float64), (dF, M))))
         dN, pe, pl = _new_priors(prior_eta, prior_lam, self.D)
         d = _capi.LinExtNonlinear(dN, dF, iptr(var_a), iptr(var_b), dptr(z), dptr(s), dptr(pe), dptr(pl))
         check(self._lib.gbp_lin_extend_nonlinear(self._h, ct.byref(d)))
@@ -299,8 +334,9 @@ class LinearEngine:
         return n.value
 
     def linearisation(self):
-        """(linpoint (F, 6) = [xa; xb], iters_since_relin (F,) int32, eta_damping (F,)) of every factor (gbp.py:231, 248-249)."""
-        lp, it, dm = np.zeros((max(self.F, 1), 6)), np.zeros(max(self.F, 1), dtype=np.int32), np.zeros(max(self.F, 1))
+        """(linpoint (F, 2 D) = [xa; xb] -- (F, 6), on an engine of se3_pose_graph (F, 12) --, iters_since_relin (F,) int32,
+        eta_damping (F,)) of every factor (gbp.py:231, 248-249)."""
+        lp, it, dm = np.zeros((max(self.F, 1), 2 * self.D)), np.zeros(max(self.F, 1), dtype=np.int32), np.zeros(max(self.F, 1))
         check(self._lib.gbp_lin_get_linearisation(self._h, dptr(lp), iptr(it), dptr(dm)))
         return lp[:self.F], it[:self.F], dm[:self.F]
 

@@ -265,7 +265,11 @@ int  gbp_lin_get_alloc_count(gbp_lin_t *h, int32_t *count);
 /* ---- nonlinear pairwise factors, relinearised on the device: FactorGraph(nonlinear_factors=True) (gbp.py:30-34) with relinearise_factors
  * (gbp.py:64-80), the per-factor damping that a relinearisation switches off and num_undamped_iters sweeps later restores (gbp.py:46-54),
  * and Factor.compute_factor at a moving linearisation point (gbp.py:267-294) -- without a host round trip per sweep ----
- * One factor family so far, GBP_LIN_MODEL_SE2_BETWEEN: the planar relative-pose ("between") factor on variables x = (tx, ty, theta),
+ * Two factor families, both relative-pose ("between") factors; a model has D dofs per variable and M rows per measurement, and every
+ * array below is as wide as the handle's model says: measurement and sqrt_info F x M, linpoint F x 2D.
+ *   GBP_LIN_MODEL_SE2_BETWEEN   D = M = 3   planar poses (tx, ty, theta)
+ *   GBP_LIN_MODEL_SE3_BETWEEN   D = M = 6   spatial poses (t, w), w a rotation vector               (further below)
+ * GBP_LIN_MODEL_SE2_BETWEEN: the planar relative-pose factor on variables x = (tx, ty, theta),
  * d = 3.  A factor joins a and b and has a measurement z in R^3 and positive square-root information s in R^3, one per component (the
  * reference knows a scalar noise std only: this is its arithmetic with std 1 and a whitened meas_fn / jac_fn).  With c = cos theta_a,
  * s_ = sin theta_a, dx = xb - xa, dy = yb - ya:
@@ -277,10 +281,26 @@ int  gbp_lin_get_alloc_count(gbp_lin_t *h, int32_t *count);
  * ANGLES ARE NOT WRAPPED anywhere -- not in h, not in the distance of the relinearisation test, not in the beliefs -- because the
  * reference does not wrap: the caller keeps theta continuous along the trajectory (a pose 1.5 turns on has theta = 3 pi + ...).
  *
+ * GBP_LIN_MODEL_SE3_BETWEEN: a variable is x = (t, w) in R^6, translation then rotation vector, R = Exp(w) by Rodrigues; GBP adds and
+ * subtracts variables as plain vectors, as the reference does everywhere.  A factor joins a and b and has a measurement z = (z_t, z_w)
+ * in R^6 -- the pose of b in the frame of a, the relative rotation as a rotation vector -- and positive square-root information s in
+ * R^6.  With u = R_a^T (t_b - t_a), E = R_a^T R_b and phi = Log(E), the principal value:
+ *   h(xa, xb) = diag(s) [ u ; phi ]
+ *   J = diag(s) [ -R_a^T   [u]x Jr(w_a)               R_a^T   0                   ]
+ *               [  0       -Jr^-1(phi) E^T Jr(w_a)    0       Jr^-1(phi) Jr(w_b)  ]
+ *   Jr(w)      = I - (1 - cos th)/th^2 [w]x + (th - sin th)/th^3 [w]x^2                              (th = |w|; series near 0)
+ *   Jr^-1(phi) = I + 1/2 [phi]x + (1/th^2 - (1 + cos th)/(2 th sin th)) [phi]x^2                     (th = |phi|; series near 0)
+ *   Lambda_f = J^T J,  eta_f = J^T (J x0 + diag(s) z - h(x0))                                        (gbp.py:280-289, noise variance 1)
+ * THE DOMAIN, as SE(2)'s "angles are never wrapped": w IS NEVER WRAPPED, and the caller keeps it continuous along the trajectory;
+ * |w| > pi is legal.  Relative rotations -- Log(R_a^T R_b) at every point a factor is evaluated at -- and z_w stay below pi in norm.
+ * Jr(w) loses rank at |w| = 2 pi k, k >= 1: a pose there has a direction of w that turns nothing.
+ *
  * gbp_lin_set_nonlinear (Factor(meas_fn=, jac_fn=) gbp.py:207-208, 237-239; compute_all_factors gbp.py:60-62, 273-276; the per-factor
- * state gbp.py:248-249): legal on a handle with dofs == 3, without losses set, and not already nonlinear; GBP_EINVAL for a NULL
- * descriptor or array (with F > 0), an unknown model, dofs != 3, a negative num_undamped_iters / min_linear_iters, beta negative or NaN
- * (+inf is legal: never relinearise), a sqrt_info that is not positive and finite or a measurement that is not finite; GBP_ESTATE with
+ * state gbp.py:248-249): legal on a handle whose dofs are the model's D (3 for GBP_LIN_MODEL_SE2_BETWEEN, 6 for
+ * GBP_LIN_MODEL_SE3_BETWEEN), without losses set, and not already nonlinear; GBP_EINVAL for a NULL
+ * descriptor or array (with F > 0), an unknown model, dofs other than the model's, a negative num_undamped_iters / min_linear_iters, beta negative or NaN
+ * (+inf is legal: never relinearise), a sqrt_info that is not positive and finite, a measurement that is not finite or (SE(3)) a
+ * measured rotation vector z_w whose norm is not below pi; GBP_ESTATE with
  * losses set or on a handle that is already nonlinear; all decided before anything changes.  The eta_f, Lambda_f given at create are
  * ignored and overwritten, factor_const is not used.  If the handle has no beliefs the belief stage runs first (belief = prior); then
  * every factor is computed at linpoint = its adjacent belief means, iters_since_relin = 1 and the per-factor damping = 0.  Messages are
@@ -301,7 +321,7 @@ int  gbp_lin_get_alloc_count(gbp_lin_t *h, int32_t *count);
  * seen, like the trace buffer of gbp_lin_iterate_until.  n_iters < 0: GBP_EINVAL.
  * gbp_lin_relinearise: relinearise_factors (gbp.py:64-80) alone -- the test, the re-made factors, iters; not the damping switch, which
  * belongs to compute_all_messages.  n_relinearised may be NULL.
- * gbp_lin_get_linearisation: Factor.linpoint (gbp.py:231, F x 6 = [xa; xb]), Factor.iters_since_relin and Factor.eta_damping
+ * gbp_lin_get_linearisation: Factor.linpoint (gbp.py:231, F x 2D = [xa; xb]: F x 6, SE(3) F x 12), Factor.iters_since_relin and Factor.eta_damping
  * (gbp.py:248-249); any of the three may be NULL.
  * On a handle that is not nonlinear the three return GBP_ESTATE.
  *
@@ -318,21 +338,22 @@ int  gbp_lin_get_alloc_count(gbp_lin_t *h, int32_t *count);
  *                            belief means: such a handle has its losses from gbp_lin_set_robust_nonlinear, further below.)
  * No floating-point atomics: two identical call sequences on two handles are bit-identical, counts included. */
 #define GBP_LIN_MODEL_SE2_BETWEEN 1
+#define GBP_LIN_MODEL_SE3_BETWEEN 2
 typedef struct {
     int32_t model;                      /* GBP_LIN_MODEL_*                                                     */
     int32_t num_undamped_iters;         /* FactorGraph.num_undamped_iters gbp.py:33, >= 0                      */
     int32_t min_linear_iters;           /* FactorGraph.min_linear_iters gbp.py:34, >= 0                        */
     int32_t reserved;
     double beta;                        /* FactorGraph.beta gbp.py:32, >= 0; +inf = never relinearise          */
-    const double *measurement;          /* F x 3   Factor.measurement gbp.py:233 (not whitened)                */
-    const double *sqrt_info;            /* F x 3, positive and finite                                          */
+    const double *measurement;          /* F x M   Factor.measurement gbp.py:233 (not whitened); M = 3 or 6    */
+    const double *sqrt_info;            /* F x M, positive and finite                                          */
 } gbp_lin_nonlinear_desc_t;
 int  gbp_lin_set_nonlinear(gbp_lin_t *h, const gbp_lin_nonlinear_desc_t *d);    /* compute_all_factors gbp.py:60-62 */
 int  gbp_lin_relinearise(gbp_lin_t *h, int32_t *n_relinearised /* or NULL */);  /* relinearise_factors gbp.py:64-80 */
 int  gbp_lin_iterate_nonlinear(gbp_lin_t *h, int32_t n_iters, int32_t *relin_counts /* host, n_iters, or NULL */);   /* n x synchronous_iteration(local_relin=True) gbp.py:86-92 */
-int  gbp_lin_get_linearisation(gbp_lin_t *h, double *linpoint /* F x 6 */, int32_t *iters_since_relin /* F */, double *eta_damping /* F */);   /* Factor.linpoint gbp.py:231, iters_since_relin / eta_damping gbp.py:248-249; any may be NULL */
+int  gbp_lin_get_linearisation(gbp_lin_t *h, double *linpoint /* F x 2D */, int32_t *iters_since_relin /* F */, double *eta_damping /* F */);   /* Factor.linpoint gbp.py:231, iters_since_relin / eta_damping gbp.py:248-249; any may be NULL */
 
-/* ---- growing and shrinking a live NONLINEAR handle: a fixed-lag smoother for SE(2) pose graphs ----
+/* ---- growing and shrinking a live NONLINEAR handle: a fixed-lag smoother for SE(2) and SE(3) pose graphs ----
  * Both calls return GBP_ESTATE on a handle without nonlinear factors, validate completely before anything changes, leave the handle
  * bit-identical on any failure before the commit (GBP_EINVAL, GBP_ENOMEM), drop the solver workspaces and mark the joint stale as
  * gbp_lin_extend / gbp_lin_shrink do, and leave the handle holding ONE generation of arrays: gbp_lin_get_alloc_count does not grow
@@ -343,7 +364,7 @@ int  gbp_lin_get_linearisation(gbp_lin_t *h, double *linpoint /* F x 6 */, int32
  *
  * gbp_lin_extend_nonlinear: var_nodes.append / factors.append / adj_factors.append, update_all_beliefs() (gbp.py:56-58), then
  * compute_factor() on the NEW factors only (gbp.py:267-294).  Ids, adjacency order and the index and size rules are those of
- * gbp_lin_extend; measurements must be finite and sqrt_info positive and finite, as for gbp_lin_set_nonlinear.  A new factor is
+ * gbp_lin_extend; measurements must be finite and sqrt_info positive and finite (SE(3): |z_w| < pi), as for gbp_lin_set_nonlinear.  A new factor is
  * linearised at its two adjacent belief means as they are AFTER the belief update -- a new variable's belief is its prior, so the
  * caller puts the odometry prediction there -- and starts with zero messages, iters_since_relin = 1 and damping 0 (gbp.py:222,
  * 248-249).  Every old factor keeps eta_f, Lambda_f, linpoint, iters_since_relin, damping and both messages bit for bit, and every old
@@ -360,9 +381,9 @@ int  gbp_lin_get_linearisation(gbp_lin_t *h, double *linpoint /* F x 6 */, int32
 typedef struct {
     int32_t n_new_vars, n_new_factors;      /* dN, dF >= 0                                                          */
     const int32_t *var_a, *var_b;           /* dF: ids in [0, N + dN), a != b; old-old, old-new and new-new allowed */
-    const double *measurement;              /* dF x 3, finite (not whitened)                                        */
-    const double *sqrt_info;                /* dF x 3, positive and finite                                          */
-    const double *prior_eta, *prior_lam;    /* dN x 3, dN x 3 x 3                                                   */
+    const double *measurement;              /* dF x M, finite (not whitened); the handle's model: M = 3 or 6        */
+    const double *sqrt_info;                /* dF x M, positive and finite                                          */
+    const double *prior_eta, *prior_lam;    /* dN x D, dN x D x D                                                   */
 } gbp_lin_extend_nonlinear_desc_t;
 int  gbp_lin_extend_nonlinear(gbp_lin_t *h, const gbp_lin_extend_nonlinear_desc_t *d);   /* appends + gbp.py:56-58 + compute_factor gbp.py:267-294 on the new factors */
 int  gbp_lin_shrink_nonlinear(gbp_lin_t *h, const gbp_lin_shrink_desc_t *d);

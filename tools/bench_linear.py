@@ -50,6 +50,10 @@ ap.add_argument('--nonlinear-until', action='store_true',
                 help='ms per sweep of iterate_until_nonlinear (plain, with the energy column, with both columns) against iterate_nonlinear and the host '
                      'loop iterate(1, relinearise=True); energy(), at beta = +inf and beta = 0; with --parent-lib the older sweeps against the parent '
                      "commit's library; writes profiles/linear_nonlinear_until.json")
+ap.add_argument('--nonlinear-se3', action='store_true',
+                help='ms per sweep of the SE(3) relinearising sweeps (beta = +inf, beta = 0, robust) against the plain d = 6 gbp_lin_iterate on the same '
+                     'handle, on a 100k x 6 ring (k = 5) and a 500k-pose chain (k = 1) re-posed as SE(3), and the SE(2) nonlinear sweep against '
+                     '--parent-lib; writes profiles/linear_nonlinear_se3.json')
 ap.add_argument('--parent-lib', default=None, help="--nonlinear-live / --nonlinear-robust / --nonlinear-until: the parent commit's libgbp_hip.so, loaded beside this one for the yardsticks")
 ap.add_argument('--parent-results', default=None,
                 help="--extend / --shrink / --until / --nonlinear: a file of lines 'parent {json}' / 'here {json}', each the JSON line of a plain run of this tool from the parent "
@@ -909,6 +913,140 @@ def nonlinear_until_profile():
     print(json.dumps(out))
 
 
+def se3_graph(N, k, rs):
+    """N poses on a circle of radius N / 20, the rotation vector angle * (1, 2, 2) / 3 with the angle rising to 4.5 rad (past pi) half way
+    round and falling back, so that it is continuous and every relative rotation small; each pose joined to its next k neighbours;
+    sqrt information (10, 10, 10, 20, 20, 20), noise to match; priors sigma (1, 1, 1, 0.5, 0.5, 0.5) at truth + N(0, (0.1 x 3, 0.03 x 3))."""
+    th = np.arange(N) * 2 * np.pi / N
+    R = N / 20.0
+    axis = np.array([1.0, 2.0, 2.0]) / 3.0
+    ang = 4.5 * (1.0 - np.abs(2.0 * np.arange(N) / N - 1.0))
+    truth = np.concatenate([np.stack([R * np.cos(th), R * np.sin(th), 0.3 * np.sin(2 * th)], 1), ang[:, None] * axis], 1)
+    va = np.repeat(np.arange(N), k)
+    vb = (va + np.tile(np.arange(1, k + 1), N)) % N
+
+    def rot(w):                                             # Rodrigues, |w| > 0 or the identity
+        t = np.linalg.norm(w, axis=1)
+        u = w / np.where(t > 0, t, 1.0)[:, None]
+        K = np.zeros((w.shape[0], 3, 3))
+        K[:, 0, 1], K[:, 0, 2], K[:, 1, 0], K[:, 1, 2], K[:, 2, 0], K[:, 2, 1] = -u[:, 2], u[:, 1], u[:, 2], -u[:, 0], -u[:, 1], u[:, 0]
+        return np.eye(3)[None] + np.sin(t)[:, None, None] * K + (1 - np.cos(t))[:, None, None] * (K @ K)
+    Ra, Rb = rot(truth[va, 3:]), rot(truth[vb, 3:])
+    E = np.swapaxes(Ra, 1, 2) @ Rb
+    v = 0.5 * np.stack([E[:, 2, 1] - E[:, 1, 2], E[:, 0, 2] - E[:, 2, 0], E[:, 1, 0] - E[:, 0, 1]], 1)
+    nv = np.linalg.norm(v, axis=1)
+    phi = (np.arctan2(nv, 0.5 * (np.trace(E, axis1=1, axis2=2) - 1.0)) / np.where(nv > 0, nv, 1.0))[:, None] * v
+    s = np.tile(np.array([10.0, 10.0, 10.0, 20.0, 20.0, 20.0]), (va.shape[0], 1))
+    z = np.concatenate([np.einsum('fji,fj->fi', Ra, truth[vb, :3] - truth[va, :3]), phi], 1) + rs.normal(0, 1, s.shape) / s
+    pl = np.ascontiguousarray(np.broadcast_to(np.diag([1.0, 1.0, 1.0, 4.0, 4.0, 4.0]), (N, 6, 6)))
+    pe = np.einsum('nij,nj->ni', pl, truth + rs.normal(0, 1, (N, 6)) * np.array([0.1, 0.1, 0.1, 0.03, 0.03, 0.03]))
+    return va.astype(np.int32), vb.astype(np.int32), z, s, pe, pl
+
+
+def nonlinear_se3_profile():
+    """Host clock around whole calls, each ending in a stream synchronise, after a warm-up of every form; --repeats alternating rounds of
+    --steps sweeps, medians reported per sweep, spread = (max - min) / median.  On a 100k-pose ring with k = 5 (500k factors) and a
+    500k-pose chain with k = 1, d = 6, re-posed as SE(3) (se3_graph).  One handle with beta = +inf: `plain` (gbp_lin_iterate) against
+    `relin_none` (gbp_lin_iterate_nonlinear, the relinearise stage runs and relinearises nothing); on the same handle with the Huber
+    loss on every factor, `robust` (gbp_lin_iterate_nonlinear_robust, beta = +inf still, after `plain_weighted`, gbp_lin_iterate with the
+    losses set, was timed).  A second handle with beta = 0 and min_linear_iters = 0: `relin_all`, every factor re-made in every sweep,
+    against ITS plain sweep (`plain_b0`).  Counted beside each ratio, in doubles per factor on top of the plain d = 6 sweep's count: at
+    beta = +inf the stage gathers two means (12), reads the linpoint (12) and iters (0.5), writes iters (0.5), and the factor stage reads
+    the factor's damping (1): 26, plus one kernel boundary priced at 3.2 us; beta = 0 adds the measurement and square-root information
+    read (12) and eta_f, Lambda_f and the linpoint written (12 + 78 + 12): 114 more; the robust lane adds z and s (12), loss, threshold,
+    weight written and read, flag (4): 16.  The counts are of algorithmic bytes, not of what the caches fetch; the beta = 0 lane also does
+    the arithmetic of the model (two Rodrigues, a Log, five 3 x 3 products, 78 entries of Lambda_f), which a count of doubles does not
+    see: an excess of a measured ratio over its count is UNEXPLAINED here -- no counters were collected, and no split of the relinearise
+    kernel's time into arithmetic and traffic was measured.  With --parent-lib: the SE(2) sweeps (gbp_lin_iterate_nonlinear at
+    beta = +inf and gbp_lin_iterate on the 200k x 3 ring, k = 5) of this library against the parent commit's, alternating in one session,
+    once with either library's handle created first."""
+    import ctypes as ct
+    from gbp_amd import _capi
+    D, runs, boundary_ms = 6, [], 3.2e-3
+    n = a.steps
+    for N, k in ((100_000, 5), (500_000, 1)):
+        va, vb, z, s, pe, pl = se3_graph(N, k, np.random.RandomState(0))
+        F = va.shape[0]
+        e = LinearEngine.se3_pose_graph(va, vb, z, s, pe, pl, float('inf'), 4, 2, eta_damping=0.4)
+        e0 = LinearEngine.se3_pose_graph(va, vb, z, s, pe, pl, 0.0, 4, 0, eta_damping=0.4)
+
+        def timed(fn, h):
+            t = time.perf_counter(); fn(); h.sync()
+            return 1e3 * (time.perf_counter() - t) / n
+        forms = {'plain': lambda: timed(lambda: e.iterate(n), e),
+                 'relin_none': lambda: timed(lambda: e._lib.gbp_lin_iterate_nonlinear(e._h, n, None), e),
+                 'plain_b0': lambda: timed(lambda: e0.iterate(n), e0),
+                 'relin_all': lambda: timed(lambda: e0._lib.gbp_lin_iterate_nonlinear(e0._h, n, None), e0)}
+        e.iterate(a.warmup); e.sync()
+        rec = {key: [] for key in list(forms) + ['plain_weighted', 'robust']}
+        for fn in forms.values():
+            fn()
+        for _ in range(a.repeats):                          # alternating
+            for key, fn in forms.items():
+                rec[key].append(fn())
+        counts = e0.iterate(2, relinearise=True)
+        energy = {"beta_inf": e.energy(), "beta_0": e0.energy()}
+        e.set_robust('huber', 4.0)
+        rforms = {'plain_weighted': lambda: timed(lambda: e.iterate(n), e),
+                  'robust': lambda: timed(lambda: e._lib.gbp_lin_iterate_nonlinear_robust(e._h, n, None, None), e)}
+        for fn in rforms.values():
+            fn()
+        for _ in range(a.repeats):
+            for key, fn in rforms.items():
+                rec[key].append(fn())
+        flagged = int(e.weights()[1].sum())
+        med = {key: statistics.median(v) for key, v in rec.items()}
+        spread = {key: (max(v) - min(v)) / med[key] for key, v in rec.items()}
+        per_f = sweep_doubles(D, 1.0 / k, False)
+        runs.append({"vars": N, "dofs": D, "k": k, "factors": F, "ms_per_sweep": med, "spread": spread, "ms_all": rec,
+                     "ratio_relin_none_over_plain": med['relin_none'] / med['plain'], "ratio_none_counted": (per_f + 26) / per_f + boundary_ms / med['plain'],
+                     "ratio_relin_all_over_plain": med['relin_all'] / med['plain_b0'], "ratio_all_counted": (per_f + 26 + 114) / per_f + boundary_ms / med['plain_b0'],
+                     "ratio_robust_over_plain": med['robust'] / med['plain'], "ratio_robust_counted": (per_f + 26 + 16) / per_f + boundary_ms / med['plain'],
+                     "ratio_robust_over_plain_weighted": med['robust'] / med['plain_weighted'],
+                     "doubles_per_factor_plain": per_f, "kernel_boundary_ms_assumed": boundary_ms, "counters_collected": False,
+                     "relinearised_in_two_more_beta_0_sweeps": counts.tolist(), "flagged_at_the_end": flagged, "energy_after": energy})
+        e.close(); e0.close()
+    vs_parent = None
+    if a.parent_lib:
+        here, parent = _capi.load(), ct.CDLL(os.path.abspath(a.parent_lib))
+        va, vb, z, s, pe, pl = se2_graph(200_000, 5, np.random.RandomState(0))
+        vs_parent = {}
+        for order in ('parent_created_first', 'here_created_first'):
+            first, second = (parent, here) if order == 'parent_created_first' else (here, parent)
+            h1 = RawSE2(first, va, vb, z, s, pe, pl, float('inf'), 2)
+            h2 = RawSE2(second, va, vb, z, s, pe, pl, float('inf'), 2)
+            hp, hh = (h1, h2) if order == 'parent_created_first' else (h2, h1)
+            for call in ('gbp_lin_iterate_nonlinear', 'gbp_lin_iterate'):
+                def sweeps(h):
+                    t = time.perf_counter()
+                    rc = h.lib.gbp_lin_iterate_nonlinear(h.h, ct.c_int32(n), None) if call == 'gbp_lin_iterate_nonlinear' else h.lib.gbp_lin_iterate(h.h, ct.c_int32(n))
+                    assert rc == 0 and h.lib.gbp_lin_sync(h.h) == 0
+                    return n / (time.perf_counter() - t)
+                sweeps(hp); sweeps(hh)
+                tp, th = [], []
+                for _ in range(a.repeats):
+                    tp.append(sweeps(hp)); th.append(sweeps(hh))
+                mp, mh = statistics.median(tp), statistics.median(th)
+                sp, sh = (max(tp) - min(tp)) / mp, (max(th) - min(th)) / mh
+                vs_parent[call + '_' + order] = {"sweeps_per_s_parent": mp, "sweeps_per_s_here": mh, "ratio_here_over_parent": mh / mp, "spread_parent": sp,
+                                                 "spread_here": sh, "margin": max(sp, sh), "beyond_margin": abs(mh / mp - 1.0) > max(sp, sh),
+                                                 "all_parent": tp, "all_here": th}
+            hp.close(); hh.close()
+    out = {"what": "tools/bench_linear.py --nonlinear-se3 on one MI355X: ms per sweep of the SE(3) relinearising sweeps against the plain d = 6 gbp_lin_iterate on "
+                   "the same handle, on a 100k x 6 ring (k = 5) and a 500k-pose chain (k = 1) re-posed as SE(3); and the SE(2) sweeps against the parent "
+                   "commit's library on the 200k x 3 ring (k = 5)",
+           "method": " ".join(nonlinear_se3_profile.__doc__.split()), "repeats": a.repeats, "sweep_steps": a.steps, "runs": runs,
+           "se2_sweeps_per_s_vs_parent": vs_parent}
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'profiles', 'linear_nonlinear_se3.json')
+    with open(path, 'w') as fh:
+        json.dump(out, fh, indent=1)
+        fh.write('\n')
+    print(json.dumps(out))
+
+
+if a.nonlinear_se3:
+    nonlinear_se3_profile()
+    sys.exit(0)
 if a.nonlinear_until:
     nonlinear_until_profile()
     sys.exit(0)
