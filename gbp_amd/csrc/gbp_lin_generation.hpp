@@ -154,6 +154,13 @@ inline void lin_drop_solvers(gbp_lin *h)
         m.x = m.r = m.z = m.p = m.q = m.ebuf = m.pq_part = m.rz_part = m.rr_part = nullptr;
         h->marg_ready = false;
     }
+    if (h->gn.alloc) {                                      // gbp_lin_solve_map_nonlinear's arrays: the next call re-makes them
+        const LinGn &g = h->gn;
+        for (const void *q : {(const void *)g.feta, (const void *)g.flam, (const void *)g.prior, (const void *)g.x, (const void *)g.e_part, (const void *)g.v_part,
+                              (const void *)g.out})
+            lin_free(h, q);
+        h->gn = LinGn{};
+    }
     // gbp_lin_iterate_until's partials are one per block of the belief and energy stages; its stop word and trace buffer stay
     lin_free(h, h->until.bel_part); lin_free(h, h->until.en_part);
     h->until.bel_part = h->until.en_part = nullptr;

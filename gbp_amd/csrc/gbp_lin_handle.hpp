@@ -16,6 +16,9 @@
 //   gbp_lin_capi_nonlin.hip  nonlinear pairwise factors relinearised on the device (kernels in gbp_lin_nonlin.hpp): the relinearise stage,
 //                            the factor stage with per-factor damping (parameter block LinRelin below), the model-aware energy; growing and
 //                            shrinking such a handle are gbp_lin_extend_nonlinear / gbp_lin_shrink_nonlinear in the extend / shrink units
+//   gbp_lin_capi_map_nonlin.hip  the nonlinear batch MAP of such a handle by Levenberg-Marquardt: linearisation at a point of the solver's
+//                            own, damped priors and the step test (kernels in gbp_lin_gn.hpp) around the conjugate gradients of
+//                            gbp_lin_capi_map.hip, which run on a LinParams copy pointing at the solver's arrays
 //   gbp_lin_capi_nonlin_robust.hip  robust losses on such a handle: the weight made at the linearisation point by the relinearise lane
 //                            (k_lin_relin<MODEL, true>), and the factor stage with weight and per-factor damping together
 #pragma once
@@ -90,6 +93,19 @@ struct LinUntil {
     double *trace;                   // [cap][3]: row i = (step, energy, MAP distance) after sweep i + 1 of the call in progress
     int cap;                         // rows of `trace`: the largest max_iters seen
     int *stop;                       // [2]: GBP_LIN_STOP_* (0: go on), and the sweep that decided
+};
+
+// Workspace of gbp_lin_solve_map_nonlinear (gbp_lin_gn.hpp): device memory owned by gbp_lin::allocs, allocated by the first call, sized
+// by N and F and dropped with a generation (lin_drop_solvers).  The inner solves run in LinMap's workspace; LinMap::x is the candidate.
+struct LinGn {
+    double *feta, *flam;             // [2D][F], [P2][F]: the linearisation at x -- the solver's, never the handle's
+    double *prior;                   // [N][D + P]: the damped copy of the priors
+    double *x;                       // [N][D]: the current point
+    double *e_part;                  // [2][nen]: per-block partials of the factor energy at x, and at the candidate
+    double *v_part;                  // [2][nb]: per-block partials of the prior difference, and of max |x_c - x|
+    double *out;                     // [GN_OUT]: what the host downloads per step
+    int nen, nb;
+    bool alloc;
 };
 
 // Nonlinear factors (gbp_lin_nonlin.hpp): device memory owned by gbp_lin::allocs, allocated by gbp_lin_set_nonlinear.  Everything
@@ -167,6 +183,7 @@ struct gbp_lin {
     LinUntil until{};                // gbp_lin_capi_until.hip
     LinNonlin nl{};                  // gbp_lin_capi_nonlin.hip
     bool nonlinear = false;          // gbp_lin_set_nonlinear was called: (eta_f, Lambda_f) are those of nl.linpoint
+    LinGn gn{};                      // gbp_lin_capi_map_nonlin.hip
 };
 
 #define LHIPCHK(expr)                                                                                       \
@@ -185,6 +202,15 @@ struct gbp_lin {
 
 namespace gbp {
 int lin_map_prepare(gbp_lin *h);                    // gbp_lin_capi_map.hip: LinMap's workspace (once per handle), LDL^T and joint eta (per set of weights)
+// gbp_lin_capi_map.hip, the host side of the conjugate gradients over ANY joint: `p` names the factors, priors and weights (the handle's
+// own LinParams, or a copy pointing elsewhere), `m` the workspace.  None of them reads or writes map_ready / map_solved / map_eta_norm.
+int lin_map_workspace(gbp_lin *h);                  // LinMap's workspace, once per generation
+int lin_map_setup(gbp_lin *h, const LinParams &p, const LinMap &m, double *eta_norm);   // LDL^T of the diagonal blocks, joint eta, |eta|
+int lin_map_matvec(gbp_lin *h, const LinParams &p, const LinMap &m, const double *src, double *dst);   // dst = Lambda_joint src; partials of src . dst in pq_part
+int lin_map_restart(gbp_lin *h, const LinParams &p, const LinMap &m, int use_q, int next_it, double *rnorm);   // r = eta - q (or eta), z, p = z; *rnorm = |r|
+enum { LIN_MAP_FROM_ZERO = 0, LIN_MAP_FROM_MEANS = 1, LIN_MAP_FROM_X = 2 };   // x0 of lin_map_solve: 0, the belief means, what m.x holds
+int lin_map_solve(gbp_lin *h, const LinParams &p, const LinMap &m, double eta_norm, const gbp_lin_map_opts_t &o, int start, gbp_lin_map_info_t *info,
+                  double *rnorm0 /* |eta - Lambda x0|, or NULL */);
 int lin_sweep(gbp_lin *h);                          // gbp_lin_capi.hip: one synchronous iteration at the weights as they stand, queued on the stream
 int lin_nonlin_energy(gbp_lin *h, double *out);     // gbp_lin_capi_nonlin.hip: red_blocks partials (one per block of 256 factors, 0 past F) into `out` = d_red, queued on the stream
 int lin_nonlin_linearise(gbp_lin *h, int f0, int f1);   // gbp_lin_capi_nonlin.hip: compute_factor on the factors [f0, f1) at their belief means, queued

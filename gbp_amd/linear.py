@@ -80,6 +80,26 @@ class UntilResult:
         return f"UntilResult(iters={self.iters}, converged={self.converged}, reason={self.reason})"
 
 
+class NonlinearMapResult:
+    """What LinearEngine.solve_map_nonlinear returns: outer (LM iterations run = accepted + rejected), cg_iters (summed over the inner
+    solves), converged, reason (_capi.LIN_NLMAP_STEP / GRAD / STALL, or NONE when max_outer ran out), energy0 / energy (the factor
+    energy at x0 and at the final x), grad_norm, lambda_ (what the next iteration would use), and one value per iteration run: energy_trace
+    (at x before the step), lambdas, steps (max |dx|), dphi, taken (bool).  The final x: LinearEngine.map_mean()."""
+    __slots__ = ('outer', 'accepted', 'rejected', 'cg_iters', 'converged', 'reason', 'energy0', 'energy', 'grad_norm', 'lambda_',
+                 'energy_trace', 'lambdas', 'steps', 'dphi', 'taken')
+
+    def __init__(self, info, trace):
+        for k in ('outer', 'accepted', 'rejected', 'cg_iters', 'reason', 'energy0', 'energy', 'grad_norm', 'lambda_'):
+            setattr(self, k, getattr(info, k))
+        self.converged = bool(info.converged)
+        rows = trace[:info.outer]
+        self.energy_trace, self.lambdas, self.steps, self.dphi = (rows[:, k].copy() for k in range(4))
+        self.taken = rows[:, 4] != 0.0
+
+    def __repr__(self):
+        return f"NonlinearMapResult(outer={self.outer}, accepted={self.accepted}, converged={self.converged}, reason={self.reason}, energy={self.energy:.6g})"
+
+
 class LinearEngine:
     def __init__(self, var_a, var_b, factor_eta, factor_lam, prior_eta, prior_lam, factor_const=None, eta_damping=0.0, device=0):
         self._lib = _capi.load()
@@ -456,6 +476,24 @@ class LinearEngine:
         i = _capi.LinMapInfo()
         check(self._lib.gbp_lin_solve_map(self._h, ct.byref(o), ct.byref(i)))
         return self.map_mean(), {'iters': i.iters, 'converged': bool(i.converged), 'rel_residual': i.rel_residual, 'eta_norm': i.eta_norm}
+
+    def solve_map_nonlinear(self, max_outer=50, init='means', lambda0=1e-4, lambda_up=10.0, lambda_down=0.1, lambda_min=1e-12, lambda_max=1e8,
+                            tol_step=1e-10, tol_grad=1e-8, rel_tol=1e-12, max_iters=10000, check_every=8):
+        """The nonlinear batch MAP of an engine of se2_pose_graph / se3_pose_graph by Levenberg-Marquardt on the device
+        (gbp_lin_solve_map_nonlinear): the minimiser of sum_f w_f 0.5 |h_f(x) - diag(s_f) z_f|^2 + the priors, at the weights as
+        they stand, started at the belief means (init='means') or at the iterate of the last solve_map() / solve_map_nonlinear()
+        (init='map').  rel_tol, max_iters, check_every are those of the inner conjugate-gradient solves.  The sweep's state is left
+        bit for bit as it was; the result lands where solve_map() leaves its own, so map_mean(), map_distance() and
+        iterate_until_nonlinear(map_distance=True) then measure against the nonlinear MAP.  Returns a NonlinearMapResult."""
+        if init not in ('means', 'map'):
+            raise ValueError("init is 'means' or 'map'")
+        o = _capi.LinNlmapOpts(int(max_outer), _capi.LIN_NLMAP_FROM_MAP if init == 'map' else _capi.LIN_NLMAP_FROM_MEANS, float(lambda0), float(lambda_up),
+                               float(lambda_down), float(lambda_min), float(lambda_max), float(tol_step), float(tol_grad),
+                               _capi.LinMapOpts(float(rel_tol), int(max_iters), int(check_every), 0))
+        i = _capi.LinNlmapInfo()
+        trace = np.full((max(int(max_outer), 1), 5), np.nan)
+        check(self._lib.gbp_lin_solve_map_nonlinear(self._h, ct.byref(o), dptr(trace), ct.byref(i)))
+        return NonlinearMapResult(i, trace)
 
     def map_mean(self):
         mu = np.empty((self.N, self.D))

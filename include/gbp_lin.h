@@ -479,6 +479,80 @@ int  gbp_lin_iterate_until_nonlinear(gbp_lin_t *h, const gbp_lin_until_opts_t *o
                                      int32_t *robust_counts /* host, max_iters, or NULL; must be NULL when opts->robustify == 0 */,
                                      gbp_lin_until_info_t *info /* or NULL */);
 
+/* ---- the NONLINEAR batch MAP on the device, by Levenberg-Marquardt: what ndim_posegraph.py:94,108 measures linear GBP against
+ * (joint_distribution_cov's mu, gbp.py:128-144), for FactorGraph(nonlinear_factors=True) -- the minimiser of the nonlinear least-squares
+ * problem itself, not one Gauss-Newton step at wherever the sweeps' linearisation stands ----
+ * On a nonlinear handle (SE(2) or SE(3)) the call minimises
+ *   Phi(x) = sum_f w_f 0.5 |h_f(x) - diag(s_f) z_f|^2 + sum_v (0.5 x_v^T Lambda0_v x_v - eta0_v^T x_v)
+ * over x in R^(N D): the first sum is what gbp_lin_energy reports (factors only, w_f = 1 without losses), the second the priors, the
+ * folded priors of gbp_lin_shrink_nonlinear included.  THE WEIGHTS ARE FIXED during the call, at what they are when it is made:
+ * iteratively reweighted solves are out of scope (call gbp_lin_robustify_nonlinear and solve again).
+ * It neither reads nor writes the sweep's state, except for the belief means when they are the starting point: messages, beliefs,
+ * means, the handle's eta_f / Lambda_f, linpoint, iters_since_relin, per-factor damping, weights, flags and both count buffers are bit
+ * for bit what they were, whatever the call returns.
+ *
+ * One outer iteration at (x, lambda):
+ *   1. every factor is linearised at x, into arrays of the solver's own, by the lane code of the relinearise stage; the same pass
+ *      leaves the factor energy E(x);
+ *   2. a damped copy of the priors: Lambda0_v + lambda diag(D_v), eta0_v + lambda diag(D_v) x_v, D_v the joint's diagonal block at x
+ *      (at the weights as they stand), each diagonal entry floored at 1e-12 (GN_DIAG_FLOOR);
+ *   3. the conjugate gradients of gbp_lin_solve_map (options `cg`) on that joint, started at x: the first true residual is
+ *      eta - Lambda x = -grad Phi(x); grad_norm is its 2-norm, and tol_grad is tested there, before any CG iteration, at every x that
+ *      is new (x0 and after every accepted step).  It is formed from the DAMPED system, (eta + lambda D x) - (Lambda + lambda D) x:
+ *      the lambda D x terms cancel exactly only in exact arithmetic and leave a rounding of about 1e-16 lambda max(D |x|) in
+ *      grad_norm -- with an anchor prior of 1e6 and, after a run of rejections, lambda >= 1, that is 1e-10 |x| or more, comparable with
+ *      a tol_grad of 1e-8; at the lambda of accepted steps (<= 1e-3 by default) it is below the rounding of eta - Lambda x itself;
+ *   4. the candidate x_c is judged by dPhi = [E(x_c) - E(x)] + sum_v (x_c - x)_v^T (Lambda0_v (x_c + x)_v / 2 - eta0_v), the prior
+ *      part in difference form (no cancellation far from the origin), every sum in a fixed order;
+ *   5. the host decides: max |x_c - x| <= tol_step (tol_step > 0): stop, reason STEP, converged, x_c taken only if dPhi <= 0;
+ *      else dPhi < 0: accepted, x = x_c, lambda = max(lambda lambda_down, lambda_min); anything else -- a NaN included, which is what
+ *      an SE(3) candidate whose relative rotation leaves the domain gives -- rejected: x stays, and if the lambda just used is above
+ *      lambda_max the call ends with reason STALL, converged 0, GBP_OK, else lambda = lambda lambda_up.  A rejected step relinearises
+ *      nothing.  max_outer running out: reason NONE, converged 0, GBP_OK.
+ * trace row i (written for i < info->outer): E(x) before the step, the lambda used, max |x_c - x|, dPhi, taken (1 / 0).
+ * info: outer = accepted + rejected = rows written; cg_iters summed over the inner solves; energy0 / energy = E at x0 and at the final
+ * x (comparable with gbp_lin_energy when the means equal x); grad_norm at the last new x it was formed at; lambda: what the next
+ * iteration would use.
+ * NULL opts = { max_outer 50, init FROM_MEANS, lambda0 1e-4, lambda_up 10, lambda_down 0.1, lambda_min 1e-12, lambda_max 1e8,
+ *               tol_step 1e-10, tol_grad 1e-8, cg {1e-12, 10000, 8, 0} }.
+ * WHAT tol_grad CAN REACH: the decrease test compares values of Phi, and E(x) is known to about 1e-16 E.  A step from a point with
+ * gradient g lowers Phi by about g^2 / (2 curvature); once that is below the rounding of E -- g below about sqrt(2e-16 E curvature),
+ * e.g. 5e-6 at E = 130 and curvatures of 400 -- steps are rejected on noise and the call ends in STEP (tol_step on) or STALL.  The
+ * default tol_grad of 1e-8 is therefore reached only by problems whose energy at the optimum is of order 1e-3 or less; on the others
+ * the defaults end in STEP, which is the expected way for them to end.  Ask for a tol_grad above that floor to end in GRAD.
+ * The final x lands where gbp_lin_solve_map leaves its iterate: gbp_lin_get_map, gbp_lin_map_distance and GBP_LIN_TRACE_MAP of
+ * gbp_lin_iterate_until_nonlinear then measure against the nonlinear MAP.  The inner solves use that solver's workspace and leave its
+ * LDL^T and joint eta stale: the next gbp_lin_solve_map re-makes them in place, as after a change of weights.  The solver's own arrays
+ * (linearisation, damped priors, x, partials) are allocated on first use, dropped by gbp_lin_extend_nonlinear /
+ * gbp_lin_shrink_nonlinear with the other solver workspaces and re-made by the next call; a repeated call of the same size allocates
+ * nothing (gbp_lin_get_alloc_count).  No floating-point atomics: two identical call sequences on two handles give bit-identical x, info
+ * and trace.
+ * Refusals, all before anything changes: a handle that is not nonlinear, init FROM_MEANS without beliefs, init FROM_MAP without a
+ * solve: GBP_ESTATE.  max_outer < 0, an unknown init, a lambda that is not positive and finite, lambda_up <= 1, lambda_down >= 1,
+ * lambda_min <= lambda0 <= lambda_max violated, a tolerance negative or not finite, the cg rules of gbp_lin_solve_map, cg.warm_start
+ * != 0: GBP_EINVAL.
+ * max_outer == 0: x = x0, energy0 = energy = E(x0).  Without factors Phi is the priors' quadratic: ONE step with lambda = 0 (so the
+ * trace row says) reaches its minimiser and the call ends converged, reason GRAD.  Without variables: GBP_OK, converged, reason GRAD. */
+#define GBP_LIN_NLMAP_FROM_MEANS 0   /* x0 = the belief means                               */
+#define GBP_LIN_NLMAP_FROM_MAP   1   /* x0 = the iterate gbp_lin_get_map would return       */
+#define GBP_LIN_NLMAP_NONE  0        /* max_outer ran out                                    */
+#define GBP_LIN_NLMAP_STEP  1
+#define GBP_LIN_NLMAP_GRAD  2
+#define GBP_LIN_NLMAP_STALL 3
+typedef struct {
+    int32_t max_outer;        /* >= 0 LM iterations (accepted + rejected)                         */
+    int32_t init;             /* GBP_LIN_NLMAP_FROM_MEANS 0: x0 = belief means (GBP_ESTATE without beliefs);
+                                 GBP_LIN_NLMAP_FROM_MAP   1: x0 = the iterate gbp_lin_get_map would return (GBP_ESTATE without one) */
+    double lambda0, lambda_up, lambda_down, lambda_min, lambda_max;   /* > 0, up > 1, 0 < down < 1, min <= lambda0 <= max */
+    double tol_step;          /* > 0: stop after a step with max |dx| <= tol_step; 0: off        */
+    double tol_grad;          /* > 0: stop when |eta - Lambda x|_2 at x <= tol_grad; 0: off      */
+    gbp_lin_map_opts_t cg;    /* the inner solves; warm_start must be 0 (CG always starts at x)   */
+} gbp_lin_nlmap_opts_t;
+typedef struct { int32_t outer, accepted, rejected, cg_iters, converged, reason;   /* NONE / STEP / GRAD / STALL */
+                 double energy0, energy, grad_norm, lambda; } gbp_lin_nlmap_info_t;
+int gbp_lin_solve_map_nonlinear(gbp_lin_t *h, const gbp_lin_nlmap_opts_t *opts,
+                                double *trace /* host, max_outer x 5, or NULL */, gbp_lin_nlmap_info_t *info /* or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,10 @@ ap.add_argument('--nonlinear-se3', action='store_true',
                 help='ms per sweep of the SE(3) relinearising sweeps (beta = +inf, beta = 0, robust) against the plain d = 6 gbp_lin_iterate on the same '
                      'handle, on a 100k x 6 ring (k = 5) and a 500k-pose chain (k = 1) re-posed as SE(3), and the SE(2) nonlinear sweep against '
                      '--parent-lib; writes profiles/linear_nonlinear_se3.json')
+ap.add_argument('--nonlinear-map', action='store_true',
+                help='time per outer iteration of gbp_lin_solve_map_nonlinear (Levenberg-Marquardt on the device) on the SE(3) ring and chain, beside its counted '
+                     'bytes and its two nearest existing pieces: the relinearise kernel of an all-relinearising sweep and a gbp_lin_solve_map of the same CG '
+                     'iteration count; writes profiles/linear_nonlinear_map.json')
 ap.add_argument('--parent-lib', default=None, help="--nonlinear-live / --nonlinear-robust / --nonlinear-until: the parent commit's libgbp_hip.so, loaded beside this one for the yardsticks")
 ap.add_argument('--parent-results', default=None,
                 help="--extend / --shrink / --until / --nonlinear: a file of lines 'parent {json}' / 'here {json}', each the JSON line of a plain run of this tool from the parent "
@@ -583,14 +587,15 @@ def nonlinear_profile():
 class RawSE2:
     """gbp_lin_create + gbp_lin_set_nonlinear through the C ABI of ANY build of the library (this one or --parent-lib)."""
 
-    def __init__(self, lib, va, vb, z, s, pe, pl, beta, minlin):
+    def __init__(self, lib, va, vb, z, s, pe, pl, beta, minlin, model=1):
         import ctypes as ct
         from gbp_amd import _capi
         self.lib, self.ct = lib, ct
         F, N = va.shape[0], pe.shape[0]
-        fe, fl = np.zeros((F, 6)), np.zeros((F, 6, 6))
+        D = 3 if model == 1 else 6                           # GBP_LIN_MODEL_SE2_BETWEEN / _SE3_BETWEEN
+        fe, fl = np.zeros((F, 2 * D)), np.zeros((F, 2 * D, 2 * D))
         d = _capi.LinDesc()
-        d.n_vars, d.dofs, d.n_factors, d.device = N, 3, F, 0
+        d.n_vars, d.dofs, d.n_factors, d.device = N, D, F, 0
         d.var_a, d.var_b = _capi.iptr(va), _capi.iptr(vb)
         d.factor_eta, d.factor_lam, d.factor_const = _capi.dptr(fe), _capi.dptr(fl), None
         d.prior_eta, d.prior_lam, d.eta_damping = _capi.dptr(pe), _capi.dptr(pl), 0.4
@@ -599,7 +604,7 @@ class RawSE2:
             getattr(lib, name).restype = ct.c_int
         lib.gbp_lin_destroy.restype = None
         assert lib.gbp_lin_create(ct.byref(self.h), ct.byref(d)) == 0
-        nd = _capi.LinNonlinear(1, 4, int(minlin), 0, float(beta), _capi.dptr(z), _capi.dptr(s))
+        nd = _capi.LinNonlinear(int(model), 4, int(minlin), 0, float(beta), _capi.dptr(z), _capi.dptr(s))
         assert lib.gbp_lin_set_nonlinear(self.h, ct.byref(nd)) == 0
         assert lib.gbp_lin_sync(self.h) == 0
 
@@ -1044,6 +1049,142 @@ def nonlinear_se3_profile():
     print(json.dumps(out))
 
 
+def nonlinear_map_profile():
+    """Host clock around whole calls, each ending in a stream synchronise, after a warm-up of every form; --repeats alternating rounds,
+    medians reported, spread = (max - min) / median.  On the 100k-pose SE(3) ring with k = 5 (500k factors) and the 500k-pose chain with
+    k = 1 (se3_graph).  `lm_per_outer`: gbp_lin_solve_map_nonlinear from the belief means with max_outer = 4, tolerances off, lambda0 =
+    1e-3, inner solves of at most --steps CG iterations (rel_tol 1e-30, so every inner solve runs exactly that many, after the product
+    of its start and before the product of its true residual): ms = call / outer.  Its two nearest existing pieces run on a handle of
+    the PARENT commit's library (--parent-lib, required; loaded beside this one) with beta = 0 and min_linear_iters = 0, in the same
+    alternating rounds: `relin_all`, gbp_lin_relinearise after a sweep has moved the means (the relinearise kernel of an all-
+    relinearising sweep, alone: its count is checked to be F), and `solve_map`, gbp_lin_solve_map with the same max_iters and rel_tol and
+    warm_start = 1 -- started at the means, so that it too forms the product of its start, as every inner solve of `lm` does.  Counted
+    per outer iteration, in doubles, on top of that solve's own count: the linearise lane gathers x (12), reads z and s (12) and writes
+    eta_f, Lambda_f (12 + 78) per factor (the parent's relinearise lane moves 12 + 12 + 12 + 90 + 12 + 2: counted with relin_all, so the
+    two nearly cancel); the damping lane reads the prior (27), the factors' diagonal (6 per edge, 2 edges per factor), x (6) and writes
+    the damped prior (27) per variable; the set-up of the diagonal blocks is run per outer iteration (27 + 6 per variable read, the 42-
+    entry factor blocks per edge, 27 + 6 written), where solve_map's is made once and is outside its timed call; the energy-only lane
+    reads 24 per factor; the difference lane 27 + 12 per variable; three copies of x (12 per variable each).  An excess of `lm` over
+    relin_all + solve_map beyond that count is UNEXPLAINED here: no counters were collected.
+    The existing paths against the parent, both libraries in one session, alternating, once with either library's handle created first
+    (balanced = the geometric mean of the two orders): gbp_lin_iterate_nonlinear (beta = +inf) and gbp_lin_iterate on the 200k x 3 SE(2)
+    ring (k = 5), --steps sweeps per call; and gbp_lin_solve_map (cold, max_iters = --steps, rel_tol 1e-30) on the same handles, whose
+    host path this commit rewrote."""
+    import ctypes as ct
+    from gbp_amd import _capi
+    if not a.parent_lib:
+        raise SystemExit("--nonlinear-map needs --parent-lib: its yardsticks are measured on the parent commit's library")
+    here, parent = _capi.load(), ct.CDLL(os.path.abspath(a.parent_lib))
+    for lib in (here, parent):
+        for name in ('gbp_lin_relinearise', 'gbp_lin_solve_map', 'gbp_lin_iterate', 'gbp_lin_iterate_nonlinear', 'gbp_lin_sync'):
+            getattr(lib, name).restype = ct.c_int
+    D, runs = 6, []
+
+    def raw_solve(h, warm):
+        o, i = _capi.LinMapOpts(1e-30, int(a.steps), 8, int(warm)), _capi.LinMapInfo()
+        t = time.perf_counter()
+        assert h.lib.gbp_lin_solve_map(h.h, ct.byref(o), ct.byref(i)) == 0     # ends in a stream synchronise
+        return 1e3 * (time.perf_counter() - t), i.iters
+
+    for N, k in ((100_000, 5), (500_000, 1)):
+        va, vb, z, s, pe, pl = se3_graph(N, k, np.random.RandomState(0))
+        F = va.shape[0]
+        e = LinearEngine.se3_pose_graph(va, vb, z, s, pe, pl, float('inf'), 4, 2, eta_damping=0.4)
+        hp = RawSE2(parent, va, vb, z, s, pe, pl, 0.0, 0, model=2)
+        assert hp.lib.gbp_lin_iterate_nonlinear(hp.h, ct.c_int32(2), None) == 0 and hp.lib.gbp_lin_sync(hp.h) == 0
+        outer = 4
+        res = {}
+
+        def lm():
+            t = time.perf_counter()
+            r = e.solve_map_nonlinear(max_outer=outer, tol_step=0.0, tol_grad=0.0, lambda0=1e-3, rel_tol=1e-30, max_iters=a.steps)
+            res['r'] = r
+            return 1e3 * (time.perf_counter() - t) / max(r.outer, 1)
+
+        def relin_all():
+            assert hp.lib.gbp_lin_iterate(hp.h, ct.c_int32(1)) == 0 and hp.lib.gbp_lin_sync(hp.h) == 0   # moves the means: untimed
+            n = ct.c_int32()
+            t = time.perf_counter()
+            assert hp.lib.gbp_lin_relinearise(hp.h, ct.byref(n)) == 0           # downloads its count: ends in a stream synchronise
+            dt = 1e3 * (time.perf_counter() - t)
+            res['relin'] = n.value
+            return dt
+
+        def solve_map():
+            hp_solve = raw_solve(hp, 1)
+            res['cg'] = hp_solve[1]
+            return hp_solve[0]
+        raw_solve(hp, 1)                                    # makes the parent handle's workspace and diagonal blocks, outside the timing
+        forms = {'lm_per_outer': lm, 'relin_all': relin_all, 'solve_map': solve_map}
+        rec = {key: [] for key in forms}
+        for fn in forms.values():
+            fn()
+        for _ in range(a.repeats):                          # alternating
+            for key, fn in forms.items():
+                rec[key].append(fn())
+        assert res['relin'] == F, res
+        med = {key: statistics.median(v) for key, v in rec.items()}
+        spread = {key: (max(v) - min(v)) / med[key] for key, v in rec.items()}
+        r = res['r']
+        extra_doubles = F * (12 + 12 + 90 + 24 + 12 + 2 * 42) + N * (27 + 6 + 27 + 33 + 33 + 27 + 12 + 36)
+        parent_relin_doubles = F * (12 + 12 + 12 + 90 + 12 + 2)
+        counted = 8 * (extra_doubles - parent_relin_doubles)
+        runs.append({"vars": N, "dofs": D, "k": k, "factors": F, "ms": med, "spread": spread, "ms_all": rec, "yardsticks_on": "the parent commit's library",
+                     "outer": r.outer, "accepted": r.accepted, "rejected": r.rejected, "cg_iters_per_outer": r.cg_iters / max(r.outer, 1),
+                     "solve_map_cg_iters": res['cg'], "solve_map_warm_start": True, "relinearised": res['relin'],
+                     "energy0": r.energy0, "energy": r.energy, "sum_of_pieces_ms": med['relin_all'] + med['solve_map'],
+                     "lm_over_sum_of_pieces": med['lm_per_outer'] / (med['relin_all'] + med['solve_map']),
+                     "counted_bytes_per_outer_beyond_the_pieces": counted, "counted_ms_at_8TBps": counted / 8e12 * 1e3,
+                     "excess_over_pieces_ms": med['lm_per_outer'] - med['relin_all'] - med['solve_map'],
+                     "excess_is": "measured; whatever of it exceeds the counted bytes is unexplained: no counters collected", "counters_collected": False})
+        e.close(); hp.close()
+
+    # the existing paths, this library against the parent's
+    n = a.steps
+    va, vb, z, s, pe, pl = se2_graph(200_000, 5, np.random.RandomState(0))
+    vs_parent = {}
+    for order in ('parent_created_first', 'here_created_first'):
+        first, second = (parent, here) if order == 'parent_created_first' else (here, parent)
+        h1 = RawSE2(first, va, vb, z, s, pe, pl, float('inf'), 2)
+        h2 = RawSE2(second, va, vb, z, s, pe, pl, float('inf'), 2)
+        hp, hh = (h1, h2) if order == 'parent_created_first' else (h2, h1)
+        for call in ('gbp_lin_iterate_nonlinear', 'gbp_lin_iterate', 'gbp_lin_solve_map'):
+            def run(h):
+                if call == 'gbp_lin_solve_map':
+                    ms, it = raw_solve(h, 0)
+                    assert it == n
+                    return n / (1e-3 * ms)                  # CG iterations per second
+                t = time.perf_counter()
+                rc = h.lib.gbp_lin_iterate_nonlinear(h.h, ct.c_int32(n), None) if call == 'gbp_lin_iterate_nonlinear' else h.lib.gbp_lin_iterate(h.h, ct.c_int32(n))
+                assert rc == 0 and h.lib.gbp_lin_sync(h.h) == 0
+                return n / (time.perf_counter() - t)
+            run(hp); run(hh)
+            tp, th = [], []
+            for _ in range(a.repeats):
+                tp.append(run(hp)); th.append(run(hh))
+            mp, mh = statistics.median(tp), statistics.median(th)
+            sp, sh = (max(tp) - min(tp)) / mp, (max(th) - min(th)) / mh
+            vs_parent[call + '_' + order] = {"per_s_parent": mp, "per_s_here": mh, "ratio_here_over_parent": mh / mp, "spread_parent": sp, "spread_here": sh,
+                                             "margin": max(sp, sh), "beyond_margin": abs(mh / mp - 1.0) > max(sp, sh), "all_parent": tp, "all_here": th}
+        hp.close(); hh.close()
+    for call in ('gbp_lin_iterate_nonlinear', 'gbp_lin_iterate', 'gbp_lin_solve_map'):
+        r1, r2 = (vs_parent[call + '_' + o]["ratio_here_over_parent"] for o in ('parent_created_first', 'here_created_first'))
+        vs_parent[call + '_balanced'] = (r1 * r2) ** 0.5
+    out = {"what": "tools/bench_linear.py --nonlinear-map on one MI355X: ms per outer Levenberg-Marquardt iteration of gbp_lin_solve_map_nonlinear on the 100k x 6 SE(3) "
+                   "ring (k = 5) and the 500k-pose chain (k = 1), beside the relinearise kernel of an all-relinearising sweep plus a warm-started gbp_lin_solve_map of "
+                   "the same CG iteration count, both on the parent commit's library; and the existing sweeps and gbp_lin_solve_map against the parent's",
+           "method": " ".join(nonlinear_map_profile.__doc__.split()), "repeats": a.repeats, "cg_iters_cap": a.steps, "runs": runs,
+           "existing_paths_vs_parent": vs_parent}
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'profiles', 'linear_nonlinear_map.json')
+    with open(path, 'w') as fh:
+        json.dump(out, fh, indent=1)
+        fh.write('\n')
+    print(json.dumps(out))
+
+
+if a.nonlinear_map:
+    nonlinear_map_profile()
+    sys.exit(0)
 if a.nonlinear_se3:
     nonlinear_se3_profile()
     sys.exit(0)
