@@ -183,6 +183,7 @@ SIGNATURES = {
     'gbp_lin_iterate_nonlinear_robust': (ct.c_int, [ct.c_void_p, ct.c_int32, _ip, _ip]),
     'gbp_lin_iterate_until_nonlinear': (ct.c_int, [ct.c_void_p, ct.c_void_p, _dp, _ip, _ip, ct.c_void_p]),
     'gbp_lin_solve_map_nonlinear': (ct.c_int, [ct.c_void_p, ct.c_void_p, _dp, ct.c_void_p]),
+    'gbp_lin_solve_map_nonlinear_robust': (ct.c_int, [ct.c_void_p, ct.c_void_p, _dp, _dp, _dp, _ip, ct.c_void_p]),
     'gbp_ba_get_lmk_order': (ct.c_int, [ct.c_void_p, _ip]),
     'gbp_ba_fused_max_cams': (ct.c_int, []),
     'gbp_ba_plan_info': (ct.c_int, [ct.c_void_p, _ip, ct.c_int32]),
@@ -263,6 +264,18 @@ class LinNlmapInfo(ct.Structure):
                 ('reason', ct.c_int32), ('energy0', ct.c_double), ('energy', ct.c_double), ('grad_norm', ct.c_double), ('lambda_', ct.c_double)]
 
 
+class LinIrlsOpts(ct.Structure):
+    """gbp_lin_irls_opts_t (include/gbp_lin.h)."""
+    _fields_ = [('max_rounds', ct.c_int32), ('reserved', ct.c_int32), ('tol_weight', ct.c_double), ('tol_move', ct.c_double), ('lm', LinNlmapOpts)]
+
+
+class LinIrlsInfo(ct.Structure):
+    """gbp_lin_irls_info_t (include/gbp_lin.h)."""
+    _fields_ = [('rounds', ct.c_int32), ('outer', ct.c_int32), ('accepted', ct.c_int32), ('rejected', ct.c_int32), ('cg_iters', ct.c_int32),
+                ('converged', ct.c_int32), ('reason', ct.c_int32), ('flagged', ct.c_int32), ('energy0', ct.c_double), ('energy', ct.c_double),
+                ('weight_change', ct.c_double), ('move', ct.c_double), ('grad_norm', ct.c_double)]
+
+
 LIN_MODEL_SE2_BETWEEN = 1                           # GBP_LIN_MODEL_* (include/gbp_lin.h)
 LIN_MODEL_SE3_BETWEEN = 2
 LIN_MODEL_DOFS = {LIN_MODEL_SE2_BETWEEN: 3, LIN_MODEL_SE3_BETWEEN: 6}   # dofs of a variable = rows of a measurement
@@ -272,6 +285,7 @@ LIN_STOP_NONE, LIN_STOP_STEP, LIN_STOP_MAP = 0, 1, 2   # GBP_LIN_STOP_*
 LIN_MARG_COLS = 8
 LIN_NLMAP_FROM_MEANS, LIN_NLMAP_FROM_MAP = 0, 1     # GBP_LIN_NLMAP_FROM_*: x0 of gbp_lin_solve_map_nonlinear
 LIN_NLMAP_NONE, LIN_NLMAP_STEP, LIN_NLMAP_GRAD, LIN_NLMAP_STALL = 0, 1, 2, 3   # GBP_LIN_NLMAP_*: why it ended
+LIN_IRLS_NONE, LIN_IRLS_WEIGHTS, LIN_IRLS_MOVE = 0, 1, 2   # GBP_LIN_IRLS_*: why gbp_lin_solve_map_nonlinear_robust ended
 LIN_LOSS = {None: 0, 'huber': 1, 'constant': 2}     # GBP_LIN_LOSS_* (include/gbp_lin.h)
 
 _lib = None

@@ -23,7 +23,7 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libgbp_hip.so')
 # one translation unit per part of the C ABI (gbp_handle.hpp says which), compiled side by side and linked into ONE library
 SOURCES = ['gbp_capi.hip', 'gbp_capi_build.hip', 'gbp_capi_sweep.hip', 'gbp_capi_shard.hip', 'gbp_capi_views.hip', 'gbp_capi_state.hip', 'gbp_capi_extend.hip', 'gbp_capi_window.hip', 'gbp_lin_capi.hip', 'gbp_lin_capi_map.hip', 'gbp_lin_capi_marg.hip', 'gbp_lin_capi_robust.hip',
-           'gbp_lin_capi_extend.hip', 'gbp_lin_capi_shrink.hip', 'gbp_lin_capi_until.hip', 'gbp_lin_capi_nonlin.hip', 'gbp_lin_capi_nonlin_robust.hip', 'gbp_lin_capi_until_nonlin.hip', 'gbp_lin_capi_map_nonlin.hip', 'gbp_sort.hip']
+           'gbp_lin_capi_extend.hip', 'gbp_lin_capi_shrink.hip', 'gbp_lin_capi_until.hip', 'gbp_lin_capi_nonlin.hip', 'gbp_lin_capi_nonlin_robust.hip', 'gbp_lin_capi_until_nonlin.hip', 'gbp_lin_capi_map_nonlin.hip', 'gbp_lin_capi_map_irls.hip', 'gbp_sort.hip']
 HEADERS = ['gbp_handle.hpp', 'gbp_graft.hpp', 'gbp_build.hpp', 'gbp_build_plan.hpp', 'gbp_prior_kernels.hpp', 'gbp_kernels.hpp', 'gbp_sweep_kernels.hpp', 'gbp_view_kernels.hpp', 'gbp_fused.hpp',
            'gbp_fused_plan.hpp', 'gbp_policy.hpp', 'gbp_math.hpp', 'gbp_balio.hpp', 'gbp_lin_handle.hpp', 'gbp_lin_generation.hpp', 'gbp_lin_map.hpp', 'gbp_lin_marg.hpp', 'gbp_lin_robust.hpp', 'gbp_lin_extend.hpp', 'gbp_lin_shrink.hpp', 'gbp_lin_sweep.hpp', 'gbp_lin_until.hpp', 'gbp_lin_nonlin.hpp', 'gbp_lin_gn.hpp', os.path.join('experimental', 'gbp_instrument.hpp'),
            os.path.join('..', '..', 'include', 'gbp_ba.h'), os.path.join('..', '..', 'include', 'gbp_lin.h')]

@@ -14,9 +14,11 @@
 
 using namespace gbp;
 
-namespace {
+// What gbp_lin_solve_map_nonlinear and gbp_lin_solve_map_nonlinear_robust (gbp_lin_capi_map_irls.hip) share, declared in gbp_lin_gn.hpp:
+// the options' defaults and rules, the workspace, the start and the Levenberg-Marquardt loop itself.
+namespace gbp {
 
-constexpr gbp_lin_nlmap_opts_t NLMAP_DEFAULTS{50, GBP_LIN_NLMAP_FROM_MEANS, 1e-4, 10.0, 0.1, 1e-12, 1e8, 1e-10, 1e-8, {1e-12, 10000, 8, 0}};
+gbp_lin_nlmap_opts_t gn_nlmap_defaults() { return {50, GBP_LIN_NLMAP_FROM_MEANS, 1e-4, 10.0, 0.1, 1e-12, 1e8, 1e-10, 1e-8, {1e-12, 10000, 8, 0}}; }
 
 int gn_check_opts(const gbp_lin_nlmap_opts_t &o)
 {
@@ -65,14 +67,18 @@ int gn_workspace(gbp_lin *h)
     return GBP_OK;
 }
 
+}  // namespace gbp
+
+namespace {
+
 // the factors at `x`: LIN: the linearisation into the solver's arrays and the energy partials of slot 0; else the energy partials of slot 1
 template <bool LIN>
-int gn_factors(gbp_lin *h, const double *x)
+int gn_factors(gbp_lin *h, const LinParams &p, const double *x)
 {
     const LinGn &g = h->gn;
-    if (!h->p.F) return GBP_OK;                             // the partials stay at the zeros of gn_workspace
+    if (!p.F) return GBP_OK;                             // the partials stay at the zeros of gn_workspace
     lin_model_dispatch(h->nl.model, [&](auto m) {
-        hipLaunchKernelGGL((k_gn_factor<decltype(m)::value, LIN>), dim3(g.nen), dim3(256), 0, h->stream, h->p, h->nl, x, g.feta, g.flam, g.e_part + (LIN ? 0 : g.nen));
+        hipLaunchKernelGGL((k_gn_factor<decltype(m)::value, LIN>), dim3(g.nen), dim3(256), 0, h->stream, p, h->nl, x, g.feta, g.flam, g.e_part + (LIN ? 0 : g.nen));
     });
     LHIPCHK(hipGetLastError());
     return GBP_OK;
@@ -91,54 +97,50 @@ int gn_read(gbp_lin *h, double (&out)[GN_OUT])
 
 }  // namespace
 
-extern "C" {
+namespace gbp {
 
-int gbp_lin_solve_map_nonlinear(gbp_lin_t *h, const gbp_lin_nlmap_opts_t *opts, double *trace, gbp_lin_nlmap_info_t *info)
+// x0 -> g.x.  From the means: gathered into m.x by the solver's own kernel.  The iterate of the last solve stays valid (map_solved)
+// until the first inner solve overwrites it; from then on it is invalid until the call has put its final x there.
+int gn_start(gbp_lin *h, int init)
 {
-    LENTER(h);
-    if (!h->nonlinear) return set_error(GBP_ESTATE, "the handle has no nonlinear factors: call gbp_lin_set_nonlinear first");
-    const gbp_lin_nlmap_opts_t o = opts ? *opts : NLMAP_DEFAULTS;
-    LCHK(gn_check_opts(o));
-    if (o.init == GBP_LIN_NLMAP_FROM_MEANS && !h->has_beliefs) return set_error(GBP_ESTATE, "init from the means needs beliefs");
-    if (o.init == GBP_LIN_NLMAP_FROM_MAP && !h->map_solved) return set_error(GBP_ESTATE, "init from the MAP iterate needs a solve: call gbp_lin_solve_map first");
-
-    gbp_lin_nlmap_info_t out{};
-    out.lambda = o.lambda0;
-    const int N = h->p.N, D = h->D;
-    const size_t bytes = (size_t)N * D * sizeof(double);
-    LCHK(lin_map_workspace(h));
-    LCHK(gn_workspace(h));
     const LinMap &m = h->map;
-    const LinGn &g = h->gn;
-    h->map_ready = false;                                   // the workspace is about to hold the LDL^T and eta of damped systems
-    if (!N) {                                               // nothing to solve: the gradient of the empty problem is 0
-        h->map_solved = true;
-        out.converged = 1; out.reason = GBP_LIN_NLMAP_GRAD;
-        if (info) *info = out;
-        return GBP_OK;
-    }
-    // x0 -> g.x.  From the means: gathered into m.x by the solver's own kernel.  The iterate of the last solve stays valid (map_solved)
-    // until the first inner solve overwrites it; from then on it is invalid until the call has put its final x there.
-    if (o.init == GBP_LIN_NLMAP_FROM_MEANS) {
-        lin_dispatch(D, [&](auto d) {
+    if (init == GBP_LIN_NLMAP_FROM_MEANS) {
+        lin_dispatch(h->D, [&](auto d) {
             hipLaunchKernelGGL((k_map_load_means<decltype(d)::value>), dim3(m.nb), dim3(MAP_BLOCK), 0, h->stream, h->p, m);
         });
         LHIPCHK(hipGetLastError());
     }
     h->map_solved = false;
-    LHIPCHK(hipMemcpyAsync(g.x, m.x, bytes, hipMemcpyDeviceToDevice, h->stream));
+    LHIPCHK(hipMemcpyAsync(h->gn.x, m.x, (size_t)h->p.N * h->D * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    return GBP_OK;
+}
 
-    LinParams pd = h->p;                                    // the joint the inner solves see: this linearisation, these priors, the weights as they stand
+// The Levenberg-Marquardt loop from LinGn::x, which it leaves at the final point.  `base`: the handle's LinParams with the weights the
+// loop minimises at (`w`: the handle's as they stand, or the robust solver's own).  `linearised`: the linearisation at x and the
+// partials of E(x) in slot 0 of e_part are already made (by k_gn_reweight) -- the first iteration then does not linearise again.
+// N > 0.  trace: max_outer x 5 or NULL.
+int gn_lm(gbp_lin *h, const LinParams &base, bool linearised, const gbp_lin_nlmap_opts_t &o, double *trace, gbp_lin_nlmap_info_t *info)
+{
+    gbp_lin_nlmap_info_t out{};
+    out.lambda = o.lambda0;
+    const int N = base.N, D = h->D;
+    const size_t bytes = (size_t)N * D * sizeof(double);
+    const LinMap &m = h->map;
+    const LinGn &g = h->gn;
+
+    LinParams pd = base;                                    // the joint the inner solves see: this linearisation, these priors, these weights
     pd.feta = g.feta; pd.flam = g.flam; pd.prior = g.prior;
-    LinParams pl = h->p;                                    // the damping lane: this linearisation, the handle's priors
+    LinParams pl = base;                                    // the damping lane: this linearisation, the handle's priors
     pl.feta = g.feta; pl.flam = g.flam;
 
     double res[GN_OUT];
     double lambda = o.lambda0, E = 0.0;
     bool fresh = true;                                      // x has moved since the last linearisation
-    const bool linear = h->p.F == 0;                        // no factors: Phi is the priors' quadratic, one undamped step is exact
+    bool made = linearised;                                 // ... which the caller made for the first x
+    const bool linear = base.F == 0;                        // no factors: Phi is the priors' quadratic, one undamped step is exact
     for (int it = 0; it < o.max_outer; ++it) {
-        if (fresh) LCHK(gn_factors<true>(h, g.x));
+        if (fresh && !made) LCHK(gn_factors<true>(h, base, g.x));
+        made = false;
         const double lam = linear ? 0.0 : lambda;
         lin_dispatch(D, [&](auto d) {
             hipLaunchKernelGGL((k_gn_damp<decltype(d)::value>), dim3(m.nb), dim3(MAP_BLOCK), 0, h->stream, pl, (const double *)g.x, lam, g.prior);
@@ -164,9 +166,9 @@ int gbp_lin_solve_map_nonlinear(gbp_lin_t *h, const gbp_lin_nlmap_opts_t *opts, 
         LCHK(lin_map_solve(h, pd, m, eta_norm, o.cg, LIN_MAP_FROM_X, &ci, &rn));
         if (fresh) out.grad_norm = rn;
         out.cg_iters += ci.iters;
-        LCHK(gn_factors<false>(h, m.x));
+        LCHK(gn_factors<false>(h, base, m.x));
         lin_dispatch(D, [&](auto d) {
-            hipLaunchKernelGGL((k_gn_diff<decltype(d)::value>), dim3(m.nb), dim3(MAP_BLOCK), 0, h->stream, h->p.prior, N, (const double *)g.x, (const double *)m.x, g.v_part, g.nb);
+            hipLaunchKernelGGL((k_gn_diff<decltype(d)::value>), dim3(m.nb), dim3(MAP_BLOCK), 0, h->stream, base.prior, N, (const double *)g.x, (const double *)m.x, g.v_part, g.nb);
         });
         LHIPCHK(hipGetLastError());
         LCHK(gn_read(h, res));
@@ -197,16 +199,45 @@ int gbp_lin_solve_map_nonlinear(gbp_lin_t *h, const gbp_lin_nlmap_opts_t *opts, 
         }
     }
     if (o.max_outer == 0) {                                 // no iteration ran: the energy at x0 still has to be made
-        LCHK(gn_factors<true>(h, g.x));
+        if (!linearised) LCHK(gn_factors<true>(h, base, g.x));
         LCHK(gn_read(h, res));
         E = res[0];
         out.energy0 = E;
     }
-    LHIPCHK(hipMemcpyAsync(m.x, g.x, bytes, hipMemcpyDeviceToDevice, h->stream));
-    LHIPCHK(hipStreamSynchronize(h->stream));
-    h->map_solved = true;
     out.energy = E; out.lambda = lambda;
     if (info) *info = out;
+    return GBP_OK;
+}
+
+}  // namespace gbp
+
+extern "C" {
+
+int gbp_lin_solve_map_nonlinear(gbp_lin_t *h, const gbp_lin_nlmap_opts_t *opts, double *trace, gbp_lin_nlmap_info_t *info)
+{
+    LENTER(h);
+    if (!h->nonlinear) return set_error(GBP_ESTATE, "the handle has no nonlinear factors: call gbp_lin_set_nonlinear first");
+    const gbp_lin_nlmap_opts_t o = opts ? *opts : gn_nlmap_defaults();
+    LCHK(gn_check_opts(o));
+    if (o.init == GBP_LIN_NLMAP_FROM_MEANS && !h->has_beliefs) return set_error(GBP_ESTATE, "init from the means needs beliefs");
+    if (o.init == GBP_LIN_NLMAP_FROM_MAP && !h->map_solved) return set_error(GBP_ESTATE, "init from the MAP iterate needs a solve: call gbp_lin_solve_map first");
+
+    LCHK(lin_map_workspace(h));
+    LCHK(gn_workspace(h));
+    h->map_ready = false;                                   // the workspace is about to hold the LDL^T and eta of damped systems
+    if (!h->p.N) {                                          // nothing to solve: the gradient of the empty problem is 0
+        gbp_lin_nlmap_info_t out{};
+        out.lambda = o.lambda0;
+        h->map_solved = true;
+        out.converged = 1; out.reason = GBP_LIN_NLMAP_GRAD;
+        if (info) *info = out;
+        return GBP_OK;
+    }
+    LCHK(gn_start(h, o.init));
+    LCHK(gn_lm(h, h->p, false, o, trace, info));            // at the weights as they stand
+    LHIPCHK(hipMemcpyAsync(h->map.x, h->gn.x, (size_t)h->p.N * h->D * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    LHIPCHK(hipStreamSynchronize(h->stream));
+    h->map_solved = true;
     return GBP_OK;
 }
 

@@ -157,8 +157,9 @@ inline void lin_drop_solvers(gbp_lin *h)
     if (h->gn.alloc) {                                      // gbp_lin_solve_map_nonlinear's arrays: the next call re-makes them
         const LinGn &g = h->gn;
         for (const void *q : {(const void *)g.feta, (const void *)g.flam, (const void *)g.prior, (const void *)g.x, (const void *)g.e_part, (const void *)g.v_part,
-                              (const void *)g.out})
-            lin_free(h, q);
+                              (const void *)g.out, (const void *)g.w, (const void *)g.flag, (const void *)g.xs, (const void *)g.w_part, (const void *)g.count,
+                              (const void *)g.rout})
+            lin_free(h, q);                                 // (the last six are null unless the robust solve ran)
         h->gn = LinGn{};
     }
     // gbp_lin_iterate_until's partials are one per block of the belief and energy stages; its stop word and trace buffer stay

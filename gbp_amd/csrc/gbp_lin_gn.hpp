@@ -16,6 +16,11 @@
 //                               max |x_c - x|; per-block partials;
 //   k_gn_finish                 ONE block: the partials added in a fixed order (strided per thread, then the tree of map_block_sum) into
 //                               four doubles, which is all the host downloads to decide.
+// gbp_lin_solve_map_nonlinear_robust (gbp_lin_capi_map_irls.hip) runs that loop (gn_lm) inside rounds of re-made weights:
+//   k_gn_reweight<MODEL>        one lane per factor: k_gn_factor<MODEL, true>'s linearisation and energy at x, and from the same M_f the
+//                               weight and flag of Factor.robustify_loss into the SOLVER's w / flag arrays; per-block partials of the
+//                               weighted energy and of max |w_new - w_old|, the flagged factors counted by one integer add per wave;
+//   k_gn_reweight_finish        ONE block: those partials, the count and the last round's max |x_end - x_start| into four doubles.
 // No floating-point atomics anywhere: two identical call sequences on two handles are bit-identical.
 // The per-factor and per-variable routines are host/device functions, so that the same code runs in plain loops on a CPU
 // (tests/hostmath/lin_gn_shim.hip); the kernels are thin wrappers.
@@ -27,8 +32,27 @@ namespace gbp {
 
 constexpr double GN_DIAG_FLOOR = 1e-12;                    // the least a diagonal entry of D_v counts for in the damping
 constexpr int GN_OUT = 4;                                  // what k_gn_finish leaves: E(x), E(x_c), the prior difference, max |x_c - x|
+constexpr int GN_RW_OUT = 4;                               // what k_gn_reweight_finish leaves: E_w(x), max |w_new - w_old|, flagged, max |x_end - x_start|
 
 // ---- per-factor / per-variable routines (host and device) --------------------------------------------------------------------------
+
+// eta_f and Lambda_f (packed upper) of factor f at the point pt = [x_a; x_b] into feta [2D][F] / flam [P2][F]: the entries and the stores
+// of the relinearise lane (lin_relin_one, gbp_lin_nonlin.hpp)
+template <int MODEL>
+GBP_HD void gn_linearise(const double (&pt)[2 * NonlinModel<MODEL>::D], const double (&z)[NonlinModel<MODEL>::M], const double (&s)[NonlinModel<MODEL>::M], int f, size_t F,
+                         double *feta, double *flam)
+{
+    if constexpr (NonlinModel<MODEL>::dense) {
+        double eta[6], lam[Sym<6>::size];
+        nonlin_factor<MODEL>(pt, z, s, eta, lam);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) feta[k * F + f] = eta[k];
+#pragma unroll
+        for (int k = 0; k < Sym<6>::size; ++k) flam[(size_t)k * F + f] = lam[k];
+    } else {
+        NonlinModel<MODEL>::factor_store(pt, z, s, feta + f, flam + f, F);
+    }
+}
 
 // Factor f at the point x [N][D]: with LIN, eta_f and Lambda_f (packed upper) at [x_a; x_b] into feta [2D][F] / flam [P2][F] -- the
 // entries and the stores of the relinearise lane (lin_relin_one, gbp_lin_nonlin.hpp) --; returns w_f 0.5 |h(x) - diag(s) z|^2.
@@ -43,21 +67,43 @@ GBP_HD double gn_factor_at(const LinParams &p, const LinNonlin &n, int f, const 
     for (int k = 0; k < D; ++k) { pt[k] = xa[k]; pt[D + k] = xb[k]; }
 #pragma unroll
     for (int k = 0; k < M; ++k) { z[k] = n.meas[k * F + f]; s[k] = n.sinfo[k * F + f]; }
-    if constexpr (LIN) {
-        if constexpr (NonlinModel<MODEL>::dense) {
-            double eta[6], lam[Sym<6>::size];
-            nonlin_factor<MODEL>(pt, z, s, eta, lam);
-#pragma unroll
-            for (int k = 0; k < 6; ++k) feta[k * F + f] = eta[k];
-#pragma unroll
-            for (int k = 0; k < Sym<6>::size; ++k) flam[(size_t)k * F + f] = lam[k];
-        } else {
-            NonlinModel<MODEL>::factor_store(pt, z, s, feta + f, flam + f, F);
-        }
-    }
+    if constexpr (LIN) gn_linearise<MODEL>(pt, z, s, f, F, feta, flam);
     double e = nonlin_energy<MODEL>(pt, z, s);
     if (p.w) e *= p.w[f];                                   // the weights as they stand (gbp.py:43)
     return e;
+}
+
+// The reweight lane of gbp_lin_solve_map_nonlinear_robust for factor f at the solver's x: x_a, x_b, z, s loaded once; h(x) evaluated ONCE
+// for M_f^2 = |diag(s) z - h(x)|^2, which gives the weight and the flag (lin_robust_weight at noise variance 1, Factor.robustify_loss
+// gbp.py:296-332 with the linpoint at x) and the weighted energy; w[f] and flag[f] stored -- arrays of the SOLVER's, never LinRobust's --;
+// then the linearisation at x with the stores of gn_factor_at<MODEL, true>.  loss == nullptr (no losses set) or a factor at NONE: weight
+// 1, flag 0, threshold not loaded.  Returns w_f 0.5 M_f^2; change = |w_f - the weight w[f] held| (0 when `first`: nothing is loaded),
+// flagged = the flag.
+template <int MODEL>
+GBP_HD double gn_reweight_at(const LinParams &p, const LinNonlin &n, const int *loss, const double *thr, int f, const double *x, bool first, double *feta, double *flam,
+                             double *w, int *flag, double &change, int &flagged)
+{
+    constexpr int D = NonlinModel<MODEL>::D, M = NonlinModel<MODEL>::M;
+    const size_t F = (size_t)p.F;
+    const double *xa = x + (size_t)p.va[f] * D, *xb = x + (size_t)p.vb[f] * D;
+    double pt[2 * D], z[M], s[M];
+#pragma unroll
+    for (int k = 0; k < D; ++k) { pt[k] = xa[k]; pt[D + k] = xb[k]; }
+#pragma unroll
+    for (int k = 0; k < M; ++k) { z[k] = n.meas[k * F + f]; s[k] = n.sinfo[k * F + f]; }
+    // the linearisation and then the energy, in the order and with the calls of gn_factor_at<MODEL, true>: the compiler fuses
+    // multiply-adds by context, and only the same context gives that kernel's bits (a handle without losses must reproduce
+    // gbp_lin_solve_map_nonlinear bit for bit)
+    gn_linearise<MODEL>(pt, z, s, f, F, feta, flam);
+    const double e = nonlin_energy<MODEL>(pt, z, s);       // 0.5 M^2: the one evaluation of h beside the linearisation's
+    const int ls = loss ? loss[f] : GBP_LIN_LOSS_NONE;
+    double wf = 1.0;
+    flagged = 0;
+    if (ls != GBP_LIN_LOSS_NONE) wf = lin_robust_weight(ls, thr[f], 1.0, e, flagged);
+    change = first ? 0.0 : fabs(wf - w[f]);
+    w[f] = wf;
+    flag[f] = flagged;
+    return e * wf;
 }
 
 // The damped prior of variable v: D_v's diagonal = prior Lambda_v's + the own diagonal entries of the factors of its adjacency run
@@ -176,5 +222,70 @@ __global__ __launch_bounds__(MAP_BLOCK) void k_gn_finish(const double *e_x, cons
         out[0] = ex; out[1] = ec; out[2] = dp; out[3] = mx;
     }
 }
+
+// The reweight lane over every factor: 256 lanes, one per factor; lanes past F neither load nor store.  Per block: the partial of the
+// weighted energy (the sum of k_gn_factor, so that a round's first E(x) is the one that kernel would have left) and of
+// max_f |w_new - w_old| (NaN-propagating like k_gn_diff's maximum); the flagged factors of a wave are counted by one ballot, one
+// popcount and ONE integer atomic add, as k_lin_relin counts.
+template <int MODEL>
+__global__ __launch_bounds__(256) void k_gn_reweight(LinParams p, LinNonlin n, const int *loss, const double *thr, const double *x, int first, double *feta, double *flam,
+                                                     double *w, int *flag, double *e_part, double *w_part, int *count)
+{
+    __shared__ double red[256 / 64];
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    double e = 0.0, mx = 0.0;
+    int fl = 0;
+    if (f < p.F) e = gn_reweight_at<MODEL>(p, n, loss, thr, f, x, first != 0, feta, flam, w, flag, mx, fl);
+    const unsigned long long who = __ballot(fl != 0);
+    if ((threadIdx.x & 63) == 0 && who) atomicAdd(count, __popcll(who));
+    e = map_block_sum(e, red);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_down(mx, off, 64); mx = (o > mx || o != o) ? o : mx; }
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < 256 / 64; ++k) mx = (red[k] > mx || red[k] != red[k]) ? red[k] : mx;
+        e_part[blockIdx.x] = e;
+        w_part[blockIdx.x] = mx;
+    }
+}
+
+// k_gn_finish's sibling for a reweight, ONE block of MAP_BLOCK threads, in a fixed order:
+// out = (sum e_x[0 .. nen), max w_part[0 .. nen), the flagged count, max part[nb .. 2 nb) = the last round's max |x_end - x_start|)
+template <int OUT>
+__global__ __launch_bounds__(MAP_BLOCK) void k_gn_reweight_finish(const double *e_x, const double *w_part, int nen, const int *count, const double *part, int nb, double *out)
+{
+    __shared__ double red[MAP_BLOCK / 64];
+    const double ex = map_sum_partials(e_x, nen, red);
+    double r[2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const double *src = q ? part + nb : w_part;
+        const int cnt = q ? nb : nen;
+        double mx = 0.0;
+        for (int i = threadIdx.x; i < cnt; i += MAP_BLOCK) { const double o = src[i]; mx = (o > mx || o != o) ? o : mx; }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_down(mx, off, 64); mx = (o > mx || o != o) ? o : mx; }
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+        __syncthreads();
+        for (int k = 1; k < MAP_BLOCK / 64; ++k) mx = (red[k] > mx || red[k] != red[k]) ? red[k] : mx;   // thread 0's is the block's
+        r[q] = mx;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        static_assert(OUT == 4, "the weighted energy, max |w_new - w_old|, the flagged count, max |x_end - x_start|");
+        out[0] = ex; out[1] = r[0]; out[2] = (double)count[0]; out[3] = r[1];
+    }
+}
+
+// ---- the host side both entry points share (defined in gbp_lin_capi_map_nonlin.hip) --------------------------------------------------
+
+gbp_lin_nlmap_opts_t gn_nlmap_defaults();                  // what NULL opts of gbp_lin_solve_map_nonlinear mean
+int gn_check_opts(const gbp_lin_nlmap_opts_t &o);          // every GBP_EINVAL rule of gbp_lin_nlmap_opts_t
+int gn_workspace(gbp_lin *h);                              // LinGn's arrays of the Levenberg-Marquardt loop, once per generation, all or nothing
+int gn_start(gbp_lin *h, int init);                        // x0 (GBP_LIN_NLMAP_FROM_*) -> LinGn::x; map_solved cleared
+// the loop itself, from LinGn::x: `base` names the weights (LinParams::w), `linearised` says that the linearisation and the energy
+// partials at x are already made
+int gn_lm(gbp_lin *h, const LinParams &base, bool linearised, const gbp_lin_nlmap_opts_t &o, double *trace, gbp_lin_nlmap_info_t *info);
 
 }  // namespace gbp

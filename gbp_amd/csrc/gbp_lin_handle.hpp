@@ -19,6 +19,9 @@
 //   gbp_lin_capi_map_nonlin.hip  the nonlinear batch MAP of such a handle by Levenberg-Marquardt: linearisation at a point of the solver's
 //                            own, damped priors and the step test (kernels in gbp_lin_gn.hpp) around the conjugate gradients of
 //                            gbp_lin_capi_map.hip, which run on a LinParams copy pointing at the solver's arrays
+//   gbp_lin_capi_map_irls.hip  the robust nonlinear batch MAP: that Levenberg-Marquardt loop (gn_lm, one function for both entry points)
+//                            inside rounds of re-made weights -- a reweight lane at the solver's own x (k_gn_reweight, gbp_lin_gn.hpp)
+//                            into weights of the solver's own, which the round's LinParams::w points at
 //   gbp_lin_capi_nonlin_robust.hip  robust losses on such a handle: the weight made at the linearisation point by the relinearise lane
 //                            (k_lin_relin<MODEL, true>), and the factor stage with weight and per-factor damping together
 #pragma once
@@ -106,6 +109,14 @@ struct LinGn {
     double *out;                     // [GN_OUT]: what the host downloads per step
     int nen, nb;
     bool alloc;
+    // gbp_lin_solve_map_nonlinear_robust (gbp_lin_capi_map_irls.hip) adds its own, all or nothing on ITS first call (`irls`):
+    double *w;                       // [F]: the solver's weights, made at x -- never LinRobust::w
+    int *flag;                       // [F]: M_f(x) > t_f
+    double *xs;                      // [N][D]: x at the start of the round
+    double *w_part;                  // [nen]: per-block partials of max |w_new - w_old|
+    int *count;                      // [1]: the flagged factors of the last reweight
+    double *rout;                    // [GN_RW_OUT]: what the host downloads per reweight
+    bool irls;
 };
 
 // Nonlinear factors (gbp_lin_nonlin.hpp): device memory owned by gbp_lin::allocs, allocated by gbp_lin_set_nonlinear.  Everything

@@ -100,6 +100,29 @@ class NonlinearMapResult:
         return f"NonlinearMapResult(outer={self.outer}, accepted={self.accepted}, converged={self.converged}, reason={self.reason}, energy={self.energy:.6g})"
 
 
+class RobustNonlinearMapResult:
+    """What LinearEngine.solve_map_nonlinear_robust returns: rounds (LM runs), outer / accepted / rejected / cg_iters (summed over the
+    rounds), converged, reason (_capi.LIN_IRLS_WEIGHTS / MOVE, or NONE when max_rounds ran out), flagged, energy0 / energy (the
+    weighted factor energy at the first and the last reweight), weight_change, move, grad_norm; round_trace (rounds + 1, 6): weighted
+    energy, flagged count, weight_change, the previous round's move, the LM iterations of the round and its LM reason; lm_trace
+    (outer, 5): the rounds' rows of solve_map_nonlinear one after the other; weights (F,) and robust_flag (F,) bool at the final x --
+    robust_flag is the outlier report.  The final x: LinearEngine.map_mean()."""
+    __slots__ = ('rounds', 'outer', 'accepted', 'rejected', 'cg_iters', 'converged', 'reason', 'flagged', 'energy0', 'energy', 'weight_change', 'move',
+                 'grad_norm', 'round_trace', 'lm_trace', 'weights', 'robust_flag')
+
+    def __init__(self, info, round_trace, lm_trace, weights, flag):
+        for k in ('rounds', 'outer', 'accepted', 'rejected', 'cg_iters', 'reason', 'flagged', 'energy0', 'energy', 'weight_change', 'move', 'grad_norm'):
+            setattr(self, k, getattr(info, k))
+        self.converged = bool(info.converged)
+        self.round_trace = round_trace[:info.rounds + 1].copy()
+        self.lm_trace = lm_trace[:info.outer].copy()
+        self.weights, self.robust_flag = weights, flag != 0
+
+    def __repr__(self):
+        return (f"RobustNonlinearMapResult(rounds={self.rounds}, outer={self.outer}, converged={self.converged}, reason={self.reason}, "
+                f"flagged={self.flagged}, energy={self.energy:.6g})")
+
+
 class LinearEngine:
     def __init__(self, var_a, var_b, factor_eta, factor_lam, prior_eta, prior_lam, factor_const=None, eta_damping=0.0, device=0):
         self._lib = _capi.load()
@@ -494,6 +517,27 @@ class LinearEngine:
         trace = np.full((max(int(max_outer), 1), 5), np.nan)
         check(self._lib.gbp_lin_solve_map_nonlinear(self._h, ct.byref(o), dptr(trace), ct.byref(i)))
         return NonlinearMapResult(i, trace)
+
+    def solve_map_nonlinear_robust(self, max_rounds=20, tol_weight=1e-9, tol_move=1e-10, max_outer=50, init='means', lambda0=1e-4, lambda_up=10.0,
+                                   lambda_down=0.1, lambda_min=1e-12, lambda_max=1e8, tol_step=1e-10, tol_grad=1e-8, rel_tol=1e-12, max_iters=10000,
+                                   check_every=8):
+        """The robust nonlinear batch MAP (gbp_lin_solve_map_nonlinear_robust): rounds of "make the weights of set_robust()'s losses at
+        x, minimise at those weights by solve_map_nonlinear's Levenberg-Marquardt loop" until the weights (tol_weight) or x (tol_move)
+        stop changing -- the fixed point robust relinearising GBP converges to, independent of any sweep.  The options after tol_move
+        are solve_map_nonlinear's, used by every round; init names the start of the first.  Neither the sweep's state nor the engine's
+        own weights() are written.  Returns a RobustNonlinearMapResult; the final x is map_mean()."""
+        if init not in ('means', 'map'):
+            raise ValueError("init is 'means' or 'map'")
+        lm = _capi.LinNlmapOpts(int(max_outer), _capi.LIN_NLMAP_FROM_MAP if init == 'map' else _capi.LIN_NLMAP_FROM_MEANS, float(lambda0), float(lambda_up),
+                                float(lambda_down), float(lambda_min), float(lambda_max), float(tol_step), float(tol_grad),
+                                _capi.LinMapOpts(float(rel_tol), int(max_iters), int(check_every), 0))
+        o = _capi.LinIrlsOpts(int(max_rounds), 0, float(tol_weight), float(tol_move), lm)
+        i = _capi.LinIrlsInfo()
+        rounds, outer = max(int(max_rounds), 0), max(int(max_outer), 0)
+        rt, lt = np.full((rounds + 1, 6), np.nan), np.full((max(rounds * outer, 1), 5), np.nan)
+        w, flag = np.ones(self.F), np.zeros(self.F, dtype=np.int32)
+        check(self._lib.gbp_lin_solve_map_nonlinear_robust(self._h, ct.byref(o), dptr(rt), dptr(lt), dptr(w), iptr(flag), ct.byref(i)))
+        return RobustNonlinearMapResult(i, rt, lt, w, flag)
 
     def map_mean(self):
         mu = np.empty((self.N, self.D))

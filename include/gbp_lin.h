@@ -486,7 +486,7 @@ int  gbp_lin_iterate_until_nonlinear(gbp_lin_t *h, const gbp_lin_until_opts_t *o
  *   Phi(x) = sum_f w_f 0.5 |h_f(x) - diag(s_f) z_f|^2 + sum_v (0.5 x_v^T Lambda0_v x_v - eta0_v^T x_v)
  * over x in R^(N D): the first sum is what gbp_lin_energy reports (factors only, w_f = 1 without losses), the second the priors, the
  * folded priors of gbp_lin_shrink_nonlinear included.  THE WEIGHTS ARE FIXED during the call, at what they are when it is made:
- * iteratively reweighted solves are out of scope (call gbp_lin_robustify_nonlinear and solve again).
+ * iteratively reweighted solves are gbp_lin_solve_map_nonlinear_robust below, which makes weights of its own at its own x.
  * It neither reads nor writes the sweep's state, except for the belief means when they are the starting point: messages, beliefs,
  * means, the handle's eta_f / Lambda_f, linpoint, iters_since_relin, per-factor damping, weights, flags and both count buffers are bit
  * for bit what they were, whatever the call returns.
@@ -552,6 +552,73 @@ typedef struct { int32_t outer, accepted, rejected, cg_iters, converged, reason;
                  double energy0, energy, grad_norm, lambda; } gbp_lin_nlmap_info_t;
 int gbp_lin_solve_map_nonlinear(gbp_lin_t *h, const gbp_lin_nlmap_opts_t *opts,
                                 double *trace /* host, max_outer x 5, or NULL */, gbp_lin_nlmap_info_t *info /* or NULL */);
+
+/* ---- The ROBUST nonlinear batch MAP by reweighted Levenberg-Marquardt ----
+ * With losses set, gbp_lin_solve_map_nonlinear minimises at the weights as they stand -- weights the sweeps made at whatever
+ * linearisation points they had reached, so its answer depends on the state of the thing it is a yardstick for.  What robust nonlinear
+ * GBP converges to is independent of any sweep: at a fixed point of synchronous_iteration(local_relin=True, robustify=True)
+ * (gbp.py:86-92) the linpoints equal the means, the weights are Factor.robustify_loss at those linpoints (gbp.py:296-332), and the
+ * means solve the joint at that linearisation and those weights (gbp.py:94-144):
+ *     x* = argmin_x  sum_f w_f(x*) 0.5 |h_f(x) - diag(s_f) z_f|^2 + priors(x),     w_f(x*) = the reference's weight from M_f(x*).
+ * This call finds x* as the fixed point of "make the weights at x, minimise at those weights, repeat" -- iteratively reweighted least
+ * squares with the reference's own, ENERGY-MATCHED weights (Huber: w 0.5 M^2 = t M - 0.5 t^2; not the textbook rho'/M) -- and reports
+ * the weights and the flags (M_f > t_f: the closures the optimum calls outliers) at x*.
+ *
+ * x is the solver's own point, as in gbp_lin_solve_map_nonlinear; the weights and flags are arrays of the solver's own too, NEVER the
+ * handle's (gbp_lin_get_weights).
+ *   Reweight r = 0, 1, ...: every factor with a loss gets the weight and flag of gbp.py:311-328 from M_f = |diag(s_f) z_f - h_f(x)| at
+ *     the solver's x, noise variance 1 as on every nonlinear handle, with the handle's own loss / threshold
+ *     (gbp_lin_set_robust_nonlinear); a factor at GBP_LIN_LOSS_NONE, and every factor of a handle without losses, gets 1 / 0.  The same
+ *     lane leaves the linearisation at x, the weighted energy sum_f w_f 0.5 M_f^2, weight_change = max_f |w_new - w_old| (defined as 0
+ *     at r = 0) and the number of flagged factors.
+ *   Stop test at r >= 1, in this order: tol_weight > 0 and weight_change <= tol_weight: reason WEIGHTS; tol_move > 0 and
+ *     move_{r-1} <= tol_move: reason MOVE.  With max_rounds spent: reason NONE, converged 0, GBP_OK.  The final weights are therefore
+ *     always the ones made at the final x: a run of R rounds makes R + 1 reweights and writes R + 1 rows.
+ *   Round r: exactly the Levenberg-Marquardt loop of gbp_lin_solve_map_nonlinear (options `lm`) at those weights, from x, started at
+ *     lm.lambda0; its first linearisation is the one the reweight made.  move_r = max |x_end - x_start| over the round.  A round that
+ *     ends in STALL or NONE is not an error: the loop goes on to the next reweight.
+ * round_trace row r: the weighted energy at the reweight, the flagged count, weight_change, move_{r-1} (0 at r = 0), the LM outer
+ * iterations of round r and its GBP_LIN_NLMAP_* reason (both 0 on the last row).  lm_trace: the rows gbp_lin_solve_map_nonlinear would
+ * have written, round after round WITHOUT gaps (round r's rows follow round r - 1's; column 4 of round_trace says how many each has;
+ * info->outer rows in all).  weights / robust_flag: w_f and M_f > t_f at the final x.
+ * info: rounds run, outer / accepted / rejected / cg_iters summed over the rounds, flagged / energy / weight_change / move of the last
+ * reweight, energy0 of the first, grad_norm of the last round.
+ * NULL opts = { max_rounds 20, 0, tol_weight 1e-9, tol_move 1e-10, lm = the defaults of gbp_lin_solve_map_nonlinear }.
+ * The final x lands where gbp_lin_solve_map leaves its iterate, map_solved set and the LDL^T stale, exactly as after
+ * gbp_lin_solve_map_nonlinear.  Like that call it WRITES NOTHING OF THE SWEEP, whatever it returns: messages, beliefs, means, the
+ * handle's eta_f / Lambda_f, linpoint, iters, damping, THE HANDLE'S WEIGHTS AND FLAGS and the count buffers stay bit for bit; only the
+ * means are read, when lm.init is FROM_MEANS.  Its arrays (weights, flags, a copy of x, partials) join that call's workspace: allocated
+ * all or nothing on first use, dropped with a generation, and a repeated call of the same size allocates nothing.  No floating-point
+ * atomics: two identical call sequences on two handles give bit-identical x, traces, weights and flags (the flagged count is integer
+ * adds).
+ * Refusals, all before anything changes: a handle that is not nonlinear, and the GBP_ESTATE rules of lm.init: GBP_ESTATE.
+ * max_rounds < 0, a tolerance negative or not finite, every GBP_EINVAL rule of gbp_lin_nlmap_opts_t: GBP_EINVAL.
+ * A handle WITHOUT LOSSES is legal: every weight is 1, round 1's reweight finds weight_change == 0, and with tol_weight > 0 the call
+ * ends after one round, reason WEIGHTS, its x bit-identical to gbp_lin_solve_map_nonlinear with opts->lm.
+ * Without variables: GBP_OK, converged, WEIGHTS, 0 rounds (one row of zeros).  Without factors: one round of one exact step, then
+ * WEIGHTS.  max_rounds == 0: one reweight at x0, x = x0, and weights / robust_flag describe x0.
+ * Out of scope: writing the solver's weights back into the handle; rho'/M weights or a Triggs correction; covariances at the robust
+ * MAP (gbp_lin_solve_marginals still describes the joint at the sweeps' linearisation and weights). */
+#define GBP_LIN_IRLS_NONE    0   /* max_rounds ran out                                              */
+#define GBP_LIN_IRLS_WEIGHTS 1   /* the weights made at x differ from the round's by <= tol_weight  */
+#define GBP_LIN_IRLS_MOVE    2   /* the last round moved x by <= tol_move                           */
+typedef struct {
+    int32_t max_rounds;          /* >= 0                                                            */
+    int32_t reserved;
+    double tol_weight;           /* > 0: on; 0: off                                                 */
+    double tol_move;             /* > 0: on; 0: off                                                 */
+    gbp_lin_nlmap_opts_t lm;     /* every round: the options of gbp_lin_solve_map_nonlinear; lm.init
+                                    names x0 of round 0 only, later rounds start where the last ended;
+                                    every round starts at lm.lambda0                                */
+} gbp_lin_irls_opts_t;
+typedef struct { int32_t rounds, outer, accepted, rejected, cg_iters, converged, reason, flagged;
+                 double energy0, energy, weight_change, move, grad_norm; } gbp_lin_irls_info_t;
+int gbp_lin_solve_map_nonlinear_robust(gbp_lin_t *h, const gbp_lin_irls_opts_t *opts,
+        double *round_trace /* host, (max_rounds + 1) x 6, or NULL */,
+        double *lm_trace    /* host, max_rounds * lm.max_outer x 5, or NULL: the rounds' LM rows, one after the other */,
+        double *weights     /* host, F, or NULL: w_f at the final x */,
+        int32_t *robust_flag/* host, F, or NULL: M_f(x) > t_f at the final x */,
+        gbp_lin_irls_info_t *info /* or NULL */);
 
 #ifdef __cplusplus
 }

@@ -58,6 +58,10 @@ ap.add_argument('--nonlinear-map', action='store_true',
                 help='time per outer iteration of gbp_lin_solve_map_nonlinear (Levenberg-Marquardt on the device) on the SE(3) ring and chain, beside its counted '
                      'bytes and its two nearest existing pieces: the relinearise kernel of an all-relinearising sweep and a gbp_lin_solve_map of the same CG '
                      'iteration count; writes profiles/linear_nonlinear_map.json')
+ap.add_argument('--nonlinear-map-robust', action='store_true',
+                help='gbp_lin_solve_map_nonlinear_robust on the graphs of --nonlinear-map: one reweight launch against the linearise launch of the parent '
+                     "commit's gbp_lin_solve_map_nonlinear, a full robust solve with 5 %% of the closures corrupted, and the existing paths against "
+                     '--parent-lib (required); writes profiles/linear_nonlinear_map_robust.json')
 ap.add_argument('--parent-lib', default=None, help="--nonlinear-live / --nonlinear-robust / --nonlinear-until: the parent commit's libgbp_hip.so, loaded beside this one for the yardsticks")
 ap.add_argument('--parent-results', default=None,
                 help="--extend / --shrink / --until / --nonlinear: a file of lines 'parent {json}' / 'here {json}', each the JSON line of a plain run of this tool from the parent "
@@ -1182,6 +1186,132 @@ def nonlinear_map_profile():
     print(json.dumps(out))
 
 
+def nonlinear_map_robust_profile():
+    """Host clock around whole calls, each ending in a stream synchronise, after a warm-up of every form; --repeats alternating rounds,
+    medians reported, spread = (max - min) / median.  On the 100k-pose SE(3) ring with k = 5 (500k factors) and the 500k-pose chain with
+    k = 1 (se3_graph), the Huber loss at threshold 4 on every factor that is no odometry (the ring) / on every factor (the chain), and
+    5 % of those factors' measurements corrupted by (1.5, -1, 0.8, 0.3, -0.2, 0.25).  `reweight`: gbp_lin_solve_map_nonlinear_robust with
+    max_rounds = 0 and no weights / flags asked for -- the means gathered, ONE k_gn_reweight launch, its finish, four doubles downloaded, x
+    copied; `reweight_with_report`: the same with the weights (F doubles) and flags (F int32) brought back.  `linearise_parent`:
+    gbp_lin_solve_map_nonlinear with max_outer = 0 on a handle of the PARENT commit's library (--parent-lib, loaded beside this one) --
+    the means gathered, ONE k_gn_factor<MODEL, true> launch, its finish, four doubles downloaded, x copied: the same call shape around
+    the kernel the reweight lane extends.  `lm_here` / `lm_parent`: gbp_lin_solve_map_nonlinear (max_outer 4, tolerances off, lambda0
+    1e-3, --steps CG iterations per inner solve at rel_tol 1e-30) on a handle WITHOUT losses of either library -- the loop both entry
+    points now share.  `robust_solve`: one full gbp_lin_solve_map_nonlinear_robust from the belief means (max_rounds 10, the rounds at
+    tol_grad 1e-3, tol_step 0, inner solves to 1e-10 in at most 2000 iterations), timed once per repeat: rounds, LM iterations, ms.
+    The existing sweeps and gbp_lin_solve_map against the parent: both libraries in one session on the 200k x 3 SE(2) ring (k = 5),
+    alternating, once with either library's handle created first (balanced = the geometric mean of the two orders)."""
+    import ctypes as ct
+    from gbp_amd import _capi
+    if not a.parent_lib:
+        raise SystemExit("--nonlinear-map-robust needs --parent-lib: its yardsticks are measured on the parent commit's library")
+    here, parent = _capi.load(), ct.CDLL(os.path.abspath(a.parent_lib))
+    for lib in (here, parent):
+        for name in ('gbp_lin_solve_map_nonlinear', 'gbp_lin_solve_map', 'gbp_lin_iterate', 'gbp_lin_iterate_nonlinear', 'gbp_lin_sync'):
+            getattr(lib, name).restype = ct.c_int
+    runs = []
+
+    def raw_lm(h, outer):
+        o = _capi.LinNlmapOpts(outer, 0, 1e-3, 10.0, 0.1, 1e-12, 1e8, 0.0, 0.0, _capi.LinMapOpts(1e-30, int(a.steps), 8, 0))
+        i = _capi.LinNlmapInfo()
+        t = time.perf_counter()
+        assert h.lib.gbp_lin_solve_map_nonlinear(h.h, ct.byref(o), None, ct.byref(i)) == 0
+        return 1e3 * (time.perf_counter() - t), i.outer
+
+    for N, k in ((100_000, 5), (500_000, 1)):
+        rs = np.random.RandomState(0)
+        va, vb, z, s, pe, pl = se3_graph(N, k, rs)
+        F = va.shape[0]
+        lossy = np.ones(F, bool) if k == 1 else (np.abs(vb - va) != 1) & (np.abs(vb - va) != N - 1)
+        bad = lossy & (rs.uniform(size=F) < 0.05)
+        z = z.copy()
+        z[bad] += np.array([1.5, -1.0, 0.8, 0.3, -0.2, 0.25])
+        e = LinearEngine.se3_pose_graph(va, vb, z, s, pe, pl, float('inf'), 4, 2, eta_damping=0.4)
+        e.set_robust(['huber' if l else None for l in lossy], np.full(F, 4.0))
+        hh = RawSE2(here, va, vb, z, s, pe, pl, float('inf'), 2, model=2)
+        hp = RawSE2(parent, va, vb, z, s, pe, pl, float('inf'), 2, model=2)
+        res = {}
+
+        def reweight():                                     # through the C ABI with no weights / flags asked for: nothing but four doubles comes back
+            o = _capi.LinIrlsOpts(0, 0, 1e-9, 1e-10, _capi.LinNlmapOpts(4, 0, 1e-3, 10.0, 0.1, 1e-12, 1e8, 0.0, 0.0, _capi.LinMapOpts(1e-30, int(a.steps), 8, 0)))
+            i = _capi.LinIrlsInfo()
+            t = time.perf_counter()
+            assert e._lib.gbp_lin_solve_map_nonlinear_robust(e._h, ct.byref(o), None, None, None, None, ct.byref(i)) == 0
+            return 1e3 * (time.perf_counter() - t)
+
+        def reweight_with_report():                         # the same with weights (F doubles) and flags (F int32) downloaded
+            t = time.perf_counter()
+            res['rw'] = e.solve_map_nonlinear_robust(max_rounds=0)
+            return 1e3 * (time.perf_counter() - t)
+
+        def robust_solve():
+            t = time.perf_counter()
+            res['full'] = e.solve_map_nonlinear_robust(max_rounds=10, tol_grad=1e-3, tol_step=0.0, rel_tol=1e-10, max_iters=2000)
+            return 1e3 * (time.perf_counter() - t)
+        forms = {'reweight': reweight, 'reweight_with_report': reweight_with_report, 'linearise_parent': lambda: raw_lm(hp, 0)[0], 'lm_here': lambda: raw_lm(hh, 4)[0] / 4, 'lm_parent': lambda: raw_lm(hp, 4)[0] / 4,
+                 'robust_solve': robust_solve}
+        rec = {key: [] for key in forms}
+        for fn_ in forms.values():
+            fn_()
+        for i in range(a.repeats):                          # alternating, the order turned round every other round
+            for key in (list(forms) if i % 2 == 0 else list(forms)[::-1]):
+                rec[key].append(forms[key]())
+        med = {key: statistics.median(v) for key, v in rec.items()}
+        spread = {key: (max(v) - min(v)) / med[key] for key, v in rec.items()}
+        full = res['full']
+        runs.append({"vars": N, "dofs": 6, "k": k, "factors": F, "lossy_factors": int(lossy.sum()), "corrupted": int(bad.sum()), "ms": med, "spread": spread,
+                     "ms_all": rec, "reweight_over_parent_linearise": med['reweight'] / med['linearise_parent'],
+                     "lm_here_over_parent": med['lm_here'] / med['lm_parent'], "flagged_at_x0": int(res['rw'].flagged),
+                     "robust_solve": {"rounds": full.rounds, "lm_iterations": full.outer, "rejected": full.rejected, "cg_iters": full.cg_iters,
+                                      "reason": full.reason, "converged": full.converged, "flagged": int(full.flagged), "energy0": full.energy0,
+                                      "energy": full.energy, "ms": med['robust_solve']},
+                     "counters_collected": False})
+        e.close(); hh.close(); hp.close()
+
+    n = a.steps
+    va, vb, z, s, pe, pl = se2_graph(200_000, 5, np.random.RandomState(0))
+    vs_parent = {}
+    for order in ('parent_created_first', 'here_created_first'):
+        first, second = (parent, here) if order == 'parent_created_first' else (here, parent)
+        h1 = RawSE2(first, va, vb, z, s, pe, pl, float('inf'), 2)
+        h2 = RawSE2(second, va, vb, z, s, pe, pl, float('inf'), 2)
+        hp, hh = (h1, h2) if order == 'parent_created_first' else (h2, h1)
+        for call in ('gbp_lin_iterate_nonlinear', 'gbp_lin_iterate', 'gbp_lin_solve_map'):
+            def run(h):
+                t = time.perf_counter()
+                if call == 'gbp_lin_solve_map':
+                    o, i = _capi.LinMapOpts(1e-30, int(n), 8, 0), _capi.LinMapInfo()
+                    assert h.lib.gbp_lin_solve_map(h.h, ct.byref(o), ct.byref(i)) == 0 and i.iters == n
+                else:
+                    rc = h.lib.gbp_lin_iterate_nonlinear(h.h, ct.c_int32(n), None) if call == 'gbp_lin_iterate_nonlinear' else h.lib.gbp_lin_iterate(h.h, ct.c_int32(n))
+                    assert rc == 0 and h.lib.gbp_lin_sync(h.h) == 0
+                return n / (time.perf_counter() - t)
+            run(hp); run(hh)
+            tp, th = [], []
+            for _ in range(a.repeats):
+                tp.append(run(hp)); th.append(run(hh))
+            mp, mh = statistics.median(tp), statistics.median(th)
+            sp, sh = (max(tp) - min(tp)) / mp, (max(th) - min(th)) / mh
+            vs_parent[call + '_' + order] = {"per_s_parent": mp, "per_s_here": mh, "ratio_here_over_parent": mh / mp, "spread_parent": sp, "spread_here": sh,
+                                             "margin": max(sp, sh), "beyond_margin": abs(mh / mp - 1.0) > max(sp, sh)}
+        hp.close(); hh.close()
+    for call in ('gbp_lin_iterate_nonlinear', 'gbp_lin_iterate', 'gbp_lin_solve_map'):
+        r1, r2 = (vs_parent[call + '_' + o]["ratio_here_over_parent"] for o in ('parent_created_first', 'here_created_first'))
+        vs_parent[call + '_balanced'] = (r1 * r2) ** 0.5
+    out = {"what": "tools/bench_linear.py --nonlinear-map-robust on one MI355X: gbp_lin_solve_map_nonlinear_robust on the 100k x 6 SE(3) ring (k = 5) and the "
+                   "500k-pose chain (k = 1) with 5 % of the lossy factors corrupted",
+           "method": " ".join(nonlinear_map_robust_profile.__doc__.split()), "repeats": a.repeats, "cg_iters_cap": a.steps, "runs": runs,
+           "existing_paths_vs_parent": vs_parent}
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'profiles', 'linear_nonlinear_map_robust.json')
+    with open(path, 'w') as fh:
+        json.dump(out, fh, indent=1)
+        fh.write('\n')
+    print(json.dumps(out))
+
+
+if a.nonlinear_map_robust:
+    nonlinear_map_robust_profile()
+    sys.exit(0)
 if a.nonlinear_map:
     nonlinear_map_profile()
     sys.exit(0)
