@@ -8,6 +8,7 @@
 //   h = diag(s) [ c dx + s_ dy ;  -s_ dx + c dy ;  theta_b - theta_a ]
 //   J = diag(s) [ -c  -s_  (-s_ dx + c dy) |  c   s_  0 ;   s_ -c  (-c dx - s_ dy) | -s_  c  0 ;   0  0  -1 | 0  0  1 ]
 //   Lambda_f = J^T J,  eta_f = J^T (J x0 + diag(s) z - h(x0))                                      (gbp.py:280-289, noise variance 1)
+// where J x0 - h(x0) is formed as what is left after its cancellation, diag(s) [ (-s_ dx + c dy) theta_a ; (-c dx - s_ dy) theta_a ; 0 ].
 // Angles are never wrapped: the reference does not wrap, and the caller keeps theta continuous.
 // GBP_LIN_MODEL_SE3_BETWEEN (D = M = 6): x = (t, w), R = Exp(w) by Rodrigues; with Q = R_a^T, u = Q (t_b - t_a), E = Q R_b, phi = Log(E)
 //   h = diag(s) [ u ; phi ]
@@ -15,6 +16,9 @@
 //                  0   -Jr^-1(phi) E^T Jr(w_a)    0   Jr^-1(phi) Jr(w_b) ]
 //   Jr(w) = I - (1 - cos th)/th^2 [w]x + (th - sin th)/th^3 [w]x^2,   Jr^-1(phi) = I + 1/2 [phi]x + (1/th^2 - (1 + cos th)/(2 th sin th)) [phi]x^2
 // with the coefficients from their series below th = 0.2 (se3_coeffs, se3_jrinv_coeff) and Log from atan2(|skew part|, trace part).
+// Beside pi both change form, since (1 + cos th)/sin th is 0/0 there and the skew part sin th * axis vanishes: past th = 2.6 the
+// coefficient is 1/th^2 - cot(th/2)/(2 th), and past cos th = -0.875 Log takes the axis from the symmetric part cos th I +
+// (1 - cos th) a a^T (se3_log).  The model is then good to rounding on all of |phi| < pi (fixture G31, tests/golden/make_g31.py).
 // w is never wrapped either (|w| > pi is legal; Jr(w) loses rank at |w| = 2 pi k); relative rotations stay below pi.  J is block
 // sparse: Lambda_f is made block by block from the five 3 x 3 blocks and every entry is stored as it is made (factor_store) -- no
 // 6 x 12 J, no 78 products held at once.
@@ -98,12 +102,21 @@ GBP_HD void se3_coeffs(double t, double &A, double &B, double &C)
     }
 }
 
-// 1/th^2 - (1 + cos th) / (2 th sin th) from t = th^2, 0 <= th < pi: the coefficient of [phi]x^2 in Jr^-1(phi)
+// The rotations past which Log and Jr^-1 take their forms for the neighbourhood of pi: th > 2.6 for the coefficient (t = th^2) and
+// cos th < -0.875 (th > 2.636) for Log.  Below them nothing computes differently from the forms that lose digits only near pi.
+constexpr double SE3_NEAR_PI_T = 6.76, SE3_NEAR_PI_COS = -0.875;
+
+// 1/th^2 - (1 + cos th) / (2 th sin th) from t = th^2, 0 <= th < pi: the coefficient of [phi]x^2 in Jr^-1(phi).  (1 + cos th) / sin th
+// is 0 / 0 at pi and loses eps / (pi - th) before it; it equals cot(th / 2), which has no cancellation there: past th = 2.6 that form.
 GBP_HD double se3_jrinv_coeff(double t)
 {
     if (t < 0.04) return 1.0 / 12 + t * (1.0 / 720 + t * (1.0 / 30240 + t * (1.0 / 1209600 + t * (1.0 / 47900160 + t * (691.0 / 1307674368000.0)))));
     double sn, cs;
     const double th = sqrt(t);
+    if (t > SE3_NEAR_PI_T) {
+        sincos(0.5 * th, &sn, &cs);
+        return 1.0 / t - cs / (2.0 * th * sn);
+    }
     sincos(th, &sn, &cs);
     return 1.0 / t - (1.0 + cs) / (2.0 * th * sn);
 }
@@ -141,11 +154,26 @@ GBP_HD double se3_wtmul(const double (&X)[9], const double (&w)[3], const double
 
 // Log of a rotation matrix, the principal value: the skew part is sin th * axis and the trace part cos th, so th = atan2 of the two is
 // accurate at small and at moderate angles alike (acos of the trace alone loses half the digits near 0); |phi| < pi is the domain.
+// The skew part vanishes at pi, and an axis taken from it loses eps / (pi - th).  Past cos th = SE3_NEAR_PI_COS the axis a comes from
+// the symmetric part (E + E^T) / 2 = cos th I + (1 - cos th) a a^T instead: the component with the largest diagonal entry from a square
+// root (a_k^2 >= 1/3: no cancellation), the other two from the off-diagonal entries (1 - cos th) a_k a_j divided by it (the square root
+// of a small diagonal difference would lose half the digits), the sign from the skew part (sin th > 0), the angle from the same atan2.
+// Selects, no indexing: everything stays in registers.
 GBP_HD void se3_log(const double (&E)[9], double (&phi)[3])
 {
     const double v0 = 0.5 * (E[7] - E[5]), v1 = 0.5 * (E[2] - E[6]), v2 = 0.5 * (E[3] - E[1]);
     const double nv = sqrt(v0 * v0 + v1 * v1 + v2 * v2);
-    const double th = atan2(nv, 0.5 * (E[0] + E[4] + E[8] - 1.0));
+    const double cs = 0.5 * (E[0] + E[4] + E[8] - 1.0);
+    const double th = atan2(nv, cs);
+    if (cs < SE3_NEAR_PI_COS) {
+        const bool k0 = E[0] >= E[4] && E[0] >= E[8], k1 = !k0 && E[4] >= E[8];
+        const double s01 = 0.5 * (E[1] + E[3]), s02 = 0.5 * (E[2] + E[6]), s12 = 0.5 * (E[5] + E[7]), oc = 1.0 - cs;
+        const double ak = copysign(sqrt(((k0 ? E[0] : k1 ? E[4] : E[8]) - cs) / oc), k0 ? v0 : k1 ? v1 : v2), den = oc * ak;
+        phi[0] = th * (k0 ? ak : (k1 ? s01 : s02) / den);
+        phi[1] = th * (k1 ? ak : (k0 ? s01 : s12) / den);
+        phi[2] = th * (k0 ? s02 / den : k1 ? s12 / den : ak);
+        return;
+    }
     const double k = nv > 0.0 ? th / nv : 1.0;
     phi[0] = k * v0; phi[1] = k * v1; phi[2] = k * v2;
 }
@@ -254,23 +282,21 @@ GBP_HD double nonlin_energy(const double (&x)[2 * NonlinModel<MODEL>::D], const 
 }
 
 // Factor.compute_factor at linpoint x (gbp.py:280-289) of a model with a dense J (SE(2)): eta_f [6], Lambda_f packed upper [21] (the
-// layout k_lin_factor reads).  sincos once: h and J share it.
+// layout k_lin_factor reads).
 template <int MODEL>
 GBP_HD void nonlin_factor(const double (&x)[6], const double (&z)[3], const double (&s)[3], double (&eta)[6], double (&lam)[Sym<6>::size])
 {
     static_assert(NonlinModel<MODEL>::dense && NonlinModel<MODEL>::D == 3 && NonlinModel<MODEL>::M == 3, "a block-sparse model has factor_store");
     constexpr int M = 3;
-    double sn, c, h[3], J[3][6], b[3];
-    sincos(x[2], &sn, &c);                                  // once: h and J share it
-    NonlinModel<MODEL>::h(x, s, c, sn, h);
+    double sn, c, J[3][6], b[3];
+    sincos(x[2], &sn, &c);
     NonlinModel<MODEL>::jac(x, s, c, sn, J);
-#pragma unroll
-    for (int k = 0; k < M; ++k) {                        // J x0 + diag(s) z - h(x0)
-        double v = s[k] * z[k] - h[k];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) v += J[k][i] * x[i];
-        b[k] = v;
-    }
+    // b = J x0 + diag(s) z - h(x0) with what cancels cancelled, as factor_store does for SE(3): the translation columns of J times x0
+    // are h's first two rows and (theta_b - theta_a) its third, so only the theta_a column is left.  Added up term by term the sum loses
+    // eps |x0| s -- with angles that are never wrapped, of any size.
+    b[0] = s[0] * z[0] + J[0][2] * x[2];
+    b[1] = s[1] * z[1] + J[1][2] * x[2];
+    b[2] = s[2] * z[2];
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
         double e = 0.0;

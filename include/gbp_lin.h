@@ -278,6 +278,8 @@ int  gbp_lin_get_alloc_count(gbp_lin_t *h, int32_t *count);
  *               [  s_ -c   (-c dx - s_ dy) | -s_  c   0 ]
  *               [  0   0        -1         |  0   0   1 ]
  *   Lambda_f = J^T J,  eta_f = J^T (J x0 + diag(s) z - h(x0))  at the linearisation point x0         (gbp.py:280-289, noise variance 1)
+ * (J x0 - h(x0) is formed after its cancellation, as diag(s) [ (-s_ dx + c dy) theta_a ; (-c dx - s_ dy) theta_a ; 0 ]: eta_f is accurate
+ * to rounding whatever the size of the angles and translations).
  * ANGLES ARE NOT WRAPPED anywhere -- not in h, not in the distance of the relinearisation test, not in the beliefs -- because the
  * reference does not wrap: the caller keeps theta continuous along the trajectory (a pose 1.5 turns on has theta = 3 pi + ...).
  *
@@ -289,10 +291,14 @@ int  gbp_lin_get_alloc_count(gbp_lin_t *h, int32_t *count);
  *   J = diag(s) [ -R_a^T   [u]x Jr(w_a)               R_a^T   0                   ]
  *               [  0       -Jr^-1(phi) E^T Jr(w_a)    0       Jr^-1(phi) Jr(w_b)  ]
  *   Jr(w)      = I - (1 - cos th)/th^2 [w]x + (th - sin th)/th^3 [w]x^2                              (th = |w|; series near 0)
- *   Jr^-1(phi) = I + 1/2 [phi]x + (1/th^2 - (1 + cos th)/(2 th sin th)) [phi]x^2                     (th = |phi|; series near 0)
+ *   Jr^-1(phi) = I + 1/2 [phi]x + (1/th^2 - (1 + cos th)/(2 th sin th)) [phi]x^2                     (th = |phi|; series near 0;
+ *                the coefficient as 1/th^2 - cot(th/2)/(2 th) past th = 2.6: the first form is 0/0 at pi)
+ *   Log(E):      th = atan2(|skew part|, trace part); the axis from the skew part sin th a, and past cos th = -0.875, where that
+ *                vanishes, from the symmetric part (E + E^T)/2 = cos th I + (1 - cos th) a a^T
  *   Lambda_f = J^T J,  eta_f = J^T (J x0 + diag(s) z - h(x0))                                        (gbp.py:280-289, noise variance 1)
  * THE DOMAIN, as SE(2)'s "angles are never wrapped": w IS NEVER WRAPPED, and the caller keeps it continuous along the trajectory;
  * |w| > pi is legal.  Relative rotations -- Log(R_a^T R_b) at every point a factor is evaluated at -- and z_w stay below pi in norm.
+ * On all of |phi| < pi, up to pi itself, h, eta_f and Lambda_f are accurate to rounding: no digits are lost as |phi| nears pi.
  * Jr(w) loses rank at |w| = 2 pi k, k >= 1: a pose there has a direction of w that turns nothing.
  *
  * gbp_lin_set_nonlinear (Factor(meas_fn=, jac_fn=) gbp.py:207-208, 237-239; compute_all_factors gbp.py:60-62, 273-276; the per-factor

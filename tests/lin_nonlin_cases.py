@@ -27,6 +27,16 @@ def se2_jac(x, s):
     return s[:, :, None] * J
 
 
+def se2_b(J, x0, z, s):
+    """J x0 + diag(s) z - h(x0) with what cancels cancelled, as nonlin_factor (gbp_lin_nonlin.hpp) forms it: the translation columns of J
+    times x0 are h's first two rows and theta_b - theta_a its third, so only the theta_a column is left.  Summed term by term it loses
+    eps |x0| s, which unwrapped angles make as large as one likes (fixture G31, the SE(2) block).  The twin below keeps the
+    reference's term-by-term sum (gbp.py:287): at the sizes of its graphs the two differ by rounding."""
+    b = s * z
+    b[:, 0:2] += J[:, 0:2, 2] * x0[:, 2:3]
+    return b
+
+
 class NonlinTwin:
     """FactorGraph(nonlinear_factors=True) for SE(2) relative-pose factors, vectorised over the factors."""
 

@@ -13,6 +13,7 @@ D = 6
 SQRT_INFO = np.array([10.0, 10.0, 10.0, 20.0, 20.0, 20.0])
 AXIS = np.array([1.0, 2.0, 2.0]) / 3.0
 SERIES_BELOW = 0.04             # th^2 below which the coefficients come from their series (gbp_lin_nonlin.hpp: th < 0.2)
+NEAR_PI_T, NEAR_PI_COS = 6.76, -0.875       # th^2 / cos th past which Jr^-1's coefficient / Log take their forms for the neighbourhood of pi
 
 
 # ---- the model ------------------------------------------------------------------------------------------------------------------------
@@ -42,11 +43,13 @@ def coeffs(t):
 
 
 def jrinv_coeff(t):
-    small = t < SERIES_BELOW
+    """1/th^2 - (1 + cos th) / (2 th sin th) from t = th^2; past th = 2.6 in the half-angle form 1/th^2 - cot(th / 2) / (2 th)."""
+    small, near = t < SERIES_BELOW, t > NEAR_PI_T
     th = np.sqrt(np.where(small, 1.0, t))
     tt = np.where(small, 1.0, t)
+    half = np.where(near, 0.5 * th, 1.0)
     return np.where(small, _poly(t, [1.0 / 12, 1.0 / 720, 1.0 / 30240, 1.0 / 1209600, 1.0 / 47900160, 691.0 / 1307674368000.0]),
-                    1.0 / tt - (1.0 + np.cos(th)) / (2.0 * th * np.sin(th)))
+                    np.where(near, 1.0 / tt - np.cos(half) / (2.0 * th * np.sin(half)), 1.0 / tt - (1.0 + np.cos(th)) / (2.0 * th * np.sin(th))))
 
 
 def ik(w, a, b):
@@ -56,10 +59,24 @@ def ik(w, a, b):
 
 
 def so3_log(E):
+    """The principal Log: axis from the skew part, angle from atan2(|skew part|, trace part); past cos th = NEAR_PI_COS the axis from the
+    symmetric part cos th I + (1 - cos th) a a^T -- its largest diagonal entry by a square root, the other two components by division
+    of the off-diagonal entries, the sign from the skew part (gbp_lin_nonlin.hpp, se3_log)."""
     v = 0.5 * np.stack([E[:, 2, 1] - E[:, 1, 2], E[:, 0, 2] - E[:, 2, 0], E[:, 1, 0] - E[:, 0, 1]], 1)
     nv = np.linalg.norm(v, axis=1)
-    th = np.arctan2(nv, 0.5 * (np.trace(E, axis1=1, axis2=2) - 1.0))
-    return np.where(nv > 0, th / np.where(nv > 0, nv, 1.0), 1.0)[:, None] * v
+    cs = 0.5 * (np.trace(E, axis1=1, axis2=2) - 1.0)
+    th = np.arctan2(nv, cs)
+    out = np.where(nv > 0, th / np.where(nv > 0, nv, 1.0), 1.0)[:, None] * v
+    near = cs < NEAR_PI_COS
+    if near.any():
+        En, vn, c, r = E[near], v[near], cs[near], np.arange(int(near.sum()))
+        k = np.argmax(np.stack([En[:, 0, 0], En[:, 1, 1], En[:, 2, 2]], 1), axis=1)      # the first of equal entries, as the engine's selects
+        oc = 1.0 - c
+        ak = np.copysign(np.sqrt((En[r, k, k] - c) / oc), vn[r, k])
+        a = 0.5 * (En[r, k, :] + En[r, :, k]) / (oc * ak)[:, None]
+        a[r, k] = ak
+        out[near] = th[near, None] * a
+    return out
 
 
 def se3_parts(x):

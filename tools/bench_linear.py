@@ -62,6 +62,9 @@ ap.add_argument('--nonlinear-map-robust', action='store_true',
                 help='gbp_lin_solve_map_nonlinear_robust on the graphs of --nonlinear-map: one reweight launch against the linearise launch of the parent '
                      "commit's gbp_lin_solve_map_nonlinear, a full robust solve with 5 %% of the closures corrupted, and the existing paths against "
                      '--parent-lib (required); writes profiles/linear_nonlinear_map_robust.json')
+ap.add_argument('--model-cost', action='store_true',
+                help='the kernels that evaluate the SE(3) / SE(2) models (relinearise, energy, the Gauss-Newton linearise and reweight calls, a sweep) '
+                     'of this library against --parent-lib (required), alternating; prints one JSON line')
 ap.add_argument('--parent-lib', default=None, help="--nonlinear-live / --nonlinear-robust / --nonlinear-until: the parent commit's libgbp_hip.so, loaded beside this one for the yardsticks")
 ap.add_argument('--parent-results', default=None,
                 help="--extend / --shrink / --until / --nonlinear: a file of lines 'parent {json}' / 'here {json}', each the JSON line of a plain run of this tool from the parent "
@@ -1309,6 +1312,96 @@ def nonlinear_map_robust_profile():
     print(json.dumps(out))
 
 
+def model_cost_profile():
+    """Every kernel that evaluates the pose models, this library against the PARENT commit's (--parent-lib, required, loaded beside
+    this one), through the C ABI on handles of the same graph.  Host clock around whole calls, each ending in a stream synchronise, after
+    a warm-up of every form; --repeats alternating rounds, the order of the two libraries turned round every other round; medians,
+    ratio = here / parent in time, spread = (max - min) / median; all of it once with the parent's handles created first and once with
+    this library's (ratio_balanced: the geometric mean of the two).  On the 100k-pose SE(3) ring with k = 5 (se3_graph: no relative
+    rotation comes near the branch for the neighbourhood of pi, as in every graph the benchmarks run): `relin_all` --steps sweeps of
+    gbp_lin_iterate_nonlinear at beta = 0, min_linear_iters = 0, where k_lin_relin<SE3> re-makes every factor in every sweep;
+    `relin_none` the same at beta = +inf: an SE(3) sweep in which nothing relinearises; `energy` gbp_lin_energy (k_lin_energy_nl<SE3>);
+    `linearise` gbp_lin_solve_map_nonlinear with max_outer = 0 (one k_gn_factor<SE3, true> launch); `reweight`
+    gbp_lin_solve_map_nonlinear_robust with max_rounds = 0 and the Huber loss at 4 on every factor (one k_gn_reweight<SE3> launch).
+    `se2_relin_all`: the first form on the 200k-pose SE(2) ring with k = 5 (se2_graph)."""
+    import ctypes as ct
+    from gbp_amd import _capi
+    if not a.parent_lib:
+        raise SystemExit("--model-cost needs --parent-lib")
+    libs = {'here': _capi.load(), 'parent': ct.CDLL(os.path.abspath(a.parent_lib))}
+    for lib in libs.values():
+        for name in ('gbp_lin_solve_map_nonlinear', 'gbp_lin_solve_map_nonlinear_robust', 'gbp_lin_set_robust_nonlinear', 'gbp_lin_energy'):
+            getattr(lib, name).restype = ct.c_int
+    n = a.steps
+
+    def lm0(h):
+        o = _capi.LinNlmapOpts(0, 0, 1e-3, 10.0, 0.1, 1e-12, 1e8, 0.0, 0.0, _capi.LinMapOpts(1e-30, 8, 8, 0))
+        t = time.perf_counter()
+        assert h.lib.gbp_lin_solve_map_nonlinear(h.h, ct.byref(o), None, ct.byref(_capi.LinNlmapInfo())) == 0
+        return 1e3 * (time.perf_counter() - t)
+
+    def irls0(h):
+        o = _capi.LinIrlsOpts(0, 0, 1e-9, 1e-10, _capi.LinNlmapOpts(4, 0, 1e-3, 10.0, 0.1, 1e-12, 1e8, 0.0, 0.0, _capi.LinMapOpts(1e-30, 8, 8, 0)))
+        t = time.perf_counter()
+        assert h.lib.gbp_lin_solve_map_nonlinear_robust(h.h, ct.byref(o), None, None, None, None, ct.byref(_capi.LinIrlsInfo())) == 0
+        return 1e3 * (time.perf_counter() - t)
+
+    def energy(h):
+        out = ct.c_double()
+        t = time.perf_counter()
+        assert h.lib.gbp_lin_energy(h.h, ct.byref(out)) == 0
+        return 1e3 * (time.perf_counter() - t)
+
+    rec = {}
+
+    def measure(order, forms):
+        """forms: {name: (fn, handles by library)}"""
+        for name, (fn, hs) in forms.items():
+            for who in ('parent', 'here'):
+                fn(hs[who])
+        for i in range(a.repeats):
+            for name, (fn, hs) in forms.items():
+                for who in (('parent', 'here') if i % 2 == 0 else ('here', 'parent')):
+                    rec.setdefault(name, {}).setdefault(order, {'parent': [], 'here': []})[who].append(fn(hs[who]))
+
+    g3, g2 = se3_graph(100_000, 5, np.random.RandomState(0)), se2_graph(200_000, 5, np.random.RandomState(0))
+    F3 = g3[0].shape[0]
+    codes, thr = _capi.i32(np.ones(F3)), np.full(F3, 4.0)
+    # where a handle's arrays land moves a sweep by several per cent: every form is measured with either library's handle created first
+    for first in ('parent', 'here'):
+        who = (first, 'here' if first == 'parent' else 'parent')
+        order = first + '_created_first'
+        all3 = {w: RawSE2(libs[w], *g3, 0.0, 0, model=2) for w in who}
+        none3 = {w: RawSE2(libs[w], *g3, float('inf'), 2, model=2) for w in who}
+        lossy3 = {w: RawSE2(libs[w], *g3, float('inf'), 2, model=2) for w in who}
+        for h in lossy3.values():
+            assert h.lib.gbp_lin_set_robust_nonlinear(h.h, 0, F3, _capi.iptr(codes), _capi.dptr(thr)) == 0
+        measure(order, {'relin_all': (lambda h: h.sweeps(n), all3), 'relin_none': (lambda h: h.sweeps(n), none3), 'energy': (energy, none3),
+                        'linearise': (lm0, none3), 'reweight': (irls0, lossy3)})
+        for hs in (all3, none3, lossy3):
+            for h in hs.values():
+                h.close()
+        all2 = {w: RawSE2(libs[w], *g2, 0.0, 0) for w in who}
+        measure(order, {'se2_relin_all': (lambda h: h.sweeps(n), all2)})
+        for h in all2.values():
+            h.close()
+    res = {}
+    for name, by in rec.items():
+        res[name] = {}
+        for order, v in by.items():
+            mp, mh = statistics.median(v['parent']), statistics.median(v['here'])
+            res[name][order] = {"ms_parent": mp, "ms_here": mh, "ratio_here_over_parent": mh / mp, "spread_parent": (max(v['parent']) - min(v['parent'])) / mp,
+                                "spread_here": (max(v['here']) - min(v['here'])) / mh, "ms_all_parent": v['parent'], "ms_all_here": v['here']}
+        r1, r2 = (res[name][o]["ratio_here_over_parent"] for o in ('parent_created_first', 'here_created_first'))
+        res[name]["ratio_balanced"] = (r1 * r2) ** 0.5
+    print(json.dumps({"what": "tools/bench_linear.py --model-cost on one MI355X: the kernels that evaluate the SE(3) / SE(2) models, this library "
+                              "against the parent commit's", "method": " ".join(model_cost_profile.__doc__.split()), "repeats": a.repeats,
+                      "sweeps_per_call": n, "se3_factors": F3, "se2_factors": int(g2[0].shape[0]), "counters_collected": False, "results": res}))
+
+
+if a.model_cost:
+    model_cost_profile()
+    sys.exit(0)
 if a.nonlinear_map_robust:
     nonlinear_map_robust_profile()
     sys.exit(0)
